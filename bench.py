@@ -10,7 +10,11 @@ GPU (scalars and the committer key already resident in HBM), result normalised t
 With N > 1 each rank owns a disjoint shard of the key (weak scaling: 2^log2n pairs per GPU, the job is
 one N*2^log2n-pair MSM); ranks all-gather their 128-byte partial sums over RCCL and fold them.
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit/..., plus
+Prints ONE JSON line on rank 0: metric/value/unit/n_gpus/steps/warmup/ms_per_step/higher_is_better/scaling/dtype/data and
+a `config` that describes the workload.  A plain run does only that: set-up, preheat, W warm-up steps, the K timed steps, the
+outputs (--dump-outputs DIR) and the line.  --full measures everything else as well, after and outside the timed region:
+  "value_cold":   config.value_cold, the same K steps timed from an idle device (before the preheat);
+  "config":       the synchronous, host-scalar, host-slice-batch, one-shot and plain-key rates, key memory, pipeline counters;
   "roofline":     the dominant kernel (bucket accumulation) against the HBM roofline, achieved =
                   algorithmic bytes (96 B per pair) / mean kernel time measured
                   with hipEvents on the engine's stream inside the timed region;
@@ -23,6 +27,14 @@ Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/un
                   accumulator twice, MakeZK::Enabled) and the lighter n_all = 2 no-zk shape, each verified, decided and
                   serialised; measured after and outside the timed region (--no-schemes skips).  N > 1: `accumulations_multi_device`,
                   the same harness over one multi-device context of the N GPUs.
+(--no-cpu-baseline, --no-bls, --no-schemes, --cpu-log2n and --cpu-leg-max-log2 trim a --full run; a plain run has none of it.)
+
+--dump-outputs DIR writes the result of the LAST timed step, as a caller of the batch call receives it, into DIR:
+  msm_xy.npy        float64 (2, 2 * limbs): the affine x and y in Montgomery form, as 32-bit words, least significant first
+                    (the u32 view of the C ABI's 64-bit limbs; every word is exact in float64);
+  msm_infinity.npy  float64 (1,): 1.0 if the result is the point at infinity.
+The inputs are generated from fixed seeds (SEED_SCALARS, SEED_POINTS), so two builds run with the same arguments compare output
+for output.
 
     python bench.py --gpus N --single-process [--devices 0,1,...]
 runs the N-GPU job from ONE process through the multi-device context of the C ABI (amsm_ctx_create_multi: key sharded over
@@ -79,6 +91,11 @@ def main() -> int:
                     help="drive all --gpus devices from this process through amsm_ctx_create_multi (no torchrun)")
     ap.add_argument("--devices", default=None, help="--single-process: comma-separated device ids (default 0..gpus-1; an id "
                                                     "may repeat: several shards on one GPU, numbers meaningless)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline (cold clocks, other call shapes, roofline and stage times, "
+                         "CPU baseline, BLS12-381, accumulations/sec): minutes instead of seconds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result to DIR/*.npy (float64; see the module docstring)")
     args = ap.parse_args()
     if args.single_process:
         return main_single_process(args)
@@ -155,11 +172,11 @@ def main() -> int:
             elif world == 1:
                 pts, infs = VariableBaseMSM.multi_scalar_mul_batch(ck, [vecs[i % n_distinct] for i in range(k)],
                                                                    mont=False)
-                last["xy"], last["inf"] = pts[0], bool(infs[0])
+                last["xy"], last["inf"] = pts[-1], bool(infs[-1])
                 last["all"] = (np.array(pts), np.array(infs))
             else:
                 outs, infs = sharded.msm_batch([vecs[i % n_distinct] for i in range(k)], mont=False)
-                last["xy"], last["inf"] = outs[0], bool(infs[0])
+                last["xy"], last["inf"] = outs[-1], bool(infs[-1])
 
         def sync_all():
             torch.cuda.synchronize()
@@ -174,90 +191,95 @@ def main() -> int:
         # the metric is about, so the device is kept busy with PREHEAT untimed MSMs of the same workload before the W warm-up steps
         # (reported as config.preheat_msms; --no-preheat measures from cold clocks).  The timed region is still exactly K steps.
         # value_cold (round 5): the SAME K steps timed the way rounds 1-3 did -- W warm-up steps after an idle
-        # device, no preheat -- reported beside `value` in the same line so that rounds stay comparable whatever the protocol
+        # device, no preheat -- reported beside `value` in the same line so that rounds stay comparable whatever the protocol (--full)
         elapsed_cold = None
         if not args.no_preheat:
-            sync_all()
-            time.sleep(0.25)  # idle clocks, as a freshly started process finds them
-            run_steps(args.warmup)
-            sync_all()
-            t0 = time.perf_counter()
-            run_steps(args.steps)
-            sync_all()
-            elapsed_cold = time.perf_counter() - t0
+            if args.full:
+                sync_all()
+                time.sleep(0.25)  # idle clocks, as a freshly started process finds them
+                run_steps(args.warmup)
+                sync_all()
+                t0 = time.perf_counter()
+                run_steps(args.steps)
+                sync_all()
+                elapsed_cold = time.perf_counter() - t0
             run_steps(PREHEAT_MSMS)
         run_steps(args.warmup)
-        ctx.set_profiling(True)
+        ctx.set_profiling(args.full)  # (the per-stage events feed `roofline` and `stage_ms` only)
         sync_all()
         t0 = time.perf_counter()
         run_steps(args.steps)
         sync_all()
         elapsed = time.perf_counter() - t0
-        stage_ms = ctx.stage_ms()
-        ctx.set_profiling(False)
-        # latency of ONE synchronous MSM call (no overlap between consecutive MSMs), for reference
-        out = np.zeros((2 * ctx.fq_limbs,), dtype=np.uint64)
-        inf = C.c_uint8(0)
-        ctx.set_profiling(True)
-        t1 = time.perf_counter()
-        for _ in range(5):
-            ffi.check(ctx._lib.amsm_msm_device(ctx._h, ck._h, 0, scalars.ptr, n, 0, _ptr(out), C.byref(inf)),
-                      "amsm_msm_device")
-        ms_sync = (time.perf_counter() - t1) / 5 * 1e3
-        stage_ms_alone = ctx.stage_ms()  # stages of the last blocking call: nothing else on the GPU
-        ctx.set_profiling(False)
-        # the PCIe-inclusive form (`amsm_msm`: the scalars start in pageable host memory like a Rust `&[BigInt]`); never `value`
-        h_scalars = scalars.download()
-        ffi.check(ctx._lib.amsm_msm(ctx._h, ck._h, 0, _ptr(h_scalars), n, 0, _ptr(out), C.byref(inf)), "amsm_msm")
-        t1 = time.perf_counter()
-        for _ in range(5):
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last["xy"], last["inf"])
+        ms_sync = ms_host = ms_host_batch = pipe = plain_rate = witness_rate = ms_dev_batch12 = oneshot = None
+        if args.full:
+            stage_ms = ctx.stage_ms()
+            ctx.set_profiling(False)
+            # latency of ONE synchronous MSM call (no overlap between consecutive MSMs), for reference
+            out = np.zeros((2 * ctx.fq_limbs,), dtype=np.uint64)
+            inf = C.c_uint8(0)
+            ctx.set_profiling(True)
+            t1 = time.perf_counter()
+            for _ in range(5):
+                ffi.check(ctx._lib.amsm_msm_device(ctx._h, ck._h, 0, scalars.ptr, n, 0, _ptr(out), C.byref(inf)),
+                          "amsm_msm_device")
+            ms_sync = (time.perf_counter() - t1) / 5 * 1e3
+            stage_ms_alone = ctx.stage_ms()  # stages of the last blocking call: nothing else on the GPU
+            ctx.set_profiling(False)
+            # the PCIe-inclusive form (`amsm_msm`: the scalars start in pageable host memory like a Rust `&[BigInt]`); never `value`
+            h_scalars = scalars.download()
             ffi.check(ctx._lib.amsm_msm(ctx._h, ck._h, 0, _ptr(h_scalars), n, 0, _ptr(out), C.byref(inf)), "amsm_msm")
-        ms_host = (time.perf_counter() - t1) / 5 * 1e3
-        # ... and the same host slices handed over back to back, the way the reference's provers call `commit`
-        # (src/hp_as/mod.rs:372-385): amsm_msm_batch overlaps the upload of vector v + 1 with MSM v
-        ms_host_batch = pipe = plain_rate = witness_rate = ms_dev_batch12 = oneshot = None
-        if world == 1:
-            oneshot = oneshot_line(ctx, ck, h_scalars, n, out.copy(), bool(inf.value))
-            h_vecs = [v.download() for v in vecs]
-            VariableBaseMSM.multi_scalar_mul_batch_host(ck, [h_vecs[i % n_distinct] for i in range(3)])
-            reps = 12
-            # like with like: the device-resident batch of the SAME length (pipeline fill and drain weigh more in 12 MSMs than in K)
             t1 = time.perf_counter()
-            VariableBaseMSM.multi_scalar_mul_batch(ck, [vecs[i % n_distinct] for i in range(reps)], mont=False)
-            ms_dev_batch12 = (time.perf_counter() - t1) / reps * 1e3
-            t1 = time.perf_counter()
-            hb_pts, hb_inf = VariableBaseMSM.multi_scalar_mul_batch_host(ck, [h_vecs[i % n_distinct] for i in range(reps)])
-            ms_host_batch = (time.perf_counter() - t1) / reps * 1e3
-            if "all" in last and not (np.array_equal(hb_pts[:n_distinct], last["all"][0][:n_distinct])):
-                raise SystemExit("host-slice batch differs from the device-resident batch")
-            del h_vecs
-            pipe = ctx.pipeline_stats()
-            pipe["two_valued"] = ctx.two_valued_msms()  # 0 here: the timed vectors are uniform
-            # the TRUE variable-base rate: no precomputed multiples (what an ark-ec `[patch]` that passes its bases per
-            # call gets, or pays ~50 ms of table building per new base set to avoid)
-            if not args.no_precompute and args.log2n <= 21:
-                ck_plain = CommitterKey.generate(ctx, SEED_POINTS + rank, n, ffi.AMSM_BASES_NO_PRECOMPUTE)
-                VariableBaseMSM.multi_scalar_mul_batch(ck_plain, [vecs[i % n_distinct] for i in range(3)], mont=False)
+            for _ in range(5):
+                ffi.check(ctx._lib.amsm_msm(ctx._h, ck._h, 0, _ptr(h_scalars), n, 0, _ptr(out), C.byref(inf)), "amsm_msm")
+            ms_host = (time.perf_counter() - t1) / 5 * 1e3
+            # ... and the same host slices handed over back to back, the way the reference's provers call `commit`
+            # (src/hp_as/mod.rs:372-385): amsm_msm_batch overlaps the upload of vector v + 1 with MSM v
+            if world == 1:
+                oneshot = oneshot_line(ctx, ck, h_scalars, n, out.copy(), bool(inf.value))
+                h_vecs = [v.download() for v in vecs]
+                VariableBaseMSM.multi_scalar_mul_batch_host(ck, [h_vecs[i % n_distinct] for i in range(3)])
+                reps = 12
+                # like with like: the device-resident batch of the SAME length (pipeline fill and drain weigh more in 12 MSMs than in K)
                 t1 = time.perf_counter()
-                pp, pi = VariableBaseMSM.multi_scalar_mul_batch(ck_plain, [vecs[i % n_distinct] for i in range(12)], mont=False)
-                plain_rate = 12 * n / (time.perf_counter() - t1)  # (batches of 12, like the host-slice lines above)
-                if "all" in last and not np.array_equal(pp[:4], last["all"][0][:4]):
-                    raise SystemExit("plain-key MSM differs from the precomputed-key MSM")
-                # ... and over a vector that looks like an R1CS witness: 10 % of the scalars are boolean wires (0 or 1).  ark-ec adds
-                # the bases of unit scalars directly; here they are summed apart since round 5 (amsm_ctx_unit_scalar_msms) -- before,
-                # all of them landed in bucket 1 of the lowest window and this batch ran 2.3x slower than the uniform one
-                hw = vecs[0].download().copy()
-                pick = np.random.default_rng(SEED_SCALARS).random(n) < 0.1
-                bits = np.zeros_like(hw)
-                bits[:, 0] = np.random.default_rng(SEED_SCALARS + 1).integers(0, 2, n)
-                hw[pick] = bits[pick]
-                wv = ctx.upload(hw)
-                VariableBaseMSM.multi_scalar_mul_batch(ck_plain, [wv] * 3, mont=False)
+                VariableBaseMSM.multi_scalar_mul_batch(ck, [vecs[i % n_distinct] for i in range(reps)], mont=False)
+                ms_dev_batch12 = (time.perf_counter() - t1) / reps * 1e3
                 t1 = time.perf_counter()
-                VariableBaseMSM.multi_scalar_mul_batch(ck_plain, [wv] * 12, mont=False)
-                witness_rate = 12 * n / (time.perf_counter() - t1)
-                wv.free()
-                ck_plain.free()
+                hb_pts, hb_inf = VariableBaseMSM.multi_scalar_mul_batch_host(ck, [h_vecs[i % n_distinct] for i in range(reps)])
+                ms_host_batch = (time.perf_counter() - t1) / reps * 1e3
+                m_chk = min(n_distinct, args.steps)  # (the timed batch's first steps used vectors 0, 1, ...)
+                if "all" in last and not (np.array_equal(hb_pts[:m_chk], last["all"][0][:m_chk])):
+                    raise SystemExit("host-slice batch differs from the device-resident batch")
+                del h_vecs
+                pipe = ctx.pipeline_stats()
+                pipe["two_valued"] = ctx.two_valued_msms()  # 0 here: the timed vectors are uniform
+                # the TRUE variable-base rate: no precomputed multiples (what an ark-ec `[patch]` that passes its bases per
+                # call gets, or pays ~50 ms of table building per new base set to avoid)
+                if not args.no_precompute and args.log2n <= 21:
+                    ck_plain = CommitterKey.generate(ctx, SEED_POINTS + rank, n, ffi.AMSM_BASES_NO_PRECOMPUTE)
+                    VariableBaseMSM.multi_scalar_mul_batch(ck_plain, [vecs[i % n_distinct] for i in range(3)], mont=False)
+                    t1 = time.perf_counter()
+                    pp, pi = VariableBaseMSM.multi_scalar_mul_batch(ck_plain, [vecs[i % n_distinct] for i in range(12)], mont=False)
+                    plain_rate = 12 * n / (time.perf_counter() - t1)  # (batches of 12, like the host-slice lines above)
+                    if "all" in last and not np.array_equal(pp[:m_chk], last["all"][0][:m_chk]):
+                        raise SystemExit("plain-key MSM differs from the precomputed-key MSM")
+                    # ... and over a vector that looks like an R1CS witness: 10 % of the scalars are boolean wires (0 or 1).  ark-ec adds
+                    # the bases of unit scalars directly; here they are summed apart since round 5 (amsm_ctx_unit_scalar_msms) -- before,
+                    # all of them landed in bucket 1 of the lowest window and this batch ran 2.3x slower than the uniform one
+                    hw = vecs[0].download().copy()
+                    pick = np.random.default_rng(SEED_SCALARS).random(n) < 0.1
+                    bits = np.zeros_like(hw)
+                    bits[:, 0] = np.random.default_rng(SEED_SCALARS + 1).integers(0, 2, n)
+                    hw[pick] = bits[pick]
+                    wv = ctx.upload(hw)
+                    VariableBaseMSM.multi_scalar_mul_batch(ck_plain, [wv] * 3, mont=False)
+                    t1 = time.perf_counter()
+                    VariableBaseMSM.multi_scalar_mul_batch(ck_plain, [wv] * 12, mont=False)
+                    witness_rate = 12 * n / (time.perf_counter() - t1)
+                    wv.free()
+                    ck_plain.free()
 
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
@@ -267,7 +289,7 @@ def main() -> int:
         t = torch.tensor([elapsed_cold], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed_cold = float(t.item())
-    if world > 1:  # what every rank holds, for the line's `ranks` (a bad curve should be diagnosable from the JSON alone)
+    if world > 1 and args.full:  # what every rank holds, for the line's `ranks` (a bad curve should be diagnosable from the JSON alone)
         mem = ctx.memory()
         mine = {"rank": rank, "key_bytes": key_bytes(ck, ctx, n), "workspace_bytes": mem["workspace_bytes"],
                 "host_pool_threads": int(ctx._lib.amsm_host_threads()), "pipeline_stats": ctx.pipeline_stats()}
@@ -283,10 +305,6 @@ def main() -> int:
 
     result = None
     if rank == 0:
-        bytes_per_pair = 32 + 16 * ctx.fq_limbs  # 32 B scalar + affine point (64 B Pallas / 96 B BLS12-381)
-        dom = "accum_l0"
-        dom_ms = stage_ms.get(dom, 0.0)
-        achieved = (n * bytes_per_pair / (dom_ms * 1e-3)) / 1e9 if dom_ms > 0 else 0.0
         result = {
             "metric": metric_name(args),
             "value": value,
@@ -310,68 +328,76 @@ def main() -> int:
                 "precomputed_key": bool(ck.precomputed),
                 "parallelism": f"point-sharded x{world}" + (" + one RCCL all-gather of the steps' partial records" if world > 1 else ""),
                 "key_setup_s": round(t_key, 3),
-                "ms_per_msm_synchronous_call": round(ms_sync, 4),
-                "ms_per_msm_host_scalars": round(ms_host, 4),
-                "pairs_per_s_host_scalars": round(n / (ms_host * 1e-3), 1),
-                # host slices, 12 per call (amsm_msm_batch): PCIe-inclusive like the line above, uploads overlapped
-                "ms_per_msm_host_scalars_batch": None if ms_host_batch is None else round(ms_host_batch, 4),
-                "pairs_per_s_host_scalars_batch": None if ms_host_batch is None else round(n / (ms_host_batch * 1e-3), 1),
-                # the device-resident batch of the same twelve MSMs, and the ratio the host slices reach of it
-                "pairs_per_s_device_batch_of_12": None if ms_dev_batch12 is None else round(n / (ms_dev_batch12 * 1e-3), 1),
-                "host_slices_fraction_of_device_batch_of_12": None if not (ms_dev_batch12 and ms_host_batch) else round(ms_dev_batch12 / ms_host_batch, 3),
-                "host_scalars_page_locked": "not measured: amsm_host_register is a documented no-op since round 5 -- page-locked slices never ran "
-                                            "faster than pageable ones and ran up to 27 % slower (profiles/r05_host_slices.md)",
-                # no precomputed multiples (one copy of the key, a bucket set per window): the variable-base rate
-                "pairs_per_s_plain_key": None if plain_rate is None else round(plain_rate, 1),
-                "pairs_per_s_plain_key_witness_10pct_booleans": None if witness_rate is None else round(witness_rate, 1),
-                # the ark-ec call shape itself: multi_scalar_mul(&[G], &[BigInt]) with BOTH slices in host memory, nothing resident
-                # (amsm_msm_oneshot): PCIe-bound -- its rate against 96 B per pair over the H2D rate measured in this run
-                "pairs_per_s_oneshot_host_bases": None if oneshot is None else oneshot.get("pairs_per_s"),
-                "oneshot_host_bases": oneshot,
-                "key_bytes": key_bytes(ck, ctx, n),
                 "window_bits": int(ck.window_bits),
                 "pipeline": ("bucket-per-lane (k_prep_local_t + k_accum_bpl; skewed scalars re-run chunked)"
                              if ck.window_bits == 20 else "chunked (k_accum_l0 + k_accum_l1)"),
                 "window_widths": "9 x 20 + 4 x 19 bits = 256 (MsmGeom::n_narrow)" if ck.window_bits == 20 else None,
-                "pipeline_stats": pipe,
                 "rccl_ranks": None if rank_info is None else (len(rank_info) if args.backend == "nccl" else 0),
                 "ranks": rank_info,
                 "msms_in_flight": 1 if args.sync else 3,
                 "preheat_msms": 0 if args.no_preheat else PREHEAT_MSMS,
-                # the --no-preheat protocol of rounds 1-3 on the same box, same process (whole-job pairs/s; max over ranks)
-                "value_cold": value_cold,
                 "host_pool_threads": int(ctx._lib.amsm_host_threads()),
                 "collective": None if world == 1 else (f"torch.distributed all_gather_into_tensor of {sharded.engine.record_bytes}-byte records, "
                                                         f"backend {args.backend}" + (f" (RCCL {rccl_version()})" if args.backend == "nccl" else "")),
                 "seeds": {"scalars": SEED_SCALARS, "points": SEED_POINTS},
+                "full": bool(args.full),
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": ("k_accum_bpl" if ck.window_bits == 20 else "k_accum_l0") + " (bucket accumulation)",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": pmc_traffic(args)[0],
-                "traffic_source": pmc_traffic(args)[1],
-                "kernel_ms": dom_ms,
-                "algorithmic_bytes_per_launch": n * bytes_per_pair,
-                # the kernel is integer-VALU bound, not HBM bound: the ceiling that binds is
-                # the issue rate of the 10-multiplication mixed addition measured in isolation (tools/fp_bench.hip)
-                "alu": alu_roofline(args, ck, n, dom_ms),
-                # a ceiling that does not come from this repo's own micro-benchmark: the multiplier's issue rate alone --
-                # 1024 SIMDs x 2.4 GHz / 5.2 cycles per wave64 v_mad_u64_u32 x 64 lanes / MADs per mixed addition
-                "alu_hw": alu_hw_roofline(args, ck, n, dom_ms),
-                # the same kernel with the GPU to itself (one blocking MSM call after the timed region)
-                "kernel_ms_unshared": stage_ms_alone.get(dom, 0.0),
-                "alu_unshared": alu_roofline(args, ck, n, stage_ms_alone.get(dom, 0.0)),
-            },
-            # elapsed device time per pipeline stage (hipEvent pairs on the stage's stream): inside the timed batch, where
-            # the prep chain of MSM k+1 and the tail of MSM k-1 share the GPU with accumulate L0 of MSM k (so the prep chain
-            # STRETCHES to about one L0: it is not queue wait), and for one blocking call with the GPU to itself
-            "stage_ms": {"in_batch": {k: round(v, 4) for k, v in stage_ms.items()},
-                         "blocking_call": {k: round(v, 4) for k, v in stage_ms_alone.items()}},
         }
+    if rank == 0 and args.full:
+        bytes_per_pair = 32 + 16 * ctx.fq_limbs  # 32 B scalar + affine point (64 B Pallas / 96 B BLS12-381)
+        dom = "accum_l0"
+        dom_ms = stage_ms.get(dom, 0.0)
+        achieved = (n * bytes_per_pair / (dom_ms * 1e-3)) / 1e9 if dom_ms > 0 else 0.0
+        result["config"].update({
+            "ms_per_msm_synchronous_call": round(ms_sync, 4),
+            "ms_per_msm_host_scalars": round(ms_host, 4),
+            "pairs_per_s_host_scalars": round(n / (ms_host * 1e-3), 1),
+            # host slices, 12 per call (amsm_msm_batch): PCIe-inclusive like the line above, uploads overlapped
+            "ms_per_msm_host_scalars_batch": None if ms_host_batch is None else round(ms_host_batch, 4),
+            "pairs_per_s_host_scalars_batch": None if ms_host_batch is None else round(n / (ms_host_batch * 1e-3), 1),
+            # the device-resident batch of the same twelve MSMs, and the ratio the host slices reach of it
+            "pairs_per_s_device_batch_of_12": None if ms_dev_batch12 is None else round(n / (ms_dev_batch12 * 1e-3), 1),
+            "host_slices_fraction_of_device_batch_of_12": None if not (ms_dev_batch12 and ms_host_batch) else round(ms_dev_batch12 / ms_host_batch, 3),
+            "host_scalars_page_locked": "not measured: amsm_host_register is a documented no-op since round 5 -- page-locked slices never ran "
+                                        "faster than pageable ones and ran up to 27 % slower (profiles/r05_host_slices.md)",
+            # no precomputed multiples (one copy of the key, a bucket set per window): the variable-base rate
+            "pairs_per_s_plain_key": None if plain_rate is None else round(plain_rate, 1),
+            "pairs_per_s_plain_key_witness_10pct_booleans": None if witness_rate is None else round(witness_rate, 1),
+            # the ark-ec call shape itself: multi_scalar_mul(&[G], &[BigInt]) with BOTH slices in host memory, nothing resident
+            # (amsm_msm_oneshot): PCIe-bound -- its rate against 96 B per pair over the H2D rate measured in this run
+            "pairs_per_s_oneshot_host_bases": None if oneshot is None else oneshot.get("pairs_per_s"),
+            "oneshot_host_bases": oneshot,
+            "key_bytes": key_bytes(ck, ctx, n),
+            "pipeline_stats": pipe,
+            # the --no-preheat protocol of rounds 1-3 on the same box, same process (whole-job pairs/s; max over ranks)
+            "value_cold": value_cold,
+        })
+        result["roofline"] = {
+            "bound": "hbm",
+            "kernel": ("k_accum_bpl" if ck.window_bits == 20 else "k_accum_l0") + " (bucket accumulation)",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "traffic": pmc_traffic(args)[0],
+            "traffic_source": pmc_traffic(args)[1],
+            "kernel_ms": dom_ms,
+            "algorithmic_bytes_per_launch": n * bytes_per_pair,
+            # the kernel is integer-VALU bound, not HBM bound: the ceiling that binds is
+            # the issue rate of the 10-multiplication mixed addition measured in isolation (tools/fp_bench.hip)
+            "alu": alu_roofline(args, ck, n, dom_ms),
+            # a ceiling that does not come from this repo's own micro-benchmark: the multiplier's issue rate alone --
+            # 1024 SIMDs x 2.4 GHz / 5.2 cycles per wave64 v_mad_u64_u32 x 64 lanes / MADs per mixed addition
+            "alu_hw": alu_hw_roofline(args, ck, n, dom_ms),
+            # the same kernel with the GPU to itself (one blocking MSM call after the timed region)
+            "kernel_ms_unshared": stage_ms_alone.get(dom, 0.0),
+            "alu_unshared": alu_roofline(args, ck, n, stage_ms_alone.get(dom, 0.0)),
+        }
+        # elapsed device time per pipeline stage (hipEvent pairs on the stage's stream): inside the timed batch, where
+        # the prep chain of MSM k+1 and the tail of MSM k-1 share the GPU with accumulate L0 of MSM k (so the prep chain
+        # STRETCHES to about one L0: it is not queue wait), and for one blocking call with the GPU to itself
+        result["stage_ms"] = {"in_batch": {k: round(v, 4) for k, v in stage_ms.items()},
+                              "blocking_call": {k: round(v, 4) for k, v in stage_ms_alone.items()}}
         if world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(ctx, ck, vecs, curve_id, args, out.copy(), bool(inf.value), last.get("all"))
         if world == 1 and not args.no_bls and args.log2n == 20 and args.curve == "pallas" and not args.no_precompute:
@@ -385,7 +411,7 @@ def main() -> int:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if not args.no_schemes and args.log2n == 20 and args.curve == "pallas":
+        if args.full and not args.no_schemes and args.log2n == 20 and args.curve == "pallas":
             if world == 1:
                 result["accumulations"] = scheme_rates(cpu_leg_max_log2=args.cpu_leg_max_log2)
             else:
@@ -608,6 +634,8 @@ def main_single_process(args) -> int:
     pts, infs = run_steps(args.steps)
     ctx.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pts[-1], infs[-1])
     result = {
         "metric": metric_name(args), "value": n * N * args.steps / elapsed,
         "unit": "pairs/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -616,9 +644,9 @@ def main_single_process(args) -> int:
                                f"process (amsm_ctx_create_multi), scalars resident per shard",
                    "pairs_per_gpu": n, "curve": args.curve, "devices": devices, "collective": ctx.collective,
                    "parallelism": f"point-sharded x{N}, single process, one host thread per device",
-                   "key_setup_s": round(t_key, 3), "seeds": {"scalars": SEED_SCALARS, "points": SEED_POINTS}},
+                   "key_setup_s": round(t_key, 3), "seeds": {"scalars": SEED_SCALARS, "points": SEED_POINTS}, "full": bool(args.full)},
     }
-    if not args.no_cpu_baseline and n * N <= (1 << 21):  # bit-exact check of the first step against the CPU restatement
+    if args.full and not args.no_cpu_baseline and n * N <= (1 << 21):  # bit-exact check of the first step against the CPU restatement
         from oracle import cref
         xy, _ = ck.read(0, n * N)
         sc = np.concatenate([slices[0][g].download() for g in range(N)])
@@ -628,6 +656,15 @@ def main_single_process(args) -> int:
     print(json.dumps(result), flush=True)
     ctx.close()
     return 0
+
+
+def dump_outputs(out_dir, xy, inf):
+    """The last timed step's MSM result as float64 .npy files (module docstring): the 64-bit Montgomery limbs split into their
+    32-bit words, which float64 holds exactly, so that two builds compare bit for bit."""
+    os.makedirs(out_dir, exist_ok=True)
+    words = np.ascontiguousarray(xy, dtype=np.uint64).reshape(2, -1).astype("<u8").view("<u4")
+    np.save(os.path.join(out_dir, "msm_xy.npy"), words.astype(np.float64))
+    np.save(os.path.join(out_dir, "msm_infinity.npy"), np.array([1.0 if inf else 0.0]))
 
 
 def oneshot_line(ctx, ck, h_scalars, n, ref_xy, ref_inf):

@@ -1,4 +1,5 @@
-"""bench.py's contract on a GPU box: the default N = 1 line carries every field the driver reads (plus `roofline`,
+"""bench.py's contract on a GPU box: a plain N = 1 run prints the headline line and, with --dump-outputs, the last timed step's
+result (bit-exact against the CPU restatement); the --full N = 1 line carries every field the driver reads (plus `roofline`,
 `cpu_baseline` and `accumulations`), and the N > 1 branch -- launched exactly like the driver launches it, but with both
 ranks on the one GPU of the test box and gloo instead of RCCL -- runs through its barrier / max-over-ranks timing / sharded
 MSM path and prints one line with n_gpus = 2."""
@@ -21,9 +22,42 @@ def _line(out):
     return json.loads(lines[0])
 
 
+def test_plain_line_and_dumped_outputs(built_lib, cref, tmp_path):
+    """The driver's plain command line: the headline fields only (nothing --full measures), K timed steps exactly, and the last
+    step's result in DIR/*.npy, float64, equal to the CPU restatement's MSM of the same seeded inputs"""
+    import numpy as np
+
+    import bench
+    from accumulation_amd import CommitterKey, Context, ffi
+    steps, log2n = 7, 16
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+                        "--log2n", str(log2n), "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r.stdout)
+    for k in KEYS[:-1]:
+        assert k in d, k
+    assert not {"roofline", "stage_ms", "cpu_baseline", "accumulations"} & set(d), sorted(d)
+    assert "value_cold" not in d["config"] and d["config"]["full"] is False
+    assert d["steps"] == steps and d["warmup"] == 2 and d["ms_per_step"] > 0
+    assert d["value"] * d["ms_per_step"] * 1e-3 == pytest.approx(1 << log2n, rel=1e-6)
+    xy, inf = np.load(out / "msm_xy.npy"), np.load(out / "msm_infinity.npy")
+    assert xy.dtype == np.float64 and inf.dtype == np.float64 and xy.shape == (2, 8) and inf.shape == (1,)
+    # the inputs bench.py generates: step k uses scalar vector k % 4
+    ctx = Context(ffi.AMSM_PALLAS, device=0)
+    ck = CommitterKey.generate(ctx, bench.SEED_POINTS, 1 << log2n, ffi.AMSM_BASES_PRECOMPUTE)
+    bases, _ = ck.read(0, 1 << log2n)
+    scalars = ctx.random_vector(bench.SEED_SCALARS + 1000 * ((steps - 1) % 4), 1 << log2n, mont=False).download()
+    ck.free()
+    ctx.close()
+    ref, ref_inf = cref.msm(ffi.AMSM_PALLAS, bases, scalars)
+    assert float(inf[0]) == float(bool(ref_inf))
+    assert np.array_equal(xy.astype(np.uint64).astype("<u4").view("<u8").reshape(-1), np.asarray(ref, dtype=np.uint64).reshape(-1))
+
+
 def test_default_line_n1(built_lib):
     # (--cpu-leg-max-log2 14: the CPU legs of `accumulations` at <= 2^14 -- the same code path in seconds instead of a minute)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--cpu-leg-max-log2", "14"], capture_output=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "12", "--warmup", "3", "--cpu-leg-max-log2", "14"], capture_output=True,
                        text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -70,7 +104,7 @@ def test_default_line_n1(built_lib):
 
 def test_single_process_two_shards_on_one_gpu(built_lib):
     """--single-process: the N-device job from one process through amsm_ctx_create_multi (both shards on GPU 0 here)"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-process", "--devices", "0,0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-process", "--full", "--devices", "0,0",
                         "--log2n", "16", "--steps", "4", "--warmup", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -84,7 +118,7 @@ def test_two_rank_branch_on_one_gpu(built_lib):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6",
-                        "--warmup", "2", "--backend", "gloo", "--one-gpu"], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                        "--warmup", "2", "--backend", "gloo", "--one-gpu", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -106,7 +140,7 @@ def test_eight_rank_branch_on_one_gpu(built_lib, strong):
     """The driver's 8-GPU command line with all eight ranks on the one GPU of this box (gloo; numbers meaningless): rendezvous, the
     rank table, max-over-ranks timing, eight 832 MiB keys + eight workspaces + eight host pools side by side -- what the first real
     8-rank run would otherwise meet for the first time."""
-    args = ["--gpus", "8", "--steps", "4", "--warmup", "1", "--backend", "gloo", "--one-gpu"] + (["--strong", "--no-schemes"] if strong else [])
+    args = ["--gpus", "8", "--steps", "4", "--warmup", "1", "--backend", "gloo", "--one-gpu", "--full"] + (["--strong", "--no-schemes"] if strong else [])
     r = _torchrun(8, 29561 + int(strong), os.path.join(ROOT, "bench.py"), *args)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     d = _line(r.stdout)

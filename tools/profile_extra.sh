@@ -35,7 +35,7 @@ for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         res[k][ctr + "_launches"] = len(v)
 json.dump(res, open(f"{out}/summary/pmc_vec_kernels.json", "w"), indent=1)
 PY
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_bls -- python3 $R/bench.py --curve bls12_381_g1 --steps 20 --warmup 4 --no-cpu-baseline --no-schemes > $OUT/trace_bls.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_bls -- python3 $R/bench.py --full --curve bls12_381_g1 --steps 20 --warmup 4 --no-cpu-baseline --no-schemes > $OUT/trace_bls.log 2>&1
 cp $(find $OUT/trace_bls -name "*kernel_stats.csv" | head -1) $OUT/summary/bench_bls12_381_kernel_stats.csv
 grep "^{\"metric\"" $OUT/trace_bls.log | tail -1 > $OUT/summary/bench_bls12_381.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_ipa -- $R/build/profile_as ipa_pc_as 16 16 --reps 5 --shape harness > $OUT/trace_ipa.log 2>&1
