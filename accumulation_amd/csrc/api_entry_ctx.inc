@@ -132,13 +132,15 @@ void amsm_ctx_destroy(amsm_ctx* c) {
   if (c->s_prep) (void)hipStreamSynchronize(c->s_prep);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->s_tail) (void)hipStreamSynchronize(c->s_tail);
+  if (c->s_copy) (void)hipStreamSynchronize(c->s_copy);
+  if (c->s_tv) (void)hipStreamSynchronize(c->s_tv);
+  auto free_buf = [](DevBuf& b) {
+    if (b.p) (void)hipFree(b.p);
+  };
+  for_each_ctx_buf(c, free_buf);
   for (int k = 0; k < N_SLOTS; k++) {
     Slot* sl = &c->slot[k];
-    DevBuf* bufs[] = {&sl->keys_a, &sl->keys_b, &sl->vals_a, &sl->vals_b, &sl->start, &sl->items, &sl->item_off,
-                      &sl->partials, &sl->buckets, &sl->red_out, &sl->fold_out, &sl->heavy, &sl->misc, &sl->sort_tmp,
-                      &sl->scan_tmp, &sl->prep_small, &sl->heavy_scratch, &sl->bpl_grp, &sl->bpl_order, &sl->red2_rc, &sl->ds_flags, &sl->red_ticket};
-    for (DevBuf* b : bufs)
-      if (b->p) (void)hipFree(b->p);
+    for_each_slot_buf(sl, free_buf);
     if (sl->h_pinned) (void)hipHostFree(sl->h_pinned);
     for (int i = 0; i <= ST_COUNT; i++)
       if (sl->ev[i]) (void)hipEventDestroy(sl->ev[i]);
@@ -153,31 +155,16 @@ void amsm_ctx_destroy(amsm_ctx* c) {
   if (c->s_prep) (void)hipStreamDestroy(c->s_prep);
   if (c->s_tail) (void)hipStreamDestroy(c->s_tail);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-  if (c->scalars.p) (void)hipFree(c->scalars.p);
-  if (c->probe_flags.p) (void)hipFree(c->probe_flags.p);
-  if (c->s_copy) {
-    (void)hipStreamSynchronize(c->s_copy);
-    (void)hipStreamDestroy(c->s_copy);
-  }
-  for (int k = 0; k < amsm_ctx::STAGE_RING; k++) {
-    if (c->stage_ring[k].p) (void)hipFree(c->stage_ring[k].p);
-    if (c->up_ev[k]) (void)hipEventDestroy(c->up_ev[k]);
-  }
-  if (c->xyzz_scratch.p) (void)hipFree(c->xyzz_scratch.p);
-  for (DevBuf* b : {&c->tv_flags, &c->tv_parts, &c->tv_out, &c->shared_buckets[0], &c->shared_buckets[1], &c->oneshot_table, &c->oneshot_inf})
-    if (b->p) (void)hipFree(b->p);
+  if (c->s_copy) (void)hipStreamDestroy(c->s_copy);
+  for (hipEvent_t e : c->up_ev)
+    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->shared_free)
     if (e) (void)hipEventDestroy(e);
   if (c->tv_pinned) (void)hipHostFree(c->tv_pinned);
-  if (c->s_tv) {
-    (void)hipStreamSynchronize(c->s_tv);
-    (void)hipStreamDestroy(c->s_tv);
-  }
+  if (c->s_tv) (void)hipStreamDestroy(c->s_tv);
   if (c->tv_done) (void)hipEventDestroy(c->tv_done);
   pool_release_all(c);
   pool_forget_ctx(c);
-  for (DevBuf* b : {&c->rec_send, &c->rec_recv, &c->stage})
-    if (b->p) (void)hipFree(b->p);
   if (c->multi_fork) (void)hipEventDestroy(c->multi_fork);
   delete c;
 }

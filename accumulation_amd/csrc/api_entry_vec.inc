@@ -140,16 +140,10 @@ int amsm_dev_free(amsm_ctx* c, void* d_ptr) {
 }
 int amsm_ctx_memory(const amsm_ctx* c, size_t* workspace_bytes, size_t* vectors_live_bytes, size_t* vectors_pooled_bytes) {
   if (!c) return AMSM_E_INVALID_ARG;
-  size_t ws = c->scalars.bytes + c->xyzz_scratch.bytes + c->rec_send.bytes + c->rec_recv.bytes + c->stage.bytes + c->tv_flags.bytes +
-              c->tv_parts.bytes + c->tv_out.bytes + c->shared_buckets[0].bytes + c->shared_buckets[1].bytes + c->oneshot_table.bytes + c->oneshot_inf.bytes;
-  for (int k = 0; k < amsm_ctx::STAGE_RING; k++) ws += c->stage_ring[k].bytes;
-  for (int k = 0; k < N_SLOTS; k++) {
-    const Slot* sl = &c->slot[k];
-    const DevBuf* bufs[] = {&sl->keys_a, &sl->keys_b, &sl->vals_a, &sl->vals_b, &sl->start, &sl->items, &sl->item_off,
-                            &sl->partials, &sl->buckets, &sl->red_out, &sl->fold_out, &sl->heavy, &sl->misc, &sl->sort_tmp,
-                            &sl->scan_tmp, &sl->prep_small, &sl->heavy_scratch, &sl->bpl_grp, &sl->bpl_order, &sl->red2_rc, &sl->ds_flags, &sl->red_ticket};
-    for (const DevBuf* b : bufs) ws += b->bytes;
-  }
+  size_t ws = 0;
+  auto count = [&](const DevBuf& b) { ws += b.bytes; };
+  for_each_ctx_buf(c, count);
+  for (const Slot& sl : c->slot) for_each_slot_buf(&sl, count);
   if (workspace_bytes) *workspace_bytes = ws;
   if (vectors_live_bytes) *vectors_live_bytes = c->pool_live_bytes;
   if (vectors_pooled_bytes) *vectors_pooled_bytes = c->pool_free_bytes;
@@ -162,29 +156,12 @@ int amsm_ctx_trim(amsm_ctx* c) {
   TRY(amsm_ctx_synchronize(c));
   pool_release_all(c);
   if (c->s_copy) (void)hipStreamSynchronize(c->s_copy);
-  DevBuf* own[] = {&c->scalars, &c->xyzz_scratch, &c->rec_send, &c->rec_recv, &c->stage, &c->probe_flags, &c->tv_flags, &c->tv_parts,
-                   &c->tv_out, &c->shared_buckets[0], &c->shared_buckets[1], &c->oneshot_table, &c->oneshot_inf};
-  for (DevBuf* b : own)
-    if (b->p) {
-      (void)hipFree(b->p);
-      *b = DevBuf();
-    }
-  for (int k = 0; k < amsm_ctx::STAGE_RING; k++)
-    if (c->stage_ring[k].p) {
-      (void)hipFree(c->stage_ring[k].p);
-      c->stage_ring[k] = DevBuf();
-    }
-  for (int k = 0; k < N_SLOTS; k++) {
-    Slot* sl = &c->slot[k];
-    DevBuf* bufs[] = {&sl->keys_a, &sl->keys_b, &sl->vals_a, &sl->vals_b, &sl->start, &sl->items, &sl->item_off,
-                      &sl->partials, &sl->buckets, &sl->red_out, &sl->fold_out, &sl->heavy, &sl->misc, &sl->sort_tmp,
-                      &sl->scan_tmp, &sl->prep_small, &sl->heavy_scratch, &sl->bpl_grp, &sl->bpl_order, &sl->red2_rc, &sl->ds_flags, &sl->red_ticket};
-    for (DevBuf* b : bufs)
-      if (b->p) {
-        (void)hipFree(b->p);
-        *b = DevBuf();
-      }
-  }
+  auto release = [](DevBuf& b) {
+    if (b.p) (void)hipFree(b.p);
+    b = DevBuf();
+  };
+  for_each_ctx_buf(c, release);
+  for (Slot& sl : c->slot) for_each_slot_buf(&sl, release);
   return AMSM_OK;
 }
 int amsm_dev_upload(amsm_ctx* c, void* d_dst, const void* h_src, size_t bytes) {

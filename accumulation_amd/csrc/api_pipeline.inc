@@ -54,6 +54,20 @@ int ensure_pinned(Slot* sl, size_t bytes) {
   return AMSM_OK;
 }
 
+// The slot's arrival counters of k_bucket_reduce_fold_quad, one per bucket set: zeroed when the buffer grows (a memset, then the
+// caller's stream is synchronised), left clear by every launch
+int ensure_red_ticket(amsm_ctx* ctx, Slot* sl, size_t n_sets) {
+  if (sl->red_ticket.bytes < n_sets * 4) {
+    TRY(ensure(sl->red_ticket, std::max<size_t>(n_sets * 4, 4096)));
+    // (hipMemset on device memory may return before it has run, and the null stream does not order the context's non-blocking
+    // streams: a reduction that found the counters not yet zeroed never saw its last workgroup -- one wrong sum in ~3 of 10 proves over
+    // eight contexts, none with the two-launch tail: profiles/r06_experiments.md section 1b)
+    HIP_TRY(hipMemsetAsync(sl->red_ticket.p, 0, sl->red_ticket.bytes, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  return AMSM_OK;
+}
+
 inline u32 cdiv(u32 a, u32 b) { return (a + b - 1) / b; }
 using msel::ilog2_ceil;
 
@@ -239,8 +253,6 @@ int prep_fork(amsm_ctx* ctx) {
   return AMSM_OK;
 }
 
-// Geometry and EVERY allocation of one MSM on slot `sl`, nothing launched: what can fail for lack of memory fails here, so a
-// caller with side effects to apply first (amsm_ipa_round_fused folds its vectors in place) can reserve before it commits.
 template <class Fq>
 int bases_alt(amsm_ctx* ctx, const amsm_bases* b, const amsm_bases** out);
 
@@ -314,8 +326,9 @@ inline bool bps_geom(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, si
 // bucket sets of 2^18 buckets and more reduce as row / column sums (msm_kernels.h: k_red2_*); smaller sets LOSE with that form
 // (measured: 2^15 buckets, 2^16 pairs 280 -> 212 M pairs/s) and keep the running-sum kernels
 inline bool red2_applies(const amsm_ctx*, const MsmGeom& g) { return g.nb >= (1u << 18) && (g.nb & 1023u) == 0u; }
-// Geometry and EVERY allocation of one MSM on slot `sl`, nothing launched: what can fail for lack of memory fails here, so a caller
-// with side effects to apply first (amsm_ipa_round_fused folds its vectors in place) can reserve before it commits.
+// Geometry and EVERY allocation of one MSM on slot `sl`: what can fail for lack of memory fails here, so a caller with side effects
+// to apply first (amsm_ipa_round_fused folds its vectors in place) can reserve before it commits.  Nothing of the MSM is launched;
+// when the slot's arrival counters grow, their zeroing is (a memset, and the caller's stream is synchronised: ensure_red_ticket).
 // *eff = the key the MSM runs over: `bases`, or its 17-bit twin when msm_select.h sends a range of a 20-bit key there.
 template <class Fq>
 int msm_plan(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, size_t base_off, size_t n, int group_shift, bool* short_prep_out,
@@ -334,15 +347,7 @@ int msm_plan(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, size_t base_off, 
     TRY(ensure(sl->red_out, (size_t)g.n_sets * red_blocks * rec));
     TRY(ensure(sl->fold_out, (size_t)g.n_sets * rec + 64));
     TRY(ensure_pinned(sl, g.n_sets * rec + 64));
-    if (sl->red_ticket.bytes < (size_t)g.n_sets * 4) {  // one arrival counter per set: zeroed once, left clear by every launch
-      TRY(ensure(sl->red_ticket, std::max<size_t>((size_t)g.n_sets * 4, 4096)));
-      // (hipMemset on device memory may return before it has run, and the null stream does not order the context's non-blocking
-      // streams: a reduction that found the counters not yet zeroed never saw its last workgroup -- one wrong sum in ~3 of 10 proves over
-      // eight contexts, none with the two-launch tail: profiles/r06_experiments.md section 1b)
-      HIP_TRY(hipMemsetAsync(sl->red_ticket.p, 0, sl->red_ticket.bytes, ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    return AMSM_OK;
+    return ensure_red_ticket(ctx, sl, g.n_sets);
   };
   if (ch.pipeline == msel::BUCKET_PER_LANE && bpl_geom(ctx, bases, base_off, n, group_shift, ch.plain_window, &g)) {
     sl->geom = g;
@@ -428,15 +433,15 @@ inline bool direct_sum_applies(const amsm_ctx* ctx, const amsm_bases* bases, siz
 // nv <= DS_BATCH MSMs over the key in ONE launch (the provers' batched commits: eight per r1cs_nark prove) -- the slot then carries
 // nv results, msm_collect hands them out as nv "groups" of one record each.  nv = 1: a single MSM, plain or grouped.
 template <class Fq, class Fr>
-int msm_enqueue_direct_batch(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, size_t nv, const size_t* offs, const void* const* d_scalars,
-                             const size_t* ns, int scalars_mont, int group_shift, bool alone, bool plan_only = false) {
+int msm_enqueue_direct_batch(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, const MsmJob* jobs, size_t nv, int scalars_mont,
+                             int group_shift, bool alone, bool plan_only = false) {
   if (nv == 0 || nv > (size_t)DS_BATCH || (group_shift >= 0 && nv != 1)) return AMSM_E_INVALID_ARG;
   size_t n_max = 0;
-  for (size_t v = 0; v < nv; v++) n_max = std::max(n_max, ns[v]);
+  for (size_t v = 0; v < nv; v++) n_max = std::max(n_max, jobs[v].n);
   MsmGeom g;
   memset(&g, 0, sizeof(g));
   g.n = (u32)n_max;
-  g.base_off = (u32)offs[0];
+  g.base_off = (u32)jobs[0].off;
   g.n_sets = group_shift >= 0 ? 2 : (u32)nv;
   g.groups = g.n_sets;
   g.group_shift = group_shift >= 0 ? (u32)group_shift : 0u;
@@ -463,9 +468,9 @@ int msm_enqueue_direct_batch(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, s
   sl->job.bases = bases;
   sl->job.group_shift = group_shift;
   sl->job.force_chunked = false;
-  sl->job.base_off = offs[0];
-  sl->job.n = ns[0];
-  sl->job.d_scalars = d_scalars[0];
+  sl->job.base_off = jobs[0].off;
+  sl->job.n = jobs[0].n;
+  sl->job.d_scalars = jobs[0].scalars;
   sl->job.mont = scalars_mont;
   sl->job.rerun = &msm_rerun_chunked<Fq, Fr>;
   // inside a batch the launches alternate between the two streams every caller has ordered behind the scalars' producers (the
@@ -477,9 +482,9 @@ int msm_enqueue_direct_batch(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, s
   const u32* sp[DS_BATCH];
   u32 n32[DS_BATCH], o32[DS_BATCH];
   for (size_t v = 0; v < nv; v++) {
-    sp[v] = (const u32*)d_scalars[v];
-    n32[v] = (u32)ns[v];
-    o32[v] = (u32)offs[v];
+    sp[v] = (const u32*)jobs[v].scalars;
+    n32[v] = (u32)jobs[v].n;
+    o32[v] = (u32)jobs[v].off;
   }
   launch_direct_sum<Fq>(st, (const u32*)bases->d_small, (u32)bases->n, (u32)nv, sp, n32, o32, scalars_mont, m, group_shift, d_err,
                         (u32*)sl->red_out.p);
@@ -500,7 +505,8 @@ int msm_enqueue_direct_batch(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, s
 template <class Fq, class Fr>
 int msm_enqueue_direct(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, size_t base_off, const void* d_scalars, size_t n,
                        int scalars_mont, int group_shift, bool alone, bool plan_only = false) {
-  return msm_enqueue_direct_batch<Fq, Fr>(ctx, sl, bases, 1, &base_off, &d_scalars, &n, scalars_mont, group_shift, alone, plan_only);
+  const MsmJob job{0, bases, base_off, n, d_scalars};
+  return msm_enqueue_direct_batch<Fq, Fr>(ctx, sl, bases, &job, 1, scalars_mont, group_shift, alone, plan_only);
 }
 
 // Enqueue the whole pipeline for one MSM on slot `sl` (asynchronous); leaves n_sets folded XYZZ records
@@ -742,8 +748,8 @@ template <class Fq>
 int msm_collect(amsm_ctx* ctx, Slot* sl, host::HXYZZ<Fq>* out) {
   const MsmGeom& g = sl->geom;
   size_t rec = xyzz_bytes<Fq>();
+  sl->busy = false;  // (whatever comes of the wait: a slot whose event cannot be waited for has nothing left to collect)
   HIP_TRY(hipEventSynchronize(sl->done));
-  sl->busy = false;
   if (ctx->profiling) {
     for (int s = 0; s < ST_COUNT; s++) {
       float ms = 0;
@@ -808,6 +814,64 @@ void stage_begin(amsm_ctx* ctx) {
 void stage_end(amsm_ctx* ctx) {
   if (!ctx->stage_n) return;
   for (int s = 0; s < ST_COUNT; s++) ctx->stage_ms[s] = ctx->stage_acc[s] / ctx->stage_n;
+}
+
+// The slot ring every batch of MSMs runs through, N_SLOTS in flight on the per-stage streams.  Items 0 .. n - 1 (an empty MSM is no
+// item: it takes no slot) go in order, item i to slot i % N_SLOTS, whose previous item is collected first; the rest are drained in
+// enqueue order.  enqueue(i, sl) queues item i on slot sl, collect(i, sl) reads it back (msm_collect); overflow[i] (if given) is set
+// when item i, one range of a shared bucket set, found skewed digits (its whole MSM is the caller's to re-run).  The call's one
+// prep_fork comes before the first enqueue.  Every way out leaves all slots idle: after an error the busy slots are still drained and
+// the first error is returned, and a slot found busy on entry is refused -- no item of this call owns it.
+template <class Enqueue, class Collect>
+int run_ring(amsm_ctx* ctx, size_t n, Enqueue&& enqueue, Collect&& collect, uint8_t* overflow = nullptr) {
+  for (const Slot& sl : ctx->slot)
+    if (sl.busy) return AMSM_E_INVALID_ARG;
+  stage_begin(ctx);
+  TRY(prep_fork(ctx));
+  size_t owner[N_SLOTS] = {};  // the item a busy slot carries
+  auto take = [&](size_t s) -> int {
+    Slot* sl = &ctx->slot[s];
+    const int r = collect(owner[s], sl);
+    if (overflow && sl->share_overflow) overflow[owner[s]] = 1;
+    sl->share_overflow = false;
+    return r;
+  };
+  int rc = AMSM_OK;
+  size_t i = 0;
+  for (; i < n && rc == AMSM_OK; i++) {
+    const size_t s = i % N_SLOTS;
+    if (ctx->slot[s].busy) rc = take(s);
+    if (rc != AMSM_OK) break;
+    rc = enqueue(i, &ctx->slot[s]);
+    owner[s] = i;
+  }
+  for (size_t t = 0; t < N_SLOTS; t++) {  // drain in enqueue order
+    const size_t s = (i + t) % N_SLOTS;
+    if (ctx->slot[s].busy) {
+      const int r2 = take(s);
+      if (rc == AMSM_OK) rc = r2;
+    }
+  }
+  stage_end(ctx);
+  return rc;
+}
+
+// Ranges jobs[first, first + count) of one MSM over ONE bucket set (struct Share): the context's next set -- consecutive long MSMs
+// alternate between its two, so both are grown here --, the first range writes it, the last one carries the tail
+template <class Fq>
+int arm_shared_set(amsm_ctx* ctx, std::vector<MsmJob>& jobs, size_t first, size_t count, size_t buckets) {
+  const int buf = (int)(ctx->shared_rr++ & 1u);
+  for (int b = 0; b < 2; b++) {
+    TRY(ensure(ctx->shared_buckets[b], buckets * xyzz_bytes<Fq>()));
+    if (!ctx->shared_free[b]) HIP_TRY(hipEventCreateWithFlags(&ctx->shared_free[b], hipEventDisableTiming));
+  }
+  for (size_t j = 0; j < count; j++) {
+    jobs[first + j].share.buf = buf;
+    jobs[first + j].share.first = j == 0;
+    jobs[first + j].share.last = j + 1 == count;
+  }
+  ctx->n_shared++;
+  return AMSM_OK;
 }
 
 template <class Fq, class Fr>
@@ -935,6 +999,57 @@ bool bpl_probe_host(const uint64_t* scalars, size_t n, int mont, DigitWalk dw, s
   return false;
 }
 
+// The jobs' MSMs through the slot ring; (*part)[j] = job j's result (the identity for an empty job, and for every range of a shared
+// bucket set but its last), (*overflow)[j] = 1 where job j, a range of a shared set, found skewed digits (run_ring)
+template <class Fq, class Fr>
+int msm_multi_xyzz(amsm_ctx* ctx, const std::vector<MsmJob>& jobs, int scalars_mont, std::vector<host::HXYZZ<Fq>>* part,
+                   std::vector<uint8_t>* overflow = nullptr) {
+  const size_t k = jobs.size();
+  part->assign(k, host::hx_inf<Fq>());
+  if (overflow) overflow->assign(k, 0);
+  if (k == 0) return AMSM_OK;
+  // every MSM a direct sum over this key (small keys: DESIGN.md 4.2g): up to DS_BATCH of them per launch
+  const amsm_bases* key = jobs[0].key;
+  bool all_direct = k >= 2;
+  for (const MsmJob& j : jobs) all_direct = all_direct && j.n > 0 && j.key == key && direct_sum_applies(ctx, key, j.n, -1, j.force_chunked);
+  if (all_direct) {
+    const bool one_launch = k <= (size_t)DS_BATCH;
+    return run_ring(
+        ctx, (k + DS_BATCH - 1) / DS_BATCH,
+        [&](size_t b, Slot* sl) {
+          const size_t v0 = b * DS_BATCH;
+          return msm_enqueue_direct_batch<Fq, Fr>(ctx, sl, key, &jobs[v0], std::min<size_t>(DS_BATCH, k - v0), scalars_mont, -1, one_launch);
+        },
+        [&](size_t b, Slot* sl) { return msm_collect<Fq>(ctx, sl, &(*part)[b * DS_BATCH]); });
+  }
+  std::vector<size_t> live;  // the non-empty jobs; the last one's tail is the only one the caller waits for
+  for (size_t j = 0; j < k; j++)
+    if (jobs[j].n) live.push_back(j);
+  std::vector<uint8_t> ovf(live.size(), 0);
+  const int rc = run_ring(
+      ctx, live.size(),
+      [&](size_t i, Slot* sl) {
+        const MsmJob& j = jobs[live[i]];
+        return msm_enqueue<Fq, Fr>(ctx, sl, j.key, j.off, j.scalars, j.n, scalars_mont, -1, i + 1 == live.size(), live.size() == 1,
+                                   j.force_chunked, &j.share);
+      },
+      [&](size_t i, Slot* sl) { return msm_collect<Fq>(ctx, sl, &(*part)[live[i]]); }, ovf.data());
+  if (overflow)
+    for (size_t i = 0; i < live.size(); i++) (*overflow)[live[i]] = ovf[i];
+  return rc;
+}
+// k MSMs over windows of one key, one job each: MSM v uses generators [offs[v], offs[v] + ns[v]) and the scalars at d_scalars[v]
+template <class Fq, class Fr>
+int msm_multi_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const size_t* offs, const void* const* d_scalars, const size_t* ns,
+                   int scalars_mont, std::vector<host::HXYZZ<Fq>>* out) {
+  std::vector<MsmJob> jobs(k);
+  for (size_t v = 0; v < k; v++) {
+    if (offs[v] > bases->n) return AMSM_E_INVALID_ARG;
+    jobs[v] = MsmJob{v, bases, offs[v], std::min(ns[v], bases->n - offs[v]), d_scalars[v]};
+  }
+  return msm_multi_xyzz<Fq, Fr>(ctx, jobs, scalars_mont, out);
+}
+
 template <class Fq, class Fr>
 int msm_device_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, const void* d_scalars, size_t n,
                     int scalars_mont, host::HXYZZ<Fq>* out) {
@@ -946,103 +1061,12 @@ int msm_device_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, con
   }
   const bool probe_wanted = ctx->bpl_probe && msel::wants_skew_probe(key_desc(bases), n, switches_of(ctx));
   // (long single vectors are worth the two-valued probe's synchronisation: ~20 us against 0.45 ms and up)
-  if (split_needed(ctx, bases, n) || probe_wanted || (ctx->two_valued && n >= ((size_t)1 << 17))) {  // windows of the key / the probes
-    std::vector<host::HXYZZ<Fq>> r;
-    int rc = msm_multi_split_xyzz<Fq, Fr>(ctx, bases, 1, &base_off, &d_scalars, &n, scalars_mont, &r);
-    if (rc == AMSM_OK) *out = r[0];
-    return rc;
-  }
-  stage_begin(ctx);
-  TRY(prep_fork(ctx));
-  TRY((msm_enqueue<Fq, Fr>(ctx, &ctx->slot[0], bases, base_off, d_scalars, n, scalars_mont)));
-  int rc = msm_collect<Fq>(ctx, &ctx->slot[0], out);
-  stage_end(ctx);
-  return rc;
-}
-
-// k MSMs over (windows of) the same key, N_SLOTS in flight on the per-stage streams.  MSM v uses generators
-// [offs[v], offs[v] + ns[v]) and the scalars at d_scalars[v].
-template <class Fq, class Fr>
-int msm_multi_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const size_t* offs, const void* const* d_scalars,
-                   const size_t* ns, int scalars_mont, std::vector<host::HXYZZ<Fq>>* out,
-                   const amsm_bases* const* keys = nullptr,  // keys[v] (same generators as `bases`): the key MSM v runs over
-                   const uint8_t* force_chunked = nullptr,    // force_chunked[v]: the skew probe's verdict for MSM v
-                   const Share* shares = nullptr,             // shares[v].buf >= 0: MSM v is one range of a shared-bucket MSM
-                   uint8_t* share_overflow = nullptr) {       // out, per MSM: that range's prep overflowed (re-run its whole MSM)
-  out->assign(k, host::hx_inf<Fq>());
-  std::vector<size_t> len(k);
-  for (size_t v = 0; v < k; v++) {
-    if (offs[v] > bases->n) return AMSM_E_INVALID_ARG;
-    len[v] = std::min(ns[v], bases->n - offs[v]);
-  }
-  if (k == 0) return AMSM_OK;
-  // every MSM a direct sum over this key (small keys: DESIGN.md 4.2g): up to DS_BATCH of them per launch
-  bool all_direct = k >= 2 && !keys;
-  for (size_t v = 0; v < k && all_direct; v++)
-    all_direct = len[v] > 0 && direct_sum_applies(ctx, bases, len[v], -1, force_chunked && force_chunked[v]);
-  if (all_direct) {
-    stage_begin(ctx);
-    TRY(prep_fork(ctx));
-    int rc = AMSM_OK;
-    std::vector<long> first(N_SLOTS, -1);
-    size_t slot_rr = 0;
-    const bool one_launch = k <= (size_t)DS_BATCH;
-    for (size_t v0 = 0; v0 < k && rc == AMSM_OK; v0 += DS_BATCH) {
-      const size_t nv = std::min<size_t>(DS_BATCH, k - v0);
-      Slot* sl = &ctx->slot[slot_rr % N_SLOTS];
-      if (sl->busy) rc = msm_collect<Fq>(ctx, sl, &(*out)[first[slot_rr % N_SLOTS]]);
-      if (rc != AMSM_OK) break;
-      rc = msm_enqueue_direct_batch<Fq, Fr>(ctx, sl, bases, nv, offs + v0, d_scalars + v0, len.data() + v0, scalars_mont, -1, one_launch);
-      first[slot_rr % N_SLOTS] = (long)v0;
-      slot_rr++;
-    }
-    for (int j = 0; j < N_SLOTS; j++) {
-      const size_t s = (slot_rr + j) % N_SLOTS;
-      Slot* sl = &ctx->slot[s];
-      if (sl->busy) {
-        int r2 = msm_collect<Fq>(ctx, sl, &(*out)[first[s]]);
-        if (rc == AMSM_OK) rc = r2;
-      }
-    }
-    stage_end(ctx);
-    return rc;
-  }
-  stage_begin(ctx);
-  TRY(prep_fork(ctx));
-  int rc = AMSM_OK;
-  std::vector<long> owner(N_SLOTS, -1);  // which MSM a busy slot carries
-  size_t slot_rr = 0;
-  size_t last = 0;  // the last non-empty MSM: the only one whose tail the caller waits for
-  size_t n_live = 0;
-  for (size_t v = 0; v < k; v++)
-    if (len[v]) last = v, n_live++;
-  auto collect = [&](Slot* sl, long who) -> int {
-    int r = msm_collect<Fq>(ctx, sl, &(*out)[who]);
-    if (sl->share_overflow && share_overflow) share_overflow[who] = 1;
-    sl->share_overflow = false;
-    return r;
-  };
-  for (size_t v = 0; v < k && rc == AMSM_OK; v++) {
-    if (len[v] == 0) continue;  // identity
-    Slot* sl = &ctx->slot[slot_rr % N_SLOTS];
-    if (sl->busy) rc = collect(sl, owner[slot_rr % N_SLOTS]);
-    if (rc == AMSM_OK) {
-      rc = msm_enqueue<Fq, Fr>(ctx, sl, keys ? keys[v] : bases, offs[v], d_scalars[v], len[v], scalars_mont, -1, v == last,
-                               n_live == 1, force_chunked && force_chunked[v], shares ? &shares[v] : nullptr);
-      owner[slot_rr % N_SLOTS] = (long)v;
-      slot_rr++;
-    }
-  }
-  for (int j = 0; j < N_SLOTS; j++) {  // drain in enqueue order
-    size_t s = (slot_rr + j) % N_SLOTS;
-    Slot* sl = &ctx->slot[s];
-    if (sl->busy) {
-      int r2 = collect(sl, owner[s]);
-      if (rc == AMSM_OK) rc = r2;
-    }
-  }
-  stage_end(ctx);
-  return rc;
+  const bool split = split_needed(ctx, bases, n) || probe_wanted || (ctx->two_valued && n >= ((size_t)1 << 17));  // windows of the key / the probes
+  std::vector<host::HXYZZ<Fq>> r;
+  TRY((split ? msm_multi_split_xyzz<Fq, Fr>(ctx, bases, 1, &base_off, &d_scalars, &n, scalars_mont, &r)
+             : msm_multi_xyzz<Fq, Fr>(ctx, bases, 1, &base_off, &d_scalars, &n, scalars_mont, &r)));
+  *out = r[0];
+  return AMSM_OK;
 }
 
 // Large MSMs over a precomputed key run as pipelined sub-MSMs over windows of 2^split_log2 generators, summed on the host.
@@ -1342,94 +1366,61 @@ int msm_multi_split_impl(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const
     for (size_t v = 0; v < k; v++)
       if (skew[v] && !alt) TRY(bases_alt<Fq>(ctx, bases, &alt));
   } else if (probed) {
-    bool any_skew = false, any_split = false;
-    for (size_t v = 0; v < k; v++) {
-      any_skew = any_skew || skew[v];
-      any_split = any_split || split_needed(ctx, bases, lens[v]);
-    }
-    if (!any_split)
-      return msm_multi_xyzz<Fq, Fr>(ctx, bases, k, offs, d_scalars, ns, scalars_mont, out, nullptr, any_skew ? skew.data() : nullptr);
-    std::fill(skew.begin(), skew.end(), 0);  // (longer than 2^21: ranges of the key, chunked anyway)
+    bool any_split = false;
+    for (size_t v = 0; v < k; v++) any_split = any_split || split_needed(ctx, bases, lens[v]);
+    if (any_split) std::fill(skew.begin(), skew.end(), 0);  // (longer than 2^21: ranges of the key, chunked anyway)
   }
-  bool any = alt != nullptr;
-  for (size_t v = 0; v < k && !any; v++) any = split_needed(ctx, bases, lens[v]);
-  if (!any) return msm_multi_xyzz<Fq, Fr>(ctx, bases, k, offs, d_scalars, ns, scalars_mont, out);
-  std::vector<size_t> s_offs, s_ns, owner;
-  std::vector<const void*> s_ptrs;
-  std::vector<const amsm_bases*> s_keys;
-  std::vector<Share> s_share;
-  bool any_shared = false;
+  std::vector<MsmJob> jobs;
   for (size_t v = 0; v < k; v++) {
     if (offs[v] > bases->n) return AMSM_E_INVALID_ARG;
-    const amsm_bases* key = skew[v] ? alt : bases;
+    const amsm_bases* key = skew[v] && bases->bpl ? alt : bases;
     const size_t len = lens[v];
     const bool split = split_needed(ctx, key, len);
     const size_t step = split ? split_chunk(ctx, key) : std::max<size_t>(len, 1);
-    const size_t first_job = s_ns.size();
-    for (size_t lo = 0; lo < len; lo += step) {
-      s_offs.push_back(offs[v] + lo);
-      s_ns.push_back(std::min(step, len - lo));
-      s_ptrs.push_back((const char*)d_scalars[v] + lo * 32);
-      s_keys.push_back(key);
-      owner.push_back(v);
-      s_share.push_back(Share());
-    }
+    const size_t first_job = jobs.size();
+    size_t lo = 0;
+    do {  // (an empty vector stays one empty job: a batch with one is no batch of direct sums, msm_multi_xyzz)
+      jobs.push_back(MsmJob{v, key, offs[v] + lo, std::min(step, len - lo), (const char*)d_scalars[v] + lo * 32, skew[v] && !bases->bpl});
+      lo += step;
+    } while (lo < len);
     // Round 5: the ranges of one vector over a bucket-per-lane key share ONE bucket set (struct Share) -- every leading range
     // that takes that pipeline; a short last range (below a quarter of the window: the twin's pipelines) stays an MSM of its own
-    if (split && ctx->share_buckets && key->bpl && key->precomp && ctx->bpl && s_ns.size() - first_job >= 2) {
+    if (split && ctx->share_buckets && key->bpl && key->precomp && ctx->bpl && jobs.size() - first_job >= 2) {
       size_t n_sh = 0;
       MsmGeom g;
-      while (first_job + n_sh < s_ns.size() &&
-             choose_pipeline(ctx, key, s_ns[first_job + n_sh], -1, false).pipeline == msel::BUCKET_PER_LANE &&
-             bpl_geom(ctx, key, s_offs[first_job + n_sh], s_ns[first_job + n_sh], -1, 0, &g) && g.n_sets == 1u)
+      while (first_job + n_sh < jobs.size() &&
+             choose_pipeline(ctx, key, jobs[first_job + n_sh].n, -1, false).pipeline == msel::BUCKET_PER_LANE &&
+             bpl_geom(ctx, key, jobs[first_job + n_sh].off, jobs[first_job + n_sh].n, -1, 0, &g) && g.n_sets == 1u)
         n_sh++;
-      if (n_sh >= 2) {
-        const int buf = (int)(ctx->shared_rr++ & 1u);
-        const size_t rec = xyzz_bytes<Fq>();
-        TRY(ensure(ctx->shared_buckets[0], (size_t)g.B * rec));  // (both: the next long MSM takes the other one)
-        TRY(ensure(ctx->shared_buckets[1], (size_t)g.B * rec));
-        for (int b = 0; b < 2; b++)
-          if (!ctx->shared_free[b]) HIP_TRY(hipEventCreateWithFlags(&ctx->shared_free[b], hipEventDisableTiming));
-        for (size_t j = 0; j < n_sh; j++) {
-          s_share[first_job + j].buf = buf;
-          s_share[first_job + j].first = j == 0;
-          s_share[first_job + j].last = j + 1 == n_sh;
-        }
-        any_shared = true;
-        ctx->n_shared++;
-      }
+      if (n_sh >= 2) TRY(arm_shared_set<Fq>(ctx, jobs, first_job, n_sh, g.B));
     }
   }
   std::vector<host::HXYZZ<Fq>> part;
-  std::vector<uint8_t> ovf(any_shared ? s_ns.size() : 0, 0);
-  int rc = msm_multi_xyzz<Fq, Fr>(ctx, bases, s_ns.size(), s_offs.data(), s_ptrs.data(), s_ns.data(), scalars_mont, &part,
-                                  s_keys.data(), nullptr, any_shared ? s_share.data() : nullptr, any_shared ? ovf.data() : nullptr);
+  std::vector<uint8_t> ovf;
+  const int rc = msm_multi_xyzz<Fq, Fr>(ctx, jobs, scalars_mont, &part, &ovf);
   out->assign(k, host::hx_inf<Fq>());
   if (rc != AMSM_OK) return rc;
   // a range of a shared MSM met skewed digits (what the probe's 1024 samples missed): that vector's shared ranges again, each an
   // MSM of its own with its own fallback -- the result does not depend on the path
   std::vector<uint8_t> redo(k, 0);
   bool any_redo = false;
-  for (size_t j = 0; j < ovf.size(); j++)
-    if (ovf[j]) redo[owner[j]] = 1, any_redo = true;
+  for (size_t j = 0; j < jobs.size(); j++)
+    if (ovf[j]) redo[jobs[j].owner] = 1, any_redo = true;
   if (any_redo) {
-    std::vector<size_t> r_offs, r_ns, r_job;
-    std::vector<const void*> r_ptrs;
-    std::vector<const amsm_bases*> r_keys;
-    for (size_t j = 0; j < s_ns.size(); j++)
-      if (redo[owner[j]] && s_share[j].buf >= 0) {
-        r_offs.push_back(s_offs[j]);
-        r_ns.push_back(s_ns[j]);
-        r_ptrs.push_back(s_ptrs[j]);
-        r_keys.push_back(s_keys[j]);
-        r_job.push_back(j);
+    std::vector<MsmJob> again;
+    std::vector<size_t> at;  // where each of them sits in `jobs`
+    for (size_t j = 0; j < jobs.size(); j++)
+      if (redo[jobs[j].owner] && jobs[j].share.buf >= 0) {
+        again.push_back(jobs[j]);
+        again.back().share = Share();
+        at.push_back(j);
       }
-    std::vector<host::HXYZZ<Fq>> again;
-    TRY((msm_multi_xyzz<Fq, Fr>(ctx, bases, r_ns.size(), r_offs.data(), r_ptrs.data(), r_ns.data(), scalars_mont, &again, r_keys.data())));
-    for (size_t t = 0; t < r_job.size(); t++) part[r_job[t]] = again[t];
+    std::vector<host::HXYZZ<Fq>> r;
+    TRY((msm_multi_xyzz<Fq, Fr>(ctx, again, scalars_mont, &r)));
+    for (size_t t = 0; t < at.size(); t++) part[at[t]] = r[t];
     ctx->n_bpl_fallbacks++;
   }
-  for (size_t j = 0; j < part.size(); j++) (*out)[owner[j]] = host::hx_add<Fq>((*out)[owner[j]], part[j]);
+  for (size_t j = 0; j < jobs.size(); j++) (*out)[jobs[j].owner] = host::hx_add<Fq>((*out)[jobs[j].owner], part[j]);
   return AMSM_OK;
 }
 
@@ -1572,14 +1563,7 @@ int msm_multi_host_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const 
       return msm_multi_split_xyzz<Fq, Fr>(ctx, bases, k, offs, d_ptrs.data(), lens.data(), scalars_mont, out);
     }
   }
-  struct Job {
-    size_t owner, off, n;
-    const char* h;
-    const amsm_bases* key;
-    bool force_chunked;
-    Share share;
-  };
-  std::vector<Job> jobs;
+  std::vector<MsmJob> jobs;  // (scalars: host slices)
   size_t n_max = 0;
   const amsm_bases* alt = nullptr;
   bool halved = false;
@@ -1605,113 +1589,83 @@ int msm_multi_host_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const 
                        bpl_geom(ctx, key, offs[v], h1, -1, 0, &hg) && hg.n_sets == 1u;
     if (halve) step = h1;
     for (size_t lo = 0; lo < len; lo += step) {
-      Job j{v, offs[v] + lo, std::min(step, len - lo), (const char*)h_scalars[v] + lo * 32, key, force_chunked, Share()};
-      n_max = std::max(n_max, j.n);
-      jobs.push_back(j);
+      jobs.push_back(MsmJob{v, key, offs[v] + lo, std::min(step, len - lo), (const char*)h_scalars[v] + lo * 32, force_chunked});
+      n_max = std::max(n_max, jobs.back().n);
     }
     if (halve && jobs.size() == 2) {
-      const int buf = (int)(ctx->shared_rr++ & 1u);
-      const size_t rec = xyzz_bytes<Fq>();
-      TRY(ensure(ctx->shared_buckets[0], (size_t)hg.B * rec));  // (both: the next long MSM takes the other one)
-      TRY(ensure(ctx->shared_buckets[1], (size_t)hg.B * rec));
-      for (int b = 0; b < 2; b++)
-        if (!ctx->shared_free[b]) HIP_TRY(hipEventCreateWithFlags(&ctx->shared_free[b], hipEventDisableTiming));
-      jobs[0].share.buf = jobs[1].share.buf = buf;
-      jobs[0].share.first = jobs[1].share.last = true;
+      TRY(arm_shared_set<Fq>(ctx, jobs, 0, 2, hg.B));
       halved = true;
-      ctx->n_shared++;
     }
   }
   if (jobs.empty()) return AMSM_OK;
+  const size_t J = jobs.size();
+  std::vector<host::HXYZZ<Fq>> part;
   // small keys (direct sums, DESIGN.md 4.2g): the slices are a few hundred KiB each -- copied behind one another on the caller's
   // stream into one staging buffer, then ONE batched launch per 16 MSMs (msm_multi_xyzz) instead of an upload / launch pair each
   {
-    bool all_direct = jobs.size() >= 2;
+    bool all_direct = J >= 2;
     size_t total = 0;
-    for (const Job& j : jobs) {
+    for (const MsmJob& j : jobs) {
       all_direct = all_direct && j.key == bases && direct_sum_applies(ctx, bases, j.n, -1, j.force_chunked);
       total += j.n * 32;
     }
     if (all_direct && total <= ((size_t)64 << 20)) {
       TRY(ensure(ctx->stage_ring[0], total));
-      std::vector<size_t> j_offs(jobs.size()), j_ns(jobs.size());
-      std::vector<const void*> j_ptrs(jobs.size());
+      std::vector<MsmJob> staged = jobs;
       size_t at = 0;
-      for (size_t j = 0; j < jobs.size(); j++) {
+      for (MsmJob& j : staged) {
         char* dst = (char*)ctx->stage_ring[0].p + at;
-        HIP_TRY(hipMemcpyAsync(dst, jobs[j].h, jobs[j].n * 32, hipMemcpyHostToDevice, ctx->stream));
-        j_offs[j] = jobs[j].off;
-        j_ns[j] = jobs[j].n;
-        j_ptrs[j] = dst;
-        at += jobs[j].n * 32;
+        HIP_TRY(hipMemcpyAsync(dst, j.scalars, j.n * 32, hipMemcpyHostToDevice, ctx->stream));
+        j.scalars = dst;
+        at += j.n * 32;
       }
-      std::vector<host::HXYZZ<Fq>> part;
-      TRY((msm_multi_xyzz<Fq, Fr>(ctx, bases, jobs.size(), j_offs.data(), j_ptrs.data(), j_ns.data(), scalars_mont, &part)));
-      for (size_t j = 0; j < jobs.size(); j++) (*out)[jobs[j].owner] = host::hx_add<Fq>((*out)[jobs[j].owner], part[j]);
+      TRY((msm_multi_xyzz<Fq, Fr>(ctx, staged, scalars_mont, &part)));
+      for (size_t j = 0; j < J; j++) (*out)[jobs[j].owner] = host::hx_add<Fq>((*out)[jobs[j].owner], part[j]);
       return AMSM_OK;
     }
   }
   constexpr int RING = amsm_ctx::STAGE_RING;
   if (!ctx->s_copy) HIP_TRY(hipStreamCreateWithFlags(&ctx->s_copy, hipStreamNonBlocking));
-  for (int r = 0; r < RING && (size_t)r < jobs.size(); r++) {
+  for (int r = 0; r < RING && (size_t)r < J; r++) {
     TRY(ensure(ctx->stage_ring[r], n_max * 32));
     if (!ctx->up_ev[r]) HIP_TRY(hipEventCreateWithFlags(&ctx->up_ev[r], hipEventDisableTiming));
   }
   auto upload = [&](size_t j) -> int {
     const int r = (int)(j % RING);
     if (os) TRY(oneshot_upload_range<Fq>(ctx, jobs[j].key, os, jobs[j].off, jobs[j].n, ctx->s_copy));  // the range's generators first
-    HIP_TRY(hipMemcpyAsync(ctx->stage_ring[r].p, jobs[j].h, jobs[j].n * 32, hipMemcpyHostToDevice, ctx->s_copy));
+    HIP_TRY(hipMemcpyAsync(ctx->stage_ring[r].p, jobs[j].scalars, jobs[j].n * 32, hipMemcpyHostToDevice, ctx->s_copy));
     HIP_TRY(hipEventRecord(ctx->up_ev[r], ctx->s_copy));
     return AMSM_OK;
   };
-  stage_begin(ctx);
-  TRY(prep_fork(ctx));
-  // the ring's buffers may still be read by the prep kernels of an earlier call's MSMs?  No: every call collects all its
-  // MSMs before it returns.  The copy stream only has to stay behind the caller's stream (buffers freshly grown above).
-  HIP_TRY(hipStreamWaitEvent(ctx->s_copy, ctx->fork, 0));
-  // ONE upload ahead of the MSM being enqueued (two were measured slower twice: the ring has N_SLOTS + 2 buffers all the same)
-  const size_t ahead = 1;
-  int rc = upload(0);
-  const size_t J = jobs.size();
-  for (size_t a = 1; a < ahead && a < J && rc == AMSM_OK; a++) rc = upload(a);
-  std::vector<long> owner(N_SLOTS, -1);
-  std::vector<host::HXYZZ<Fq>> part(jobs.size(), host::hx_inf<Fq>());
-  bool halves_overflowed = false;
-  for (size_t j = 0; j < J && rc == AMSM_OK; j++) {
-    Slot* sl = &ctx->slot[j % N_SLOTS];
-    if (sl->busy) {
-      rc = msm_collect<Fq>(ctx, sl, &part[owner[j % N_SLOTS]]);
-      if (sl->share_overflow) halves_overflowed = true;
-      sl->share_overflow = false;
-    }
-    if (rc != AMSM_OK) break;
-    const int r = (int)(j % RING);
-    // both streams a prep chain may start on (the caller's for a lone MSM, the prep stream otherwise) wait for the upload
-    HIP_TRY(hipStreamWaitEvent(ctx->s_prep, ctx->up_ev[r], 0));
-    // (the caller's stream reads scalars only in those two cases: inside a batch it carries the accumulations, and a barrier
-    // packet in front of each costs the queue ~10 us)
-    if (J == 1 || direct_sum_applies(ctx, jobs[j].key, jobs[j].n, -1, jobs[j].force_chunked))
-      HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->up_ev[r], 0));
-    rc = msm_enqueue<Fq, Fr>(ctx, sl, jobs[j].key, jobs[j].off, ctx->stage_ring[r].p, jobs[j].n, scalars_mont, -1, j + 1 == J,
-                             J == 1, jobs[j].force_chunked, jobs[j].share.buf >= 0 ? &jobs[j].share : nullptr);
-    owner[j % N_SLOTS] = (long)j;
-    if (rc == AMSM_OK && j + ahead < J) rc = upload(j + ahead);  // the host copies while the GPU computes MSM j
-  }
-  for (int s2 = 0; s2 < N_SLOTS; s2++) {  // drain in enqueue order
-    const size_t s = (J + s2) % N_SLOTS;
-    Slot* sl = &ctx->slot[s];
-    if (sl->busy) {
-      int r2 = msm_collect<Fq>(ctx, sl, &part[owner[s]]);
-      if (rc == AMSM_OK) rc = r2;
-      if (sl->share_overflow) halves_overflowed = true;
-      sl->share_overflow = false;
-    }
-  }
+  part.assign(J, host::hx_inf<Fq>());
+  std::vector<uint8_t> ovf(J, 0);
+  const int rc = run_ring(
+      ctx, J,
+      [&](size_t j, Slot* sl) -> int {
+        if (j == 0) {
+          // the ring's buffers may still be read by the prep kernels of an earlier call's MSMs?  No: every call collects all its
+          // MSMs before it returns.  The copy stream only has to stay behind the caller's stream (buffers freshly grown above).
+          HIP_TRY(hipStreamWaitEvent(ctx->s_copy, ctx->fork, 0));
+          TRY(upload(0));
+        }
+        const int r = (int)(j % RING);
+        // both streams a prep chain may start on (the caller's for a lone MSM, the prep stream otherwise) wait for the upload
+        HIP_TRY(hipStreamWaitEvent(ctx->s_prep, ctx->up_ev[r], 0));
+        // (the caller's stream reads scalars only in those two cases: inside a batch it carries the accumulations, and a barrier
+        // packet in front of each costs the queue ~10 us)
+        if (J == 1 || direct_sum_applies(ctx, jobs[j].key, jobs[j].n, -1, jobs[j].force_chunked))
+          HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->up_ev[r], 0));
+        TRY((msm_enqueue<Fq, Fr>(ctx, sl, jobs[j].key, jobs[j].off, ctx->stage_ring[r].p, jobs[j].n, scalars_mont, -1, j + 1 == J, J == 1,
+                                 jobs[j].force_chunked, &jobs[j].share)));
+        // ONE upload ahead of the MSM being enqueued, the host copies while the GPU computes MSM j (two ahead were measured slower
+        // twice: the ring has N_SLOTS + 2 buffers all the same)
+        return j + 1 < J ? upload(j + 1) : AMSM_OK;
+      },
+      [&](size_t j, Slot* sl) { return msm_collect<Fq>(ctx, sl, &part[j]); }, ovf.data());
   (void)hipStreamSynchronize(ctx->s_copy);
-  stage_end(ctx);
   if (rc != AMSM_OK) return rc;
-  if (halved && halves_overflowed) {  // skewed digits in one of the halves (what the host's 1024 samples missed): the one-range form,
-    ctx->n_bpl_fallbacks++;           // with its own fallback -- the result does not depend on the path
+  if (halved && (ovf[0] || ovf[1])) {  // skewed digits in one of the halves (what the host's 1024 samples missed): the one-range form,
+    ctx->n_bpl_fallbacks++;             // with its own fallback -- the result does not depend on the path
     return msm_multi_host_xyzz<Fq, Fr>(ctx, bases, k, offs, h_scalars, ns, scalars_mont, out, os, true);
   }
   for (size_t j = 0; j < J; j++) (*out)[jobs[j].owner] = host::hx_add<Fq>((*out)[jobs[j].owner], part[j]);

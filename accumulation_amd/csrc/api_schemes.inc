@@ -459,14 +459,7 @@ int ipa_jump_fold_impl(amsm_ctx* ctx, const amsm_bases* key, size_t log_key, con
   TRY(ensure(sl->red_out, (size_t)g.n_sets * red_blocks * rec));
   TRY(ensure(sl->fold_out, (size_t)g.n_sets * rec + 64));
   TRY(ensure_pinned(sl, (size_t)g.n_sets * rec + 64));
-  if (sl->red_ticket.bytes < (size_t)g.n_sets * 4) {
-    TRY(ensure(sl->red_ticket, std::max<size_t>((size_t)g.n_sets * 4, 4096)));
-    // (hipMemset on device memory may return before it has run, and the null stream does not order the context's non-blocking
-      // streams: a reduction that found the counters not yet zeroed never saw its last workgroup -- one wrong sum in ~3 of 10 proves over
-      // eight contexts, none with the two-launch tail: profiles/r06_experiments.md section 1b)
-      HIP_TRY(hipMemsetAsync(sl->red_ticket.p, 0, sl->red_ticket.bytes, ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-  }
+  TRY(ensure_red_ticket(ctx, sl, g.n_sets));
   const size_t words = sorted.size() + list_off.size() + list_slot.size();
   TRY(ensure(sl->vals_a, words * 4 + 64));
   u32* d_ent = (u32*)sl->vals_a.p;

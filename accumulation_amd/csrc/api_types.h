@@ -35,6 +35,17 @@ struct Share {
   bool first = false, last = false;
 };
 
+// One MSM, or one range of one, as the batch drivers of api_pipeline.inc list them for the slot ring
+struct MsmJob {
+  size_t owner = 0;                // index of the caller's MSM; this job's result is added to out[owner]
+  const amsm_bases* key = nullptr;  // the key this job runs over (a 20-bit key's twin for a skewed vector)
+  size_t off = 0;                  // first generator
+  size_t n = 0;                    // number of pairs (0: the identity, no slot)
+  const void* scalars = nullptr;   // device pointer; a host pointer on the upload path
+  bool force_chunked = false;      // skew probe verdict: skip the bucket-per-lane attempt
+  Share share;                     // buf >= 0: one range of a shared bucket set
+};
+
 // One pipeline slot = one stream + one private workspace, so two MSMs of a batch can be in flight:
 // the latency-bound tail of MSM i (fold partials, bucket reduce) overlaps the throughput-bound head of
 // MSM i+1 on the other slot's stream.
@@ -269,6 +280,23 @@ struct amsm_ctx {
   size_t pool_free_bytes = 0, pool_live_bytes = 0;
   size_t pool_cap_bytes = (size_t)16 << 30;               // free-list budget (AMSM_POOL_MAX_MB); beyond it frees are real
 };
+
+// Every device buffer of a slot, and every one the context owns beside its slots: the one list amsm_ctx_destroy, amsm_ctx_memory and
+// amsm_ctx_trim walk (a buffer added to a struct above goes here too)
+template <class S, class F>  // S: Slot or const Slot
+void for_each_slot_buf(S* sl, F&& f) {
+  for (auto* b : {&sl->keys_a, &sl->keys_b, &sl->vals_a, &sl->vals_b, &sl->start, &sl->items, &sl->item_off, &sl->partials, &sl->buckets,
+                  &sl->red_out, &sl->fold_out, &sl->heavy, &sl->misc, &sl->sort_tmp, &sl->scan_tmp, &sl->prep_small, &sl->heavy_scratch,
+                  &sl->bpl_grp, &sl->bpl_order, &sl->red2_rc, &sl->ds_flags, &sl->red_ticket})
+    f(*b);
+}
+template <class C, class F>  // C: amsm_ctx or const amsm_ctx
+void for_each_ctx_buf(C* c, F&& f) {
+  for (auto* b : {&c->scalars, &c->probe_flags, &c->xyzz_scratch, &c->tv_flags, &c->tv_parts, &c->tv_out, &c->shared_buckets[0],
+                  &c->shared_buckets[1], &c->oneshot_table, &c->oneshot_inf, &c->rec_send, &c->rec_recv, &c->stage})
+    f(*b);
+  for (auto& b : c->stage_ring) f(b);
+}
 
 struct amsm_bases {
   int curve = 0;
