@@ -24,6 +24,7 @@
 #include <rocprim/rocprim.hpp>
 #include <vector>
 
+#include "curves.h"
 #include "fp.h"
 #include "host_field.h"
 #include "host_glv.h"
@@ -46,8 +47,12 @@ namespace {
 #include "api_multi.inc"
 #include "api_cpu.inc"
 
-#define DISPATCH(ctx, CALL_P, CALL_B)                   \
-  ((ctx)->curve == AMSM_PALLAS ? (CALL_P) : (CALL_B))
+// CALL evaluated with Fq / Fr bound to the context's curve (curves.h; a context's curve is known: amsm_ctx_create checks it)
+#define DISPATCH(ctx, ...) with_curve((ctx)->curve, [&](auto cv_) { AMSM_CURVE_FIELDS(cv_); return (__VA_ARGS__); })
+// the statement(s) run with Fq / Fr bound to the context's curve; a `return` among them (TRY's included) leaves with that
+// status, the end gives AMSM_OK
+#define DISPATCH_DO(ctx, ...) \
+  with_curve((ctx)->curve, [&](auto cv_) -> int { AMSM_CURVE_FIELDS(cv_); __VA_ARGS__; return AMSM_OK; })
 
 int bind_device(const amsm_ctx* ctx) {
   // every entry point branches to the host backend BEFORE it binds a device; one that forgot to must fail, not touch HIP
@@ -72,17 +77,14 @@ static void fr_map2(const uint64_t* a, const uint64_t* b, size_t n, uint64_t* ou
     memcpy(out + 4 * i, r.v, 32);
   }
 }
-#define AMSM_FR_OP(NAME, EXPR)                                                                             \
-  static int NAME(int curve, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {                      \
-    if ((curve != AMSM_PALLAS && curve != AMSM_BLS12_381_G1) || (n && (!a || !out))) return AMSM_E_INVALID_ARG; \
-    if (curve == AMSM_PALLAS) {                                                                            \
-      using F = PallasFr;                                                                                  \
+#define AMSM_FR_OP(NAME, EXPR)                                                                               \
+  static int NAME(int curve, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {                \
+    if (!curve_known(curve) || (n && (!a || !out))) return AMSM_E_INVALID_ARG;                               \
+    return with_curve(curve, [&](auto cv) {                                                                  \
+      using F = typename decltype(cv)::Fr;                                                                   \
       fr_map2<F>(a, b, n, out, [](const host::HFe<F>& x, const host::HFe<F>& y) { (void)y; return EXPR; });  \
-    } else {                                                                                               \
-      using F = Bls12381Fr;                                                                                \
-      fr_map2<F>(a, b, n, out, [](const host::HFe<F>& x, const host::HFe<F>& y) { (void)y; return EXPR; });  \
-    }                                                                                                      \
-    return AMSM_OK;                                                                                        \
+      return AMSM_OK;                                                                                        \
+    });                                                                                                      \
   }
 AMSM_FR_OP(amsm_fr_mul_impl, host::h_mul<F>(x, y))
 AMSM_FR_OP(amsm_fr_add_impl, host::h_add<F>(x, y))

@@ -78,7 +78,7 @@ int bases_generate(amsm_ctx* c, uint64_t seed, size_t n, unsigned flags, amsm_ba
   if (!b) return AMSM_E_OOM;
   constexpr size_t PW = pt_words<Fq>();
   if (n) {
-    std::vector<u32> gen = generator_mont<Fq>(c->curve);
+    std::vector<u32> gen = generator_mont<Fq>();
     host::HFixedBase<Fq> fb;
     fb.build(host::hx_from_affine<Fq>((const u64*)gen.data(), false));
     par_for(n, 64, [&](size_t lo, size_t hi) {
@@ -508,5 +508,5 @@ int spmv(const amsm_matrix* m, const void* input, size_t n_input, const void* wi
 }  // namespace cpu
 
 // curve dispatch of a cpu:: template
-#define CPU_CALL(c, fn, ...)                                                                   \
-  ((c)->curve == AMSM_PALLAS ? cpu::fn<PallasFq, PallasFr>(__VA_ARGS__) : cpu::fn<Bls12381Fq, Bls12381Fr>(__VA_ARGS__))
+#define CPU_CALL(c, fn, ...) \
+  with_curve((c)->curve, [&](auto cv_) { AMSM_CURVE_FIELDS(cv_); return cpu::fn<Fq, Fr>(__VA_ARGS__); })

@@ -30,7 +30,7 @@ static size_t pool_cap_from_env(size_t dflt) {
 int amsm_ctx_create(amsm_ctx** out, int curve, int device_id, void* stream) {
   if (!out) return AMSM_E_INVALID_ARG;
   *out = nullptr;
-  if (curve != AMSM_PALLAS && curve != AMSM_BLS12_381_G1) return AMSM_E_INVALID_ARG;
+  if (!curve_known(curve)) return AMSM_E_INVALID_ARG;
   if (device_id == AMSM_DEVICE_HOST) {  // the host backend (api_cpu.inc), only ever by explicit request
     if (stream) return AMSM_E_INVALID_ARG;
     amsm_ctx* c = new (std::nothrow) amsm_ctx();
@@ -83,7 +83,7 @@ int amsm_ctx_create(amsm_ctx** out, int curve, int device_id, void* stream) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) {
       c->cu_count = prop.multiProcessorCount;
-      int per_cu = curve == AMSM_PALLAS ? accum_l0_blocks_per_cu<PallasFq>() : accum_l0_blocks_per_cu<Bls12381Fq>();
+      int per_cu = with_curve(curve, [](auto cv) { return accum_l0_blocks_per_cu<typename decltype(cv)::Fq>(); });
       c->wave_slots = prop.multiProcessorCount * std::max(1, per_cu) * 4;
     }
   }
@@ -303,7 +303,7 @@ const char* amsm_ctx_collective(const amsm_ctx* c) {
 
 int amsm_ctx_is_host(const amsm_ctx* c) { return c && c->host_only ? 1 : 0; }
 int amsm_ctx_curve(const amsm_ctx* c) { return c ? c->curve : AMSM_E_INVALID_ARG; }
-int amsm_ctx_fq_limbs(const amsm_ctx* c) { return !c ? AMSM_E_INVALID_ARG : (c->curve == AMSM_PALLAS ? 4 : 6); }
+int amsm_ctx_fq_limbs(const amsm_ctx* c) { return !c ? AMSM_E_INVALID_ARG : curve_fq_limbs(c->curve); }
 int amsm_ctx_set_window(amsm_ctx* c, int bits) {
   if (!c || (bits != 0 && (bits < 2 || bits > 24))) return AMSM_E_INVALID_ARG;
   c->window_override = bits;

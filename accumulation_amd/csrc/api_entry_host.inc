@@ -3,10 +3,10 @@
 int amsm_host_lincomb(int curve, const uint64_t* xy, const uint8_t* is_inf, const uint64_t* scalars_mont, size_t n,
                       uint64_t* out_xy, uint8_t* out_inf) {
   if (!out_xy || (n && (!xy || !scalars_mont))) return AMSM_E_INVALID_ARG;
-  if (curve == AMSM_PALLAS) return host_lincomb_impl<PallasFq, PallasFr>(xy, is_inf, scalars_mont, n, out_xy, out_inf);
-  if (curve == AMSM_BLS12_381_G1)
-    return host_lincomb_impl<Bls12381Fq, Bls12381Fr>(xy, is_inf, scalars_mont, n, out_xy, out_inf);
-  return AMSM_E_INVALID_ARG;
+  return with_curve(curve, [&](auto cv) {
+    AMSM_CURVE_FIELDS(cv);
+    return host_lincomb_impl<Fq, Fr>(xy, is_inf, scalars_mont, n, out_xy, out_inf);
+  });
 }
 
 int amsm_host_lincomb_batch(int curve, size_t n_jobs, const size_t* n_terms, const uint64_t* const* xy, const uint8_t* const* is_inf,
@@ -14,11 +14,10 @@ int amsm_host_lincomb_batch(int curve, size_t n_jobs, const size_t* n_terms, con
   if (n_jobs && (!n_terms || !xy || !scalars_mont || !out_xy)) return AMSM_E_INVALID_ARG;
   for (size_t j = 0; j < n_jobs; j++)
     if (n_terms[j] && (!xy[j] || !scalars_mont[j])) return AMSM_E_INVALID_ARG;
-  if (curve == AMSM_PALLAS)
-    return host_lincomb_batch_impl<PallasFq, PallasFr>(n_jobs, n_terms, xy, is_inf, scalars_mont, out_xy, out_inf);
-  if (curve == AMSM_BLS12_381_G1)
-    return host_lincomb_batch_impl<Bls12381Fq, Bls12381Fr>(n_jobs, n_terms, xy, is_inf, scalars_mont, out_xy, out_inf);
-  return AMSM_E_INVALID_ARG;
+  return with_curve(curve, [&](auto cv) {
+    AMSM_CURVE_FIELDS(cv);
+    return host_lincomb_batch_impl<Fq, Fr>(n_jobs, n_terms, xy, is_inf, scalars_mont, out_xy, out_inf);
+  });
 }
 
 int amsm_host_threads(void) { return (int)HostPool::get().workers.size(); }
@@ -47,91 +46,82 @@ int amsm_fr_from_mont(int curve, const uint64_t* a_mont, size_t n, uint64_t* out
 
 // ---- wire format (host_serialize.h) ------------------------------------------------------------------------------
 size_t amsm_fr_serialized_size(int curve) {
-  if (curve == AMSM_PALLAS) return host::h_serialized_size<PallasFr>(0);
-  if (curve == AMSM_BLS12_381_G1) return host::h_serialized_size<Bls12381Fr>(0);
-  return 0;
+  return with_curve_or(curve, (size_t)0, [](auto cv) {
+    AMSM_CURVE_FIELDS(cv);
+    return host::h_serialized_size<Fr>(0);
+  });
 }
 size_t amsm_point_serialized_size(int curve, int compressed) {
-  if (curve == AMSM_PALLAS) return host::point_serialized_size<PallasFq>(compressed != 0);
-  if (curve == AMSM_BLS12_381_G1) return host::point_serialized_size<Bls12381Fq>(compressed != 0);
-  return 0;
+  return with_curve_or(curve, (size_t)0, [&](auto cv) {
+    AMSM_CURVE_FIELDS(cv);
+    return host::point_serialized_size<Fq>(compressed != 0);
+  });
 }
 int amsm_fr_serialize(int curve, const uint64_t* a_mont, size_t n, uint8_t* out) {
-  if ((curve != AMSM_PALLAS && curve != AMSM_BLS12_381_G1) || (n && (!a_mont || !out))) return AMSM_E_INVALID_ARG;
-  for (size_t i = 0; i < n; i++) {
-    if (curve == AMSM_PALLAS) {
-      host::HFe<PallasFr> x;
+  if (!curve_known(curve) || (n && (!a_mont || !out))) return AMSM_E_INVALID_ARG;
+  return with_curve(curve, [&](auto cv) {
+    AMSM_CURVE_FIELDS(cv);
+    for (size_t i = 0; i < n; i++) {
+      host::HFe<Fr> x;
       memcpy(x.v, a_mont + 4 * i, 32);
-      host::h_write_le<PallasFr>(x, out + 32 * i, 32);
-    } else {
-      host::HFe<Bls12381Fr> x;
-      memcpy(x.v, a_mont + 4 * i, 32);
-      host::h_write_le<Bls12381Fr>(x, out + 32 * i, 32);
+      host::h_write_le<Fr>(x, out + 32 * i, 32);
     }
-  }
-  return AMSM_OK;
+    return AMSM_OK;
+  });
 }
 int amsm_fr_deserialize(int curve, const uint8_t* in, size_t n, uint64_t* out_mont) {
-  if ((curve != AMSM_PALLAS && curve != AMSM_BLS12_381_G1) || (n && (!in || !out_mont))) return AMSM_E_INVALID_ARG;
-  for (size_t i = 0; i < n; i++) {
-    bool ok;
-    if (curve == AMSM_PALLAS) {
-      host::HFe<PallasFr> x;
-      ok = host::h_read_le<PallasFr>(in + 32 * i, 32, &x);
+  if (!curve_known(curve) || (n && (!in || !out_mont))) return AMSM_E_INVALID_ARG;
+  return with_curve(curve, [&](auto cv) {
+    AMSM_CURVE_FIELDS(cv);
+    for (size_t i = 0; i < n; i++) {
+      host::HFe<Fr> x;
+      const bool ok = host::h_read_le<Fr>(in + 32 * i, 32, &x);
       memcpy(out_mont + 4 * i, x.v, 32);
-    } else {
-      host::HFe<Bls12381Fr> x;
-      ok = host::h_read_le<Bls12381Fr>(in + 32 * i, 32, &x);
-      memcpy(out_mont + 4 * i, x.v, 32);
+      if (!ok) return AMSM_E_INVALID_ARG;
     }
-    if (!ok) return AMSM_E_INVALID_ARG;
-  }
-  return AMSM_OK;
+    return AMSM_OK;
+  });
 }
 int amsm_points_serialize(int curve, const uint64_t* xy_mont, const uint8_t* is_inf, size_t n, int compressed, uint8_t* out) {
-  if ((curve != AMSM_PALLAS && curve != AMSM_BLS12_381_G1) || (n && (!xy_mont || !out))) return AMSM_E_INVALID_ARG;
+  if (!curve_known(curve) || (n && (!xy_mont || !out))) return AMSM_E_INVALID_ARG;
   const size_t sz = amsm_point_serialized_size(curve, compressed);
-  for (size_t i = 0; i < n; i++) {
-    const bool inf = is_inf && is_inf[i];
-    if (curve == AMSM_PALLAS) host::point_serialize<PallasFq>(xy_mont + i * 8, inf, compressed != 0, out + i * sz);
-    else host::point_serialize<Bls12381Fq>(xy_mont + i * 12, inf, compressed != 0, out + i * sz);
-  }
-  return AMSM_OK;
+  return with_curve(curve, [&](auto cv) {
+    AMSM_CURVE_FIELDS(cv);
+    for (size_t i = 0; i < n; i++) {
+      const bool inf = is_inf && is_inf[i];
+      host::point_serialize<Fq>(xy_mont + i * Fq::W, inf, compressed != 0, out + i * sz);
+    }
+    return AMSM_OK;
+  });
 }
 int amsm_points_deserialize(int curve, const uint8_t* in, size_t n, int compressed, uint64_t* xy_mont, uint8_t* is_inf) {
-  if ((curve != AMSM_PALLAS && curve != AMSM_BLS12_381_G1) || (n && (!in || !xy_mont || !is_inf))) return AMSM_E_INVALID_ARG;
+  if (!curve_known(curve) || (n && (!in || !xy_mont || !is_inf))) return AMSM_E_INVALID_ARG;
   const size_t sz = amsm_point_serialized_size(curve, compressed);
-  for (size_t i = 0; i < n; i++) {
-    bool ok;
-    if (curve == AMSM_PALLAS) {  // y^2 = x^3 + 5, cofactor 1
-      ok = host::point_deserialize<PallasFq>(in + i * sz, compressed != 0, 5, false, nullptr, xy_mont + i * 8, is_inf + i);
-    } else {  // y^2 = x^3 + 4; G1 is the order-r subgroup (cofactor != 1)
-      u64 r[4];
-      for (int k = 0; k < 4; k++) r[k] = host::hmod<Bls12381Fr>(k);
-      ok = host::point_deserialize<Bls12381Fq>(in + i * sz, compressed != 0, 4, true, r, xy_mont + i * 12, is_inf + i);
+  return with_curve(curve, [&](auto cv) {
+    AMSM_CURVE_FIELDS(cv);
+    using C = decltype(cv);
+    u64 r[4];  // the subgroup order, for the curves whose points need the check (cofactor != 1)
+    for (int k = 0; k < 4; k++) r[k] = host::hmod<Fr>(k);
+    for (size_t i = 0; i < n; i++) {
+      const bool ok = host::point_deserialize<Fq>(in + i * sz, compressed != 0, C::b, C::subgroup_check,
+                                                  C::subgroup_check ? r : nullptr, xy_mont + i * Fq::W, is_inf + i);
+      if (!ok) return AMSM_E_INVALID_ARG;
     }
-    if (!ok) return AMSM_E_INVALID_ARG;
-  }
-  return AMSM_OK;
+    return AMSM_OK;
+  });
 }
 
 // ---- Poseidon sponge (host_poseidon.h) ---------------------------------------------------------------------------------
-#define SPONGE_DO(s, EXPR_P, EXPR_B) \
-  do {                               \
-    if ((s)->curve == AMSM_PALLAS) { \
-      auto& sp = (s)->pallas;        \
-      using FQ = PallasFq;           \
-      (void)sizeof(FQ);              \
-      EXPR_P;                        \
-    } else {                         \
-      auto& sp = (s)->bls;           \
-      using FQ = Bls12381Fq;         \
-      (void)sizeof(FQ);              \
-      EXPR_B;                        \
-    }                                \
-  } while (0)
+// runs the statement with `sp` = the sponge state of s's curve (a sponge's curve is known: amsm_poseidon_new checks it)
+#define SPONGE_DO(s, ...)                                 \
+  (void)with_curve((s)->curve, [&](auto cv_) {            \
+    using FQ = typename decltype(cv_)::Fq;                \
+    auto& sp = (s)->of<FQ>();                             \
+    __VA_ARGS__;                                          \
+    return AMSM_OK;                                       \
+  })
 int amsm_poseidon_new(int curve, amsm_sponge** out) {
-  if (!out || (curve != AMSM_PALLAS && curve != AMSM_BLS12_381_G1)) return AMSM_E_INVALID_ARG;
+  if (!out || !curve_known(curve)) return AMSM_E_INVALID_ARG;
   amsm_sponge* s = new (std::nothrow) amsm_sponge();
   if (!s) return AMSM_E_OOM;
   s->curve = curve;
@@ -148,22 +138,22 @@ int amsm_poseidon_clone(const amsm_sponge* s, amsm_sponge** out) {
 void amsm_poseidon_free(amsm_sponge* s) { delete s; }
 int amsm_poseidon_absorb_native(amsm_sponge* s, const uint64_t* fq_mont, size_t n) {
   if (!s || (n && !fq_mont)) return AMSM_E_INVALID_ARG;
-  SPONGE_DO(s, sp.absorb_words(fq_mont, n), sp.absorb_words(fq_mont, n));
+  SPONGE_DO(s, sp.absorb_words(fq_mont, n));
   return AMSM_OK;
 }
 int amsm_poseidon_absorb_u64(amsm_sponge* s, uint64_t v) {
   if (!s) return AMSM_E_INVALID_ARG;
-  SPONGE_DO(s, sp.absorb_u64(v), sp.absorb_u64(v));
+  SPONGE_DO(s, sp.absorb_u64(v));
   return AMSM_OK;
 }
 int amsm_poseidon_absorb_bytes(amsm_sponge* s, const uint8_t* b, size_t n) {
   if (!s || (n && !b)) return AMSM_E_INVALID_ARG;
-  SPONGE_DO(s, sp.absorb_bytes(b, n), sp.absorb_bytes(b, n));
+  SPONGE_DO(s, sp.absorb_bytes(b, n));
   return AMSM_OK;
 }
 int amsm_poseidon_absorb_points(amsm_sponge* s, const uint64_t* xy_mont, const uint8_t* is_inf, size_t n) {
   if (!s || (n && !xy_mont)) return AMSM_E_INVALID_ARG;
-  SPONGE_DO(s, sp.absorb_points(xy_mont, is_inf, n), sp.absorb_points(xy_mont, is_inf, n));
+  SPONGE_DO(s, sp.absorb_points(xy_mont, is_inf, n));
   return AMSM_OK;
 }
 int amsm_poseidon_fork(const amsm_sponge* s, const uint8_t* domain, size_t n, amsm_sponge** out) {
@@ -176,13 +166,13 @@ int amsm_poseidon_fork(const amsm_sponge* s, const uint8_t* domain, size_t n, am
 }
 int amsm_poseidon_squeeze_native(amsm_sponge* s, size_t n, uint64_t* out_fq_mont) {
   if (!s || (n && !out_fq_mont)) return AMSM_E_INVALID_ARG;
-  SPONGE_DO(s, sp.squeeze_words(n, out_fq_mont), sp.squeeze_words(n, out_fq_mont));
+  SPONGE_DO(s, sp.squeeze_words(n, out_fq_mont));
   return AMSM_OK;
 }
 int amsm_poseidon_squeeze_bits(amsm_sponge* s, size_t n_bits, uint8_t* out_bytes) {
   if (!s || (n_bits && !out_bytes)) return AMSM_E_INVALID_ARG;
   std::vector<uint8_t> b;
-  SPONGE_DO(s, b = sp.squeeze_bits(n_bits), b = sp.squeeze_bits(n_bits));
+  SPONGE_DO(s, b = sp.squeeze_bits(n_bits));
   if (!b.empty()) memcpy(out_bytes, b.data(), b.size());
   return AMSM_OK;
 }
@@ -190,7 +180,7 @@ int amsm_poseidon_squeeze_nonnative(amsm_sponge* s, unsigned n_bits, size_t coun
   if (!s || (count && !out_canonical) || n_bits == 0 || n_bits > 254) return AMSM_E_INVALID_ARG;
   std::vector<uint8_t> b;
   const size_t total = (size_t)n_bits * count;
-  SPONGE_DO(s, b = sp.squeeze_bits(total), b = sp.squeeze_bits(total));
+  SPONGE_DO(s, b = sp.squeeze_bits(total));
   memset(out_canonical, 0, count * 32);
   for (size_t k = 0; k < count; k++)
     for (unsigned i = 0; i < n_bits; i++) {
@@ -200,15 +190,10 @@ int amsm_poseidon_squeeze_nonnative(amsm_sponge* s, unsigned n_bits, size_t coun
   return AMSM_OK;
 }
 int amsm_poseidon_permute(int curve, uint64_t* state_mont) {
-  if (!state_mont || (curve != AMSM_PALLAS && curve != AMSM_BLS12_381_G1)) return AMSM_E_INVALID_ARG;
+  if (!state_mont || !curve_known(curve)) return AMSM_E_INVALID_ARG;
   amsm_sponge s;
   s.curve = curve;
   SPONGE_DO(&s, {
-    constexpr int N = host::HFe<FQ>::N;
-    for (int i = 0; i < 3; i++) memcpy(sp.state[i].v, state_mont + i * N, 8 * N);
-    sp.permute();
-    for (int i = 0; i < 3; i++) memcpy(state_mont + i * N, sp.state[i].v, 8 * N);
-  }, {
     constexpr int N = host::HFe<FQ>::N;
     for (int i = 0; i < 3; i++) memcpy(sp.state[i].v, state_mont + i * N, 8 * N);
     sp.permute();
@@ -217,17 +202,15 @@ int amsm_poseidon_permute(int curve, uint64_t* state_mont) {
   return AMSM_OK;
 }
 int amsm_poseidon_round_constants(int curve, uint64_t* out_mont) {  // (8 + 31) * 3 elements, round-major
-  if (!out_mont || (curve != AMSM_PALLAS && curve != AMSM_BLS12_381_G1)) return AMSM_E_INVALID_ARG;
-  if (curve == AMSM_PALLAS) {
-    const auto& p = host::PoseidonParams<PallasFq>::get();
+  if (!out_mont) return AMSM_E_INVALID_ARG;
+  return with_curve(curve, [&](auto cv) {
+    AMSM_CURVE_FIELDS(cv);
+    constexpr int N = host::HFe<Fq>::N;
+    const auto& p = host::PoseidonParams<Fq>::get();
     for (int r = 0; r < 39; r++)
-      for (int i = 0; i < 3; i++) memcpy(out_mont + (r * 3 + i) * 4, p.ark[r][i].v, 32);
-  } else {
-    const auto& p = host::PoseidonParams<Bls12381Fq>::get();
-    for (int r = 0; r < 39; r++)
-      for (int i = 0; i < 3; i++) memcpy(out_mont + (r * 3 + i) * 6, p.ark[r][i].v, 48);
-  }
-  return AMSM_OK;
+      for (int i = 0; i < 3; i++) memcpy(out_mont + (r * 3 + i) * N, p.ark[r][i].v, 8 * N);
+    return AMSM_OK;
+  });
 }
 
 // ---- page-locked caller memory (include/amsm.h: amsm_host_register) ----

@@ -6,20 +6,17 @@ int amsm_bases_load(amsm_ctx* c, const uint64_t* xy, const uint8_t* is_inf, size
   TRY(bind_device(c));
   if (wants_replicas(c, n, flags))  // (round 6) every device loads the whole key
     return bases_create_replicated(c, out, [&](size_t, amsm_ctx* cg, amsm_bases** o) {
-      return DISPATCH(cg, (bases_load_impl<PallasFq, PallasFr>(cg, xy, is_inf, n, flags & ~(unsigned)AMSM_BASES_REPLICATE, o)),
-                      (bases_load_impl<Bls12381Fq, Bls12381Fr>(cg, xy, is_inf, n, flags & ~(unsigned)AMSM_BASES_REPLICATE, o)));
+      return DISPATCH(cg, bases_load_impl<Fq, Fr>(cg, xy, is_inf, n, flags & ~(unsigned)AMSM_BASES_REPLICATE, o));
     });
   flags &= ~(unsigned)AMSM_BASES_REPLICATE;
   if (ctx_shards_keys(c)) {  // shard g copies its own range of the caller's arrays
     const size_t L2 = 2 * (size_t)amsm_ctx_fq_limbs(c);
     return bases_create_sharded(c, n, out, [&](size_t, amsm_ctx* cg, size_t lo, size_t cnt, amsm_bases** o) {
       // the impl, not the entry point: shard 0's context IS this (multi-device) context
-      return DISPATCH(cg, (bases_load_impl<PallasFq, PallasFr>(cg, xy + lo * L2, is_inf ? is_inf + lo : nullptr, cnt, flags, o)),
-                      (bases_load_impl<Bls12381Fq, Bls12381Fr>(cg, xy + lo * L2, is_inf ? is_inf + lo : nullptr, cnt, flags, o)));
+      return DISPATCH(cg, bases_load_impl<Fq, Fr>(cg, xy + lo * L2, is_inf ? is_inf + lo : nullptr, cnt, flags, o));
     });
   }
-  return DISPATCH(c, (bases_load_impl<PallasFq, PallasFr>(c, xy, is_inf, n, flags, out)),
-                  (bases_load_impl<Bls12381Fq, Bls12381Fr>(c, xy, is_inf, n, flags, out)));
+  return DISPATCH(c, bases_load_impl<Fq, Fr>(c, xy, is_inf, n, flags, out));
 }
 int amsm_bases_generate(amsm_ctx* c, uint64_t seed, size_t n, unsigned flags, amsm_bases** out) {
   if (!c || !out) return AMSM_E_INVALID_ARG;
@@ -28,17 +25,14 @@ int amsm_bases_generate(amsm_ctx* c, uint64_t seed, size_t n, unsigned flags, am
   TRY(bind_device(c));
   if (wants_replicas(c, n, flags))  // (round 6) every device generates the whole key
     return bases_create_replicated(c, out, [&](size_t, amsm_ctx* cg, amsm_bases** o) {
-      return DISPATCH(cg, (bases_generate_impl<PallasFq, PallasFr>(cg, seed, n, flags & ~(unsigned)AMSM_BASES_REPLICATE, o)),
-                      (bases_generate_impl<Bls12381Fq, Bls12381Fr>(cg, seed, n, flags & ~(unsigned)AMSM_BASES_REPLICATE, o)));
+      return DISPATCH(cg, bases_generate_impl<Fq, Fr>(cg, seed, n, flags & ~(unsigned)AMSM_BASES_REPLICATE, o));
     });
   flags &= ~(unsigned)AMSM_BASES_REPLICATE;
   if (ctx_shards_keys(c))  // shard g generates its own range of the synthetic stream
     return bases_create_sharded(c, n, out, [&](size_t, amsm_ctx* cg, size_t lo, size_t cnt, amsm_bases** o) {
-      return DISPATCH(cg, (bases_generate_impl<PallasFq, PallasFr>(cg, seed, cnt, flags, o, lo)),
-                      (bases_generate_impl<Bls12381Fq, Bls12381Fr>(cg, seed, cnt, flags, o, lo)));
+      return DISPATCH(cg, bases_generate_impl<Fq, Fr>(cg, seed, cnt, flags, o, lo));
     });
-  return DISPATCH(c, (bases_generate_impl<PallasFq, PallasFr>(c, seed, n, flags, out)),
-                  (bases_generate_impl<Bls12381Fq, Bls12381Fr>(c, seed, n, flags, out)));
+  return DISPATCH(c, bases_generate_impl<Fq, Fr>(c, seed, n, flags, out));
 }
 int amsm_bases_read(amsm_ctx* c, const amsm_bases* b, size_t off, size_t n, uint64_t* xy, uint8_t* is_inf) {
   if (!c || !b || (n && !xy) || b->curve != c->curve) return AMSM_E_INVALID_ARG;
@@ -54,10 +48,9 @@ int amsm_bases_read(amsm_ctx* c, const amsm_bases* b, size_t off, size_t n, uint
     return bind_device(c);
   }
   if (c->host_only != b->host) return AMSM_E_INVALID_ARG;
-  if (b->host) return c->curve == AMSM_PALLAS ? cpu::bases_read<PallasFq>(b, off, n, xy, is_inf) : cpu::bases_read<Bls12381Fq>(b, off, n, xy, is_inf);
+  if (b->host) return DISPATCH(c, cpu::bases_read<Fq>(b, off, n, xy, is_inf));
   TRY(bind_device(c));
-  return DISPATCH(c, (bases_read_impl<PallasFq>(c, b, off, n, xy, is_inf)),
-                  (bases_read_impl<Bls12381Fq>(c, b, off, n, xy, is_inf)));
+  return DISPATCH(c, bases_read_impl<Fq>(c, b, off, n, xy, is_inf));
 }
 size_t amsm_bases_len(const amsm_bases* b) { return b ? b->n : 0; }
 int amsm_bases_precomputed(const amsm_bases* b) { return b ? b->precomp : 0; }
@@ -84,7 +77,7 @@ int amsm_bases_memory(const amsm_bases* b, size_t* table_bytes, size_t* abi_copy
       t += t1, a += a1, w += w1;
     }
   } else {
-    const size_t pb = b->curve == AMSM_PALLAS ? affine_bytes<PallasFq>() : affine_bytes<Bls12381Fq>();
+    const size_t pb = DISPATCH(b, affine_bytes<Fq>());
     t = std::max<size_t>(b->n, 1) * (b->precomp ? (size_t)b->W : 1) * pb;
     if (b->d_small) t += b->n * (size_t)(DS_W * DS_MULT) * pb;  // a small key's direct-sum table
     {
@@ -121,7 +114,7 @@ int amsm_bases_tables(const amsm_bases* b, size_t out[7]) {
     }
     return AMSM_OK;
   }
-  const size_t pb = b->curve == AMSM_PALLAS ? affine_bytes<PallasFq>() : affine_bytes<Bls12381Fq>();
+  const size_t pb = DISPATCH(b, affine_bytes<Fq>());
   out[0] = std::max<size_t>(b->n, 1) * (b->precomp ? (size_t)b->W : 1) * pb;
   out[1] = b->d_small ? b->n * (size_t)(DS_W * DS_MULT) * pb : 0;
   {
@@ -146,7 +139,7 @@ int amsm_bases_prebuild_twin(amsm_ctx* c, const amsm_bases* b) {
   if (!b->bpl || b->host) return AMSM_OK;
   TRY(bind_device(c));
   const amsm_bases* alt = nullptr;
-  return DISPATCH(c, bases_alt<PallasFq>(c, b, &alt), bases_alt<Bls12381Fq>(c, b, &alt));
+  return DISPATCH(c, bases_alt<Fq>(c, b, &alt));
 }
 void amsm_bases_free(amsm_bases* b) {
   if (!b) return;
@@ -176,15 +169,11 @@ void amsm_bases_free(amsm_bases* b) {
 static int msm_sharded_affine(amsm_ctx* c, const amsm_bases* b, size_t off, size_t n, size_t n_vecs, int mont, SliceKind kind,
                               const void* const* srcs, uint64_t* out_xy, uint8_t* out_inf) {
   TRY(bind_device(c));
-  if (c->curve == AMSM_PALLAS) {
-    std::vector<host::HXYZZ<PallasFq>> r;
-    TRY((msm_sharded<PallasFq, PallasFr>(c, b, off, n, n_vecs, mont, kind, srcs, &r)));
-    write_affine_batch<PallasFq>(r, out_xy, out_inf);
-  } else {
-    std::vector<host::HXYZZ<Bls12381Fq>> r;
-    TRY((msm_sharded<Bls12381Fq, Bls12381Fr>(c, b, off, n, n_vecs, mont, kind, srcs, &r)));
-    write_affine_batch<Bls12381Fq>(r, out_xy, out_inf);
-  }
+  TRY(DISPATCH_DO(c, {
+    std::vector<host::HXYZZ<Fq>> r;
+    TRY((msm_sharded<Fq, Fr>(c, b, off, n, n_vecs, mont, kind, srcs, &r)));
+    write_affine_batch<Fq>(r, out_xy, out_inf);
+  }));
   return AMSM_OK;
 }
 
@@ -197,15 +186,11 @@ int amsm_msm(amsm_ctx* c, const amsm_bases* b, size_t off, const uint64_t* scala
   }
   if (c->host_only) return CPU_CALL(c, msm_affine, b, off, scalars, n, mont, out_xy, out_inf);
   TRY(bind_device(c));
-  if (c->curve == AMSM_PALLAS) {
-    host::HXYZZ<PallasFq> r;
-    TRY((msm_host_scalars<PallasFq, PallasFr>(c, b, off, scalars, n, mont, &r)));
-    write_affine<PallasFq>(r, out_xy, out_inf);
-  } else {
-    host::HXYZZ<Bls12381Fq> r;
-    TRY((msm_host_scalars<Bls12381Fq, Bls12381Fr>(c, b, off, scalars, n, mont, &r)));
-    write_affine<Bls12381Fq>(r, out_xy, out_inf);
-  }
+  TRY(DISPATCH_DO(c, {
+    host::HXYZZ<Fq> r;
+    TRY((msm_host_scalars<Fq, Fr>(c, b, off, scalars, n, mont, &r)));
+    write_affine<Fq>(r, out_xy, out_inf);
+  }));
   return AMSM_OK;
 }
 
@@ -221,8 +206,7 @@ int amsm_msm_oneshot(amsm_ctx* c, const uint64_t* xy, const uint8_t* is_inf, siz
     amsm_bases_free(b);
     return rc;
   }
-  return DISPATCH(c, (msm_oneshot_any<PallasFq, PallasFr>(c, xy, is_inf, scalars, n, mont, out_xy, out_inf)),
-                  (msm_oneshot_any<Bls12381Fq, Bls12381Fr>(c, xy, is_inf, scalars, n, mont, out_xy, out_inf)));
+  return DISPATCH(c, msm_oneshot_any<Fq, Fr>(c, xy, is_inf, scalars, n, mont, out_xy, out_inf));
 }
 
 int amsm_msm_device(amsm_ctx* c, const amsm_bases* b, size_t off, const void* d_scalars, size_t n, int mont,
@@ -231,15 +215,11 @@ int amsm_msm_device(amsm_ctx* c, const amsm_bases* b, size_t off, const void* d_
   if (key_sharded(b)) return msm_sharded_affine(c, b, off, n, 1, mont, SLICE_PRIMARY, &d_scalars, out_xy, out_inf);
   if (c->host_only) return CPU_CALL(c, msm_affine, b, off, d_scalars, n, mont, out_xy, out_inf);
   TRY(bind_device(c));
-  if (c->curve == AMSM_PALLAS) {
-    host::HXYZZ<PallasFq> r;
-    TRY((msm_device_xyzz<PallasFq, PallasFr>(c, b, off, d_scalars, n, mont, &r)));
-    write_affine<PallasFq>(r, out_xy, out_inf);
-  } else {
-    host::HXYZZ<Bls12381Fq> r;
-    TRY((msm_device_xyzz<Bls12381Fq, Bls12381Fr>(c, b, off, d_scalars, n, mont, &r)));
-    write_affine<Bls12381Fq>(r, out_xy, out_inf);
-  }
+  TRY(DISPATCH_DO(c, {
+    host::HXYZZ<Fq> r;
+    TRY((msm_device_xyzz<Fq, Fr>(c, b, off, d_scalars, n, mont, &r)));
+    write_affine<Fq>(r, out_xy, out_inf);
+  }));
   return AMSM_OK;
 }
 
@@ -256,19 +236,14 @@ int amsm_msm_batch_device(amsm_ctx* c, const amsm_bases* b, size_t off, const vo
   if (key_replicated(b) && n_vecs >= 2 && b->owner == c) {  // (round 6) whole MSMs dealt to the devices, no exchange
     TRY(bind_device(c));
     std::vector<size_t> r_ns(n_vecs, n);
-    return DISPATCH(c, (msm_replicated_affine<PallasFq, PallasFr>(c, b, off, r_ns.data(), n_vecs, mont, SLICE_PRIMARY, d_scalars, nullptr, nullptr, out_xy, out_inf)),
-                    (msm_replicated_affine<Bls12381Fq, Bls12381Fr>(c, b, off, r_ns.data(), n_vecs, mont, SLICE_PRIMARY, d_scalars, nullptr, nullptr, out_xy, out_inf)));
+    return DISPATCH(c, msm_replicated_affine<Fq, Fr>(c, b, off, r_ns.data(), n_vecs, mont, SLICE_PRIMARY, d_scalars, nullptr, nullptr, out_xy, out_inf));
   }
   TRY(bind_device(c));
-  if (c->curve == AMSM_PALLAS) {
-    std::vector<host::HXYZZ<PallasFq>> r;
-    TRY((msm_batch_xyzz<PallasFq, PallasFr>(c, b, off, d_scalars, n_vecs, n, mont, &r)));
-    write_affine_batch<PallasFq>(r, out_xy, out_inf);
-  } else {
-    std::vector<host::HXYZZ<Bls12381Fq>> r;
-    TRY((msm_batch_xyzz<Bls12381Fq, Bls12381Fr>(c, b, off, d_scalars, n_vecs, n, mont, &r)));
-    write_affine_batch<Bls12381Fq>(r, out_xy, out_inf);
-  }
+  TRY(DISPATCH_DO(c, {
+    std::vector<host::HXYZZ<Fq>> r;
+    TRY((msm_batch_xyzz<Fq, Fr>(c, b, off, d_scalars, n_vecs, n, mont, &r)));
+    write_affine_batch<Fq>(r, out_xy, out_inf);
+  }));
   return AMSM_OK;
 }
 
@@ -287,12 +262,9 @@ int amsm_msm_batch(amsm_ctx* c, const amsm_bases* b, size_t off, const uint64_t*
   TRY(bind_device(c));
   std::vector<size_t> ns(n_vecs, n);
   if (key_replicated(b) && n_vecs >= 2 && b->owner == c)
-    return DISPATCH(c, (msm_replicated_affine<PallasFq, PallasFr>(c, b, off, ns.data(), n_vecs, mont, SLICE_HOST, (const void* const*)scalars, nullptr, nullptr, out_xy, out_inf)),
-                    (msm_replicated_affine<Bls12381Fq, Bls12381Fr>(c, b, off, ns.data(), n_vecs, mont, SLICE_HOST, (const void* const*)scalars, nullptr, nullptr, out_xy, out_inf)));
-  return DISPATCH(c, (msm_host_batch_impl<PallasFq, PallasFr>(c, b, off, scalars, ns.data(), n_vecs, mont, nullptr, nullptr,
-                                                              out_xy, out_inf)),
-                  (msm_host_batch_impl<Bls12381Fq, Bls12381Fr>(c, b, off, scalars, ns.data(), n_vecs, mont, nullptr, nullptr,
-                                                               out_xy, out_inf)));
+    return DISPATCH(c, msm_replicated_affine<Fq, Fr>(c, b, off, ns.data(), n_vecs, mont, SLICE_HOST, (const void* const*)scalars, nullptr, nullptr, out_xy, out_inf));
+  return DISPATCH(c, msm_host_batch_impl<Fq, Fr>(c, b, off, scalars, ns.data(), n_vecs, mont, nullptr, nullptr,
+                                                              out_xy, out_inf));
 }
 
 int amsm_pedersen_commit_batch(amsm_ctx* c, const amsm_bases* ck, const uint64_t* const* elems, const size_t* ns, size_t n_vecs,
@@ -319,12 +291,9 @@ int amsm_pedersen_commit_batch(amsm_ctx* c, const amsm_bases* ck, const uint64_t
   }
   TRY(bind_device(c));
   if (key_replicated(ck) && n_vecs >= 2 && ck->owner == c)
-    return DISPATCH(c, (msm_replicated_affine<PallasFq, PallasFr>(c, ck, 0, ns, n_vecs, 1, SLICE_HOST, (const void* const*)elems, any_rand ? rand_mont : nullptr, hiding_xy, out_xy, out_inf)),
-                    (msm_replicated_affine<Bls12381Fq, Bls12381Fr>(c, ck, 0, ns, n_vecs, 1, SLICE_HOST, (const void* const*)elems, any_rand ? rand_mont : nullptr, hiding_xy, out_xy, out_inf)));
-  return DISPATCH(c, (msm_host_batch_impl<PallasFq, PallasFr>(c, ck, 0, elems, ns, n_vecs, 1, any_rand ? rand_mont : nullptr,
-                                                              hiding_xy, out_xy, out_inf)),
-                  (msm_host_batch_impl<Bls12381Fq, Bls12381Fr>(c, ck, 0, elems, ns, n_vecs, 1, any_rand ? rand_mont : nullptr,
-                                                               hiding_xy, out_xy, out_inf)));
+    return DISPATCH(c, msm_replicated_affine<Fq, Fr>(c, ck, 0, ns, n_vecs, 1, SLICE_HOST, (const void* const*)elems, any_rand ? rand_mont : nullptr, hiding_xy, out_xy, out_inf));
+  return DISPATCH(c, msm_host_batch_impl<Fq, Fr>(c, ck, 0, elems, ns, n_vecs, 1, any_rand ? rand_mont : nullptr,
+                                                              hiding_xy, out_xy, out_inf));
 }
 
 int amsm_msm_multi_device(amsm_ctx* c, const amsm_bases* b, size_t n_msms, const size_t* base_offs,
@@ -341,15 +310,11 @@ int amsm_msm_multi_device(amsm_ctx* c, const amsm_bases* b, size_t n_msms, const
     for (size_t v = 0; v < n_msms;) {
       size_t e = v + 1;
       while (e < n_msms && base_offs[e] == base_offs[v] && ns[e] == ns[v]) e++;
-      if (c->curve == AMSM_PALLAS) {
-        std::vector<host::HXYZZ<PallasFq>> r;
-        TRY((msm_sharded<PallasFq, PallasFr>(c, b, base_offs[v], ns[v], e - v, mont, SLICE_PRIMARY, d_scalars + v, &r)));
-        write_affine_batch<PallasFq>(r, out_xy + v * L2, out_inf ? out_inf + v : nullptr);
-      } else {
-        std::vector<host::HXYZZ<Bls12381Fq>> r;
-        TRY((msm_sharded<Bls12381Fq, Bls12381Fr>(c, b, base_offs[v], ns[v], e - v, mont, SLICE_PRIMARY, d_scalars + v, &r)));
-        write_affine_batch<Bls12381Fq>(r, out_xy + v * L2, out_inf ? out_inf + v : nullptr);
-      }
+      TRY(DISPATCH_DO(c, {
+        std::vector<host::HXYZZ<Fq>> r;
+        TRY((msm_sharded<Fq, Fr>(c, b, base_offs[v], ns[v], e - v, mont, SLICE_PRIMARY, d_scalars + v, &r)));
+        write_affine_batch<Fq>(r, out_xy + v * L2, out_inf ? out_inf + v : nullptr);
+      }));
       v = e;
     }
     return AMSM_OK;
@@ -360,17 +325,12 @@ int amsm_msm_multi_device(amsm_ctx* c, const amsm_bases* b, size_t n_msms, const
   // jobs -- the two cross commitments of an IPA round -- keep the direct path and its single synchronisation
   bool split = false;
   for (size_t v = 0; v < n_msms; v++) split = split || (base_offs[v] <= b->n && split_needed(c, b, std::min(ns[v], b->n - base_offs[v])));
-  if (c->curve == AMSM_PALLAS) {
-    std::vector<host::HXYZZ<PallasFq>> r;
-    if (split) TRY((msm_multi_split_xyzz<PallasFq, PallasFr>(c, b, n_msms, base_offs, d_scalars, ns, mont, &r)));
-    else TRY((msm_multi_xyzz<PallasFq, PallasFr>(c, b, n_msms, base_offs, d_scalars, ns, mont, &r)));
-    write_affine_batch<PallasFq>(r, out_xy, out_inf);
-  } else {
-    std::vector<host::HXYZZ<Bls12381Fq>> r;
-    if (split) TRY((msm_multi_split_xyzz<Bls12381Fq, Bls12381Fr>(c, b, n_msms, base_offs, d_scalars, ns, mont, &r)));
-    else TRY((msm_multi_xyzz<Bls12381Fq, Bls12381Fr>(c, b, n_msms, base_offs, d_scalars, ns, mont, &r)));
-    write_affine_batch<Bls12381Fq>(r, out_xy, out_inf);
-  }
+  TRY(DISPATCH_DO(c, {
+    std::vector<host::HXYZZ<Fq>> r;
+    if (split) TRY((msm_multi_split_xyzz<Fq, Fr>(c, b, n_msms, base_offs, d_scalars, ns, mont, &r)));
+    else TRY((msm_multi_xyzz<Fq, Fr>(c, b, n_msms, base_offs, d_scalars, ns, mont, &r)));
+    write_affine_batch<Fq>(r, out_xy, out_inf);
+  }));
   return AMSM_OK;
 }
 
@@ -379,26 +339,21 @@ int amsm_msm_grouped_device(amsm_ctx* c, const amsm_bases* b, size_t off, const 
   if (!c || !b || !out_xy || (n && !d_scalars) || group_shift > 31 || !key_matches(c, b)) return AMSM_E_INVALID_ARG;
   if (key_sharded(b)) {  // (round 5) every shard sums its part of both index classes; one exchange of two records per shard
     TRY(bind_device(c));
-    if (c->curve == AMSM_PALLAS) {
-      std::vector<host::HXYZZ<PallasFq>> r;
-      TRY((msm_sharded<PallasFq, PallasFr>(c, b, off, n, 1, mont, SLICE_PRIMARY, &d_scalars, &r, (int)group_shift)));
-      write_affine_batch<PallasFq>(r, out_xy, out_inf);
-    } else {
-      std::vector<host::HXYZZ<Bls12381Fq>> r;
-      TRY((msm_sharded<Bls12381Fq, Bls12381Fr>(c, b, off, n, 1, mont, SLICE_PRIMARY, &d_scalars, &r, (int)group_shift)));
-      write_affine_batch<Bls12381Fq>(r, out_xy, out_inf);
-    }
+    TRY(DISPATCH_DO(c, {
+      std::vector<host::HXYZZ<Fq>> r;
+      TRY((msm_sharded<Fq, Fr>(c, b, off, n, 1, mont, SLICE_PRIMARY, &d_scalars, &r, (int)group_shift)));
+      write_affine_batch<Fq>(r, out_xy, out_inf);
+    }));
     return AMSM_OK;
   }
   if (c->host_only) return CPU_CALL(c, msm_grouped, b, off, d_scalars, n, mont, group_shift, out_xy, out_inf);
   TRY(bind_device(c));
-  return DISPATCH(c, (msm_grouped_impl<PallasFq, PallasFr>(c, b, off, d_scalars, n, mont, group_shift, out_xy, out_inf)),
-                  (msm_grouped_impl<Bls12381Fq, Bls12381Fr>(c, b, off, d_scalars, n, mont, group_shift, out_xy, out_inf)));
+  return DISPATCH(c, msm_grouped_impl<Fq, Fr>(c, b, off, d_scalars, n, mont, group_shift, out_xy, out_inf));
 }
 
 size_t amsm_partial_bytes(const amsm_ctx* c) {
   if (!c) return 0;
-  return c->curve == AMSM_PALLAS ? xyzz_bytes<PallasFq>() : xyzz_bytes<Bls12381Fq>();
+  return DISPATCH(c, xyzz_bytes<Fq>());
 }
 
 int amsm_msm_partial_device(amsm_ctx* c, const amsm_bases* b, size_t off, const void* d_scalars, size_t n, int mont,
@@ -408,8 +363,7 @@ int amsm_msm_partial_device(amsm_ctx* c, const amsm_bases* b, size_t off, const 
   if (key_sharded(b)) return AMSM_E_UNSUPPORTED;  // does not shard (include/amsm.h: amsm_ctx_create_multi)
   if (c->host_only) return CPU_CALL(c, msm_partial_batch, b, off, &d_scalars, 1, n, mont, d_out);
   TRY(bind_device(c));
-  return DISPATCH(c, (msm_partial_impl<PallasFq, PallasFr>(c, b, off, d_scalars, n, mont, d_out)),
-                  (msm_partial_impl<Bls12381Fq, Bls12381Fr>(c, b, off, d_scalars, n, mont, d_out)));
+  return DISPATCH(c, msm_partial_impl<Fq, Fr>(c, b, off, d_scalars, n, mont, d_out));
 }
 
 int amsm_msm_partial_batch_device(amsm_ctx* c, const amsm_bases* b, size_t off, const void* const* d_scalars, size_t n_vecs,
@@ -421,8 +375,7 @@ int amsm_msm_partial_batch_device(amsm_ctx* c, const amsm_bases* b, size_t off, 
   if (key_sharded(b)) return AMSM_E_UNSUPPORTED;  // does not shard (include/amsm.h: amsm_ctx_create_multi)
   if (c->host_only) return CPU_CALL(c, msm_partial_batch, b, off, d_scalars, n_vecs, n, mont, d_out);
   TRY(bind_device(c));
-  return DISPATCH(c, (msm_partial_batch_impl<PallasFq, PallasFr>(c, b, off, d_scalars, n_vecs, n, mont, d_out)),
-                  (msm_partial_batch_impl<Bls12381Fq, Bls12381Fr>(c, b, off, d_scalars, n_vecs, n, mont, d_out)));
+  return DISPATCH(c, msm_partial_batch_impl<Fq, Fr>(c, b, off, d_scalars, n_vecs, n, mont, d_out));
 }
 
 int amsm_partials_combine_batch(amsm_ctx* c, const void* d_partials, size_t n_groups, size_t count, uint64_t* out_xy,
@@ -430,23 +383,20 @@ int amsm_partials_combine_batch(amsm_ctx* c, const void* d_partials, size_t n_gr
   if (!c || (n_groups && !out_xy) || (n_groups && count && !d_partials)) return AMSM_E_INVALID_ARG;
   if (c->host_only) return CPU_CALL(c, partials_combine_batch, d_partials, n_groups, count, out_xy, out_inf);
   TRY(bind_device(c));
-  return DISPATCH(c, (partials_combine_batch_impl<PallasFq>(c, d_partials, n_groups, count, out_xy, out_inf)),
-                  (partials_combine_batch_impl<Bls12381Fq>(c, d_partials, n_groups, count, out_xy, out_inf)));
+  return DISPATCH(c, partials_combine_batch_impl<Fq>(c, d_partials, n_groups, count, out_xy, out_inf));
 }
 
 int amsm_partials_combine(amsm_ctx* c, const void* d_partials, size_t count, uint64_t* out_xy, uint8_t* out_inf) {
   if (!c || !out_xy || (count && !d_partials)) return AMSM_E_INVALID_ARG;
   if (c->host_only) return CPU_CALL(c, partials_combine_batch, d_partials, 1, count, out_xy, out_inf);
   TRY(bind_device(c));
-  return DISPATCH(c, (partials_combine_impl<PallasFq>(c, d_partials, count, out_xy, out_inf)),
-                  (partials_combine_impl<Bls12381Fq>(c, d_partials, count, out_xy, out_inf)));
+  return DISPATCH(c, partials_combine_impl<Fq>(c, d_partials, count, out_xy, out_inf));
 }
 
 static int pedersen_sharded(amsm_ctx* c, const amsm_bases* ck, size_t n, SliceKind kind, const void* const* src,
                             const uint64_t* rand_mont, const uint64_t* hiding_xy, uint64_t* out_xy, uint8_t* out_inf) {
   TRY(bind_device(c));
-  return DISPATCH(c, (pedersen_sharded_impl<PallasFq, PallasFr>(c, ck, n, kind, src, rand_mont, hiding_xy, out_xy, out_inf)),
-                  (pedersen_sharded_impl<Bls12381Fq, Bls12381Fr>(c, ck, n, kind, src, rand_mont, hiding_xy, out_xy, out_inf)));
+  return DISPATCH(c, pedersen_sharded_impl<Fq, Fr>(c, ck, n, kind, src, rand_mont, hiding_xy, out_xy, out_inf));
 }
 
 int amsm_msm_batch_sharded_device(amsm_ctx* c, const amsm_bases* b, const void* const* d_slices, size_t n_vecs, int mont,
@@ -474,8 +424,7 @@ int amsm_pedersen_commit(amsm_ctx* c, const amsm_bases* ck, const uint64_t* elem
   }
   if (c->host_only) return CPU_CALL(c, pedersen, ck, elems, n, rand_mont, hiding_xy, out_xy, out_inf);
   TRY(bind_device(c));
-  return DISPATCH(c, (pedersen_impl<PallasFq, PallasFr>(c, ck, elems, n, rand_mont, hiding_xy, out_xy, out_inf)),
-                  (pedersen_impl<Bls12381Fq, Bls12381Fr>(c, ck, elems, n, rand_mont, hiding_xy, out_xy, out_inf)));
+  return DISPATCH(c, pedersen_impl<Fq, Fr>(c, ck, elems, n, rand_mont, hiding_xy, out_xy, out_inf));
 }
 
 int amsm_pedersen_commit_device(amsm_ctx* c, const amsm_bases* ck, const void* d_elems, size_t n,
@@ -485,7 +434,5 @@ int amsm_pedersen_commit_device(amsm_ctx* c, const amsm_bases* ck, const void* d
   if (key_sharded(ck)) return pedersen_sharded(c, ck, n, SLICE_PRIMARY, &d_elems, rand_mont, hiding_xy, out_xy, out_inf);
   if (c->host_only) return CPU_CALL(c, pedersen, ck, d_elems, n, rand_mont, hiding_xy, out_xy, out_inf);
   TRY(bind_device(c));
-  return DISPATCH(c, (pedersen_device_impl<PallasFq, PallasFr>(c, ck, d_elems, n, rand_mont, hiding_xy, out_xy, out_inf)),
-                  (pedersen_device_impl<Bls12381Fq, Bls12381Fr>(c, ck, d_elems, n, rand_mont, hiding_xy, out_xy,
-                                                                out_inf)));
+  return DISPATCH(c, pedersen_device_impl<Fq, Fr>(c, ck, d_elems, n, rand_mont, hiding_xy, out_xy, out_inf));
 }

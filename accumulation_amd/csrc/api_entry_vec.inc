@@ -196,10 +196,7 @@ int amsm_vec_random(amsm_ctx* c, uint64_t seed, size_t n, int mont, void* d_out)
   if (c->host_only) return CPU_CALL(c, vec_random, seed, n, mont, d_out);
   TRY(bind_device(c));
   if (!n) return AMSM_OK;
-  if (c->curve == AMSM_PALLAS)
-    launch_vec_random<PallasFr>(c->stream, (u32*)d_out, seed, (u32)n, mont);
-  else
-    launch_vec_random<Bls12381Fr>(c->stream, (u32*)d_out, seed, (u32)n, mont);
+  DISPATCH_DO(c, launch_vec_random<Fr>(c->stream, (u32*)d_out, seed, (u32)n, mont));
   HIP_TRY(hipGetLastError());
   return AMSM_OK;
 }
@@ -209,10 +206,7 @@ int amsm_vec_hadamard(amsm_ctx* c, const void* d_a, const void* d_b, void* d_out
   if (c->host_only) return CPU_CALL(c, vec_hadamard, d_a, d_b, d_out, n);
   TRY(bind_device(c));
   if (!n) return AMSM_OK;
-  if (c->curve == AMSM_PALLAS)
-    launch_vec_hadamard<PallasFr>(c->stream, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, (u32)n);
-  else
-    launch_vec_hadamard<Bls12381Fr>(c->stream, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, (u32)n);
+  DISPATCH_DO(c, launch_vec_hadamard<Fr>(c->stream, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, (u32)n));
   HIP_TRY(hipGetLastError());
   return AMSM_OK;
 }
@@ -222,8 +216,7 @@ int amsm_vec_combine(amsm_ctx* c, const void* const* d_vecs, const size_t* lens,
   if (!c || (n && !d_out) || (n_vecs && (!d_vecs || !coeffs)) || n >= (1ull << 32)) return AMSM_E_INVALID_ARG;
   if (c->host_only) return CPU_CALL(c, vec_combine, d_vecs, lens, n_vecs, coeffs, d_hiding, hiding_len, d_out, n);
   TRY(bind_device(c));
-  return DISPATCH(c, (vec_combine_impl<PallasFr>(c, d_vecs, lens, n_vecs, coeffs, d_hiding, hiding_len, d_out, n)),
-                  (vec_combine_impl<Bls12381Fr>(c, d_vecs, lens, n_vecs, coeffs, d_hiding, hiding_len, d_out, n)));
+  return DISPATCH(c, vec_combine_impl<Fr>(c, d_vecs, lens, n_vecs, coeffs, d_hiding, hiding_len, d_out, n));
 }
 
 int amsm_bases_from_device(amsm_ctx* c, const void* d_xy, size_t n, unsigned flags, amsm_bases** out) {
@@ -235,7 +228,7 @@ int amsm_bases_from_device(amsm_ctx* c, const void* d_xy, size_t n, unsigned fla
   b->curve = c->curve;
   b->device = c->device;
   b->n = n;
-  size_t pb = (c->curve == AMSM_PALLAS) ? affine_bytes<PallasFq>() : affine_bytes<Bls12381Fq>();
+  size_t pb = DISPATCH(c, affine_bytes<Fq>());
   if (hipMalloc((void**)&b->d_table, std::max<size_t>(n, 1) * pb) != hipSuccess) {
     (void)hipGetLastError();
     delete b;
@@ -245,13 +238,11 @@ int amsm_bases_from_device(amsm_ctx* c, const void* d_xy, size_t n, unsigned fla
   if (n) {
     if (hipMemcpyAsync(b->d_table, d_xy, n * pb, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) s = AMSM_E_HIP;
     if (s == AMSM_OK) {
-      if (c->curve == AMSM_PALLAS) launch_points_import<PallasFq>(c->stream, b->d_table, b->d_table, (u32)n);
-      else launch_points_import<Bls12381Fq>(c->stream, b->d_table, b->d_table, (u32)n);
+      DISPATCH_DO(c, launch_points_import<Fq>(c->stream, b->d_table, b->d_table, (u32)n));
       if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) s = AMSM_E_HIP;
     }
     if (s == AMSM_OK)
-      s = DISPATCH(c, (bases_finish<PallasFq, PallasFr>(c, b, flags ? flags : AMSM_BASES_NO_PRECOMPUTE)),
-                   (bases_finish<Bls12381Fq, Bls12381Fr>(c, b, flags ? flags : AMSM_BASES_NO_PRECOMPUTE)));
+      s = DISPATCH(c, bases_finish<Fq, Fr>(c, b, flags ? flags : AMSM_BASES_NO_PRECOMPUTE));
   }
   if (s != AMSM_OK) {
     (void)hipFree(b->d_table);
@@ -264,21 +255,20 @@ int amsm_bases_from_device(amsm_ctx* c, const void* d_xy, size_t n, unsigned fla
 const void* amsm_bases_device_ptr(const amsm_bases* b) {
   if (!b || key_sharded(b)) return nullptr;
   if (b->host) return b->d_table;  // already in the C-ABI radix
-  bool internal = b->curve == AMSM_PALLAS ? device_internal_radix<PallasFq>() : device_internal_radix<Bls12381Fq>();
+  bool internal = DISPATCH(b, device_internal_radix<Fq>());
   // the table may still be written by the fold that created the key (queued on that context's non-blocking stream,
   // which the NULL stream below does not order behind)
   if (b->ready && hipEventSynchronize(b->ready) != hipSuccess) return nullptr;
   if (!internal) return b->d_table;
   std::lock_guard<std::mutex> lock(b->abi_mu);
   if (!b->d_abi && b->n) {  // the table is in the device radix: hand out a C-ABI-radix copy of level 0
-    size_t pb = (b->curve == AMSM_PALLAS) ? affine_bytes<PallasFq>() : affine_bytes<Bls12381Fq>();
+    size_t pb = DISPATCH(b, affine_bytes<Fq>());
     int prev = 0;
     if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(b->device) != hipSuccess) return nullptr;
     u32* p = nullptr;
     bool ok = hipMalloc((void**)&p, b->n * pb) == hipSuccess;
     if (ok) {
-      if (b->curve == AMSM_PALLAS) launch_points_export<PallasFq>(nullptr, b->d_table, p, (u32)b->n);
-      else launch_points_export<Bls12381Fq>(nullptr, b->d_table, p, (u32)b->n);
+      DISPATCH_DO(b, launch_points_export<Fq>(nullptr, b->d_table, p, (u32)b->n));
       ok = hipStreamSynchronize(nullptr) == hipSuccess && hipGetLastError() == hipSuccess;
       if (!ok) (void)hipFree(p);
     } else {
@@ -291,24 +281,21 @@ const void* amsm_bases_device_ptr(const amsm_bases* b) {
 }
 
 static void canonical_scalar(int curve, const uint64_t* x_mont, u32 out[8]) {
-  if (curve == AMSM_PALLAS) {
-    host::HFe<PallasFr> x;
+  with_curve(curve, [&](auto cv) {
+    AMSM_CURVE_FIELDS(cv);
+    host::HFe<Fr> x;
     memcpy(x.v, x_mont, 32);
-    x = host::h_from_mont<PallasFr>(x);
+    x = host::h_from_mont<Fr>(x);
     memcpy(out, x.v, 32);
-  } else {
-    host::HFe<Bls12381Fr> x;
-    memcpy(x.v, x_mont, 32);
-    x = host::h_from_mont<Bls12381Fr>(x);
-    memcpy(out, x.v, 32);
-  }
+    return AMSM_OK;
+  });
 }
 
 // scratch for the unconverted sums of a large fold (null: the kernel converts in place); stream-ordered reuse is safe
 // because every user runs on the context's stream
 static u32* fold_scratch(amsm_ctx* c, size_t n) {
-  bool pays = c->curve == AMSM_PALLAS ? batch_affine_pays<PallasFq>((u32)n) : batch_affine_pays<Bls12381Fq>((u32)n);
-  size_t rec = c->curve == AMSM_PALLAS ? xyzz_bytes<PallasFq>() : xyzz_bytes<Bls12381Fq>();
+  bool pays = DISPATCH(c, batch_affine_pays<Fq>((u32)n));
+  size_t rec = DISPATCH(c, xyzz_bytes<Fq>());
   if (!pays || ensure(c->xyzz_scratch, n * rec) != AMSM_OK) return nullptr;
   return (u32*)c->xyzz_scratch.p;
 }
@@ -322,11 +309,7 @@ int amsm_points_fold(amsm_ctx* c, const void* d_l, const void* d_r, size_t n, co
   u32 canon[8];
   canonical_scalar(c->curve, x_mont, canon);
   u32* scratch = fold_scratch(c, n);
-  if (c->curve == AMSM_PALLAS)
-    launch_points_fold<PallasFq>(c->stream, (const u32*)d_l, (const u32*)d_r, (u32)n, canon, nbits, (u32*)d_out, true, scratch);
-  else
-    launch_points_fold<Bls12381Fq>(c->stream, (const u32*)d_l, (const u32*)d_r, (u32)n, canon, nbits, (u32*)d_out, true,
-                                   scratch);
+  DISPATCH_DO(c, launch_points_fold<Fq>(c->stream, (const u32*)d_l, (const u32*)d_r, (u32)n, canon, nbits, (u32*)d_out, true, scratch));
   HIP_TRY(hipGetLastError());
   return AMSM_OK;
 }
@@ -338,9 +321,9 @@ int amsm_bases_fold(amsm_ctx* c, const amsm_bases* key, size_t n_half, const uin
     return AMSM_E_INVALID_ARG;
   if (key_sharded(key)) return AMSM_E_UNSUPPORTED;
   if (c->host_only) {
-    amsm_bases* hb = c->curve == AMSM_PALLAS ? cpu::bases_new<PallasFq>(c, n_half) : cpu::bases_new<Bls12381Fq>(c, n_half);
+    amsm_bases* hb = DISPATCH(c, cpu::bases_new<Fq>(c, n_half));
     if (!hb) return AMSM_E_OOM;
-    const size_t hpb = (c->curve == AMSM_PALLAS) ? affine_bytes<PallasFq>() : affine_bytes<Bls12381Fq>();
+    const size_t hpb = DISPATCH(c, affine_bytes<Fq>());
     int rc = CPU_CALL(c, points_fold, key->d_table, (const char*)key->d_table + n_half * hpb, n_half, x_mont, nbits, hb->d_table);
     if (rc != AMSM_OK) {
       amsm_bases_free(hb);
@@ -350,7 +333,7 @@ int amsm_bases_fold(amsm_ctx* c, const amsm_bases* key, size_t n_half, const uin
     return AMSM_OK;
   }
   TRY(bind_device(c));
-  size_t pb = (c->curve == AMSM_PALLAS) ? affine_bytes<PallasFq>() : affine_bytes<Bls12381Fq>();
+  size_t pb = DISPATCH(c, affine_bytes<Fq>());
   amsm_bases* b = new (std::nothrow) amsm_bases();
   if (!b) return AMSM_E_OOM;
   b->curve = c->curve;
@@ -371,18 +354,10 @@ int amsm_bases_fold(amsm_ctx* c, const amsm_bases* key, size_t n_half, const uin
   bool done = false;
   if (key->precomp && key->W > 1 && key->n < (1ull << 31)) {
     const u32 levels = (u32)(key->top_shift ? key->W - 1 : key->W);
-    if (c->curve == AMSM_PALLAS)
-      done = launch_points_fold_tab<PallasFq>(c->stream, l, (u32)key->n, (u32)key->c, (u32)key->W, (u32)key->n_narrow, levels,
-                                              (u32)n_half, canon, nbits, b->d_table, scratch);
-    else
-      done = launch_points_fold_tab<Bls12381Fq>(c->stream, l, (u32)key->n, (u32)key->c, (u32)key->W, (u32)key->n_narrow, levels,
-                                                (u32)n_half, canon, nbits, b->d_table, scratch);
+    done = DISPATCH(c, launch_points_fold_tab<Fq>(c->stream, l, (u32)key->n, (u32)key->c, (u32)key->W, (u32)key->n_narrow, levels,
+                                                  (u32)n_half, canon, nbits, b->d_table, scratch));
   }
-  if (done) {
-  } else if (c->curve == AMSM_PALLAS)
-    launch_points_fold<PallasFq>(c->stream, l, r, (u32)n_half, canon, nbits, b->d_table, false, scratch);
-  else
-    launch_points_fold<Bls12381Fq>(c->stream, l, r, (u32)n_half, canon, nbits, b->d_table, false, scratch);
+  if (!done) DISPATCH_DO(c, launch_points_fold<Fq>(c->stream, l, r, (u32)n_half, canon, nbits, b->d_table, false, scratch));
   if (hipGetLastError() != hipSuccess || hipEventCreateWithFlags(&b->ready, hipEventDisableTiming) != hipSuccess ||
       hipEventRecord(b->ready, c->stream) != hipSuccess) {
     (void)hipGetLastError();
@@ -405,30 +380,19 @@ int amsm_vec_inner_product(amsm_ctx* c, const void* d_a, const void* d_b, size_t
   Slot* sl = &c->slot[0];
   TRY(ensure(sl->red_out, (size_t)blocks * 32 + 4096));
   TRY(ensure_pinned(sl, (size_t)blocks * 32));
-  if (c->curve == AMSM_PALLAS)
-    launch_vec_inner_product<PallasFr>(c->stream, (const u32*)d_a, (const u32*)d_b, (u32)n, blocks, (u32*)sl->red_out.p);
-  else
-    launch_vec_inner_product<Bls12381Fr>(c->stream, (const u32*)d_a, (const u32*)d_b, (u32)n, blocks,
-                                         (u32*)sl->red_out.p);
+  DISPATCH_DO(c, launch_vec_inner_product<Fr>(c->stream, (const u32*)d_a, (const u32*)d_b, (u32)n, blocks, (u32*)sl->red_out.p));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(sl->h_pinned, sl->red_out.p, (size_t)blocks * 32, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   const u64* h = (const u64*)sl->h_pinned;
-  if (c->curve == AMSM_PALLAS) {
-    host::HFe<PallasFr> acc = host::h_zero<PallasFr>(), t;
+  DISPATCH_DO(c, {
+    host::HFe<Fr> acc = host::h_zero<Fr>(), t;
     for (u32 i = 0; i < blocks; i++) {
       memcpy(t.v, h + 4 * i, 32);
-      acc = host::h_add<PallasFr>(acc, t);
+      acc = host::h_add<Fr>(acc, t);
     }
     memcpy(out_mont, acc.v, 32);
-  } else {
-    host::HFe<Bls12381Fr> acc = host::h_zero<Bls12381Fr>(), t;
-    for (u32 i = 0; i < blocks; i++) {
-      memcpy(t.v, h + 4 * i, 32);
-      acc = host::h_add<Bls12381Fr>(acc, t);
-    }
-    memcpy(out_mont, acc.v, 32);
-  }
+  });
   return AMSM_OK;
 }
 
@@ -439,8 +403,7 @@ int amsm_vec_powers(amsm_ctx* c, const uint64_t* point_mont, size_t n, void* d_o
   if (!n) return AMSM_OK;
   u32 pt[8];
   memcpy(pt, point_mont, 32);
-  if (c->curve == AMSM_PALLAS) launch_vec_powers<PallasFr>(c->stream, pt, (u32)n, (u32*)d_out);
-  else launch_vec_powers<Bls12381Fr>(c->stream, pt, (u32)n, (u32*)d_out);
+  DISPATCH_DO(c, launch_vec_powers<Fr>(c->stream, pt, (u32)n, (u32*)d_out));
   HIP_TRY(hipGetLastError());
   return AMSM_OK;
 }
@@ -457,15 +420,13 @@ int amsm_ipa_jump_fold(amsm_ctx* c, const amsm_bases* key, size_t log_key, const
   if (key_sharded(key)) return AMSM_E_UNSUPPORTED;  // (a fold pairs generators of different shards)
   if (c->host_only) return CPU_CALL(c, ipa_jump_fold, key, log_key, xi_mont, j, out_xy, out_inf);
   TRY(bind_device(c));
-  return DISPATCH(c, (ipa_jump_fold_impl<PallasFq, PallasFr>(c, key, log_key, xi_mont, j, out_xy, out_inf)),
-                  (ipa_jump_fold_impl<Bls12381Fq, Bls12381Fr>(c, key, log_key, xi_mont, j, out_xy, out_inf)));
+  return DISPATCH(c, ipa_jump_fold_impl<Fq, Fr>(c, key, log_key, xi_mont, j, out_xy, out_inf));
 }
 int amsm_ipa_check_poly_coeffs(amsm_ctx* c, const uint64_t* xi_mont, size_t k, void* d_out) {
   if (!c || !d_out || (k && !xi_mont) || k > 30) return AMSM_E_INVALID_ARG;
   if (c->host_only) return CPU_CALL(c, check_poly_coeffs, xi_mont, k, d_out);
   TRY(bind_device(c));
-  if (c->curve == AMSM_PALLAS) launch_check_poly_coeffs<PallasFr>(c->stream, (const u32*)xi_mont, (u32)k, (u32*)d_out);
-  else launch_check_poly_coeffs<Bls12381Fr>(c->stream, (const u32*)xi_mont, (u32)k, (u32*)d_out);
+  DISPATCH_DO(c, launch_check_poly_coeffs<Fr>(c->stream, (const u32*)xi_mont, (u32)k, (u32*)d_out));
   HIP_TRY(hipGetLastError());
   return AMSM_OK;
 }
@@ -476,12 +437,8 @@ int amsm_ipa_round_scalars(amsm_ctx* c, const uint64_t* xi_mont, size_t j, size_
     return AMSM_E_INVALID_ARG;
   if (c->host_only) return CPU_CALL(c, ipa_round_scalars, xi_mont, j, log_n, d_coeffs, d_out_l, d_out_r);
   TRY(bind_device(c));
-  if (c->curve == AMSM_PALLAS)
-    launch_ipa_round_scalars<PallasFr>(c->stream, (const u32*)xi_mont, (u32)j, (u32)log_n, (const u32*)d_coeffs,
-                                       (u32*)d_out_l, (u32*)d_out_r);
-  else
-    launch_ipa_round_scalars<Bls12381Fr>(c->stream, (const u32*)xi_mont, (u32)j, (u32)log_n, (const u32*)d_coeffs,
-                                         (u32*)d_out_l, (u32*)d_out_r);
+  DISPATCH_DO(c, launch_ipa_round_scalars<Fr>(c->stream, (const u32*)xi_mont, (u32)j, (u32)log_n, (const u32*)d_coeffs,
+                                       (u32*)d_out_l, (u32*)d_out_r));
   HIP_TRY(hipGetLastError());
   return AMSM_OK;
 }
@@ -497,14 +454,10 @@ int amsm_ipa_round(amsm_ctx* c, const amsm_bases* key, const uint64_t* xi_mont, 
   TRY(bind_device(c));
   const size_t half = (size_t)1 << (log_key - j - 1);
   if (key_sharded(key))
-    return DISPATCH(c, (ipa_round_sharded_impl<PallasFq, PallasFr>(c, key, xi_mont, j, log_key, d_coeffs, d_z, half, d_u, out_lr_xy, out_lr_inf,
-                                                                    out_ip_mont, nullptr, nullptr)),
-                    (ipa_round_sharded_impl<Bls12381Fq, Bls12381Fr>(c, key, xi_mont, j, log_key, d_coeffs, d_z, half, d_u, out_lr_xy,
-                                                                    out_lr_inf, out_ip_mont, nullptr, nullptr)));
-  return DISPATCH(c, (ipa_round_impl<PallasFq, PallasFr>(c, key, xi_mont, j, log_key, d_coeffs, d_z, half, d_u, out_lr_xy, out_lr_inf,
-                                                          out_ip_mont)),
-                  (ipa_round_impl<Bls12381Fq, Bls12381Fr>(c, key, xi_mont, j, log_key, d_coeffs, d_z, half, d_u, out_lr_xy,
-                                                          out_lr_inf, out_ip_mont)));
+    return DISPATCH(c, ipa_round_sharded_impl<Fq, Fr>(c, key, xi_mont, j, log_key, d_coeffs, d_z, half, d_u, out_lr_xy, out_lr_inf,
+                                                                    out_ip_mont, nullptr, nullptr));
+  return DISPATCH(c, ipa_round_impl<Fq, Fr>(c, key, xi_mont, j, log_key, d_coeffs, d_z, half, d_u, out_lr_xy, out_lr_inf,
+                                                          out_ip_mont));
 }
 
 int amsm_ipa_round_fused(amsm_ctx* c, const amsm_bases* key, const uint64_t* xi_mont, size_t j, size_t log_key, void* d_coeffs,
@@ -524,14 +477,10 @@ int amsm_ipa_round_fused(amsm_ctx* c, const amsm_bases* key, const uint64_t* xi_
   TRY(bind_device(c));
   const size_t half = (size_t)1 << (log_key - j - 1);
   if (key_sharded(key))
-    return DISPATCH(c, (ipa_round_sharded_impl<PallasFq, PallasFr>(c, key, xi_mont, j, log_key, d_coeffs, d_z, half, d_u, out_lr_xy, out_lr_inf,
-                                                                    out_ip_mont, fold_x_mont, h_prime_xy)),
-                    (ipa_round_sharded_impl<Bls12381Fq, Bls12381Fr>(c, key, xi_mont, j, log_key, d_coeffs, d_z, half, d_u, out_lr_xy,
-                                                                    out_lr_inf, out_ip_mont, fold_x_mont, h_prime_xy)));
-  return DISPATCH(c, (ipa_round_impl<PallasFq, PallasFr>(c, key, xi_mont, j, log_key, d_coeffs, d_z, half, d_u, out_lr_xy, out_lr_inf,
-                                                          out_ip_mont, fold_x_mont, h_prime_xy)),
-                  (ipa_round_impl<Bls12381Fq, Bls12381Fr>(c, key, xi_mont, j, log_key, d_coeffs, d_z, half, d_u, out_lr_xy,
-                                                          out_lr_inf, out_ip_mont, fold_x_mont, h_prime_xy)));
+    return DISPATCH(c, ipa_round_sharded_impl<Fq, Fr>(c, key, xi_mont, j, log_key, d_coeffs, d_z, half, d_u, out_lr_xy, out_lr_inf,
+                                                                    out_ip_mont, fold_x_mont, h_prime_xy));
+  return DISPATCH(c, ipa_round_impl<Fq, Fr>(c, key, xi_mont, j, log_key, d_coeffs, d_z, half, d_u, out_lr_xy, out_lr_inf,
+                                                          out_ip_mont, fold_x_mont, h_prime_xy));
 }
 
 int amsm_matrix_load(amsm_ctx* c, const uint32_t* row_ptr, const uint32_t* col_idx, const uint64_t* vals, size_t n_rows,
@@ -604,12 +553,8 @@ int amsm_matrix_vec_mul(amsm_ctx* c, const amsm_matrix* m, const void* d_input, 
   if (c->host_only) return CPU_CALL(c, spmv, m, d_input, n_input, d_witness, n_witness, d_out);
   TRY(bind_device(c));
   if (!m->n_rows) return AMSM_OK;
-  if (c->curve == AMSM_PALLAS)
-    launch_spmv<PallasFr>(c->stream, m->d_row_ptr, m->d_col, m->d_val, (const u32*)d_input, (u32)n_input,
-                          (const u32*)d_witness, (u32)n_witness, (u32*)d_out, (u32)m->n_rows);
-  else
-    launch_spmv<Bls12381Fr>(c->stream, m->d_row_ptr, m->d_col, m->d_val, (const u32*)d_input, (u32)n_input,
-                            (const u32*)d_witness, (u32)n_witness, (u32*)d_out, (u32)m->n_rows);
+  DISPATCH_DO(c, launch_spmv<Fr>(c->stream, m->d_row_ptr, m->d_col, m->d_val, (const u32*)d_input, (u32)n_input,
+                          (const u32*)d_witness, (u32)n_witness, (u32*)d_out, (u32)m->n_rows));
   HIP_TRY(hipGetLastError());
   return AMSM_OK;
 }
@@ -622,9 +567,6 @@ int amsm_hp_t_vecs(amsm_ctx* c, const void* const* d_a, const size_t* a_lens, co
     return CPU_CALL(c, t_vecs, d_a, a_lens, d_b, b_lens, n_inputs, mu_mont, n_mu, d_hiding_a, hiding_a_len, d_hiding_b, hiding_b_len, d_t,
                     len);
   TRY(bind_device(c));
-  return DISPATCH(c,
-                  (t_vecs_impl<PallasFr>(c, d_a, a_lens, d_b, b_lens, n_inputs, mu_mont, n_mu, d_hiding_a, hiding_a_len,
-                                         d_hiding_b, hiding_b_len, d_t, len)),
-                  (t_vecs_impl<Bls12381Fr>(c, d_a, a_lens, d_b, b_lens, n_inputs, mu_mont, n_mu, d_hiding_a,
-                                           hiding_a_len, d_hiding_b, hiding_b_len, d_t, len)));
+  return DISPATCH(c, t_vecs_impl<Fr>(c, d_a, a_lens, d_b, b_lens, n_inputs, mu_mont, n_mu, d_hiding_a, hiding_a_len,
+                                         d_hiding_b, hiding_b_len, d_t, len));
 }

@@ -89,7 +89,7 @@ const host::Glv<Fq, Fr>* host_glv() {
   static const host::Glv<Fq, Fr> g = [] {
     host::Glv<Fq, Fr> t;
     constexpr int N = host::HFe<Fq>::N;
-    std::vector<u32> g32 = generator_mont<Fq>(std::is_same<Fq, PallasFq>::value ? AMSM_PALLAS : AMSM_BLS12_381_G1);
+    std::vector<u32> g32 = generator_mont<Fq>();
     u64 gen[2 * N];
     memcpy(gen, g32.data(), sizeof(gen));
     t.setup(gen);

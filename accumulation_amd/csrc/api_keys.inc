@@ -156,8 +156,7 @@ int top_window_shift(int c, int W, int n_narrow = 0, unsigned long long* raw_max
   return raw_max == 0 ? 0 : s;
 }
 inline int top_window_shift_curve(int curve, int c, int W, int n_narrow, unsigned long long* raw_max_out) {
-  return curve == AMSM_PALLAS ? top_window_shift<PallasFr>(c, W, n_narrow, raw_max_out)
-                              : top_window_shift<Bls12381Fr>(c, W, n_narrow, raw_max_out);
+  return with_curve(curve, [&](auto cv) { return top_window_shift<typename decltype(cv)::Fr>(c, W, n_narrow, raw_max_out); });
 }
 
 template <class Fq, class Fr>
@@ -289,7 +288,7 @@ int bases_generate_impl(amsm_ctx* ctx, uint64_t seed, size_t n, unsigned flags, 
   }
   int s = AMSM_OK;
   if (n) {
-    std::vector<u32> gen = generator_mont<Fq>(ctx->curve);
+    std::vector<u32> gen = generator_mont<Fq>();
     launch_generate_bases<Fq>(ctx->stream, b->d_table, seed, (u32)first, (u32)n, gen.data());
     if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) s = AMSM_E_HIP;
     if (s == AMSM_OK) s = bases_finish<Fq, Fr>(ctx, b, flags);

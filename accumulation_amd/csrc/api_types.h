@@ -340,8 +340,10 @@ struct amsm_bases {
 
 struct amsm_sponge {  // host-side Poseidon sponge over the curve's base field (host_poseidon.h)
   int curve = 0;
-  host::PoseidonSponge<PallasFq> pallas;
-  host::PoseidonSponge<Bls12381Fq> bls;
+  // one state per base field of curves.h; only the curve's own is used (of<Fq>())
+  std::tuple<host::PoseidonSponge<PallasFq>, host::PoseidonSponge<Bls12381Fq>, host::PoseidonSponge<VestaFq>> states;
+  template <class Fq>
+  host::PoseidonSponge<Fq>& of() { return std::get<host::PoseidonSponge<Fq>>(states); }
 };
 
 struct amsm_matrix {

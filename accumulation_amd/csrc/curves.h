@@ -1,0 +1,119 @@
+// The curves the library knows, in ONE table: curve id (include/amsm.h) -> base / scalar field packs (fp.h), b of
+// y^2 = x^3 + b, the generator, and whether deserialisation checks the prime-order subgroup.  (The wrappers' own per-curve
+// numbers -- limbs, IPA fold thresholds -- are include/amsm.hpp: curve_info and accumulation_amd/ipa_pc.py: IPA_FOLD.)
+// Every entry point that takes a curve id or a context reaches its templates through with_curve(); an id that is not
+// in the table is refused there, with AMSM_E_INVALID_ARG (or the entry point's own "unknown" value).
+#pragma once
+#include <type_traits>
+#include <vector>
+
+#include "../../include/amsm.h"
+#include "host_field.h"
+
+namespace amsm {
+
+struct PallasCurve {  // ark-pallas 0.2: y^2 = x^3 + 5, cofactor 1
+  using Fq = PallasFq;
+  using Fr = PallasFr;
+  static constexpr int id = AMSM_PALLAS;
+  static constexpr int b = 5;
+  static constexpr bool subgroup_check = false;
+  static constexpr u64 gx[4] = {0x992d30ed00000000ull, 0x224698fc094cf91bull, 0, 0x4000000000000000ull};  // -1
+  static constexpr u64 gy[4] = {2, 0, 0, 0};
+};
+struct Bls12381Curve {  // ark-bls12-381 0.2 G1: y^2 = x^3 + 4, cofactor != 1
+  using Fq = Bls12381Fq;
+  using Fr = Bls12381Fr;
+  static constexpr int id = AMSM_BLS12_381_G1;
+  static constexpr int b = 4;
+  static constexpr bool subgroup_check = true;
+  static constexpr u64 gx[6] = {0xfb3af00adb22c6bbull, 0x6c55e83ff97a1aefull, 0xa14e3a3f171bac58ull,
+                                0xc3688c4f9774b905ull, 0x2695638c4fa9ac0full, 0x17f1d3a73197d794ull};
+  static constexpr u64 gy[6] = {0x0caa232946c5e7e1ull, 0xd03cc744a2888ae4ull, 0x00db18cb2c04b3edull,
+                                0xfcf5e095d5d00af6ull, 0xa09e30ed741d8ae4ull, 0x08b3f481e3aaa0f1ull};
+};
+struct VestaCurve {  // ark-vesta 0.2: y^2 = x^3 + 5, cofactor 1; Fq = Pallas Fr, Fr = Pallas Fq
+  using Fq = VestaFq;
+  using Fr = VestaFr;
+  static constexpr int id = AMSM_VESTA;
+  static constexpr int b = 5;
+  static constexpr bool subgroup_check = false;
+  static constexpr u64 gx[4] = {0x8c46eb2100000000ull, 0x224698fc0994a8ddull, 0, 0x4000000000000000ull};  // -1
+  static constexpr u64 gy[4] = {2, 0, 0, 0};
+};
+
+// base field pack -> its curve
+template <class Fq>
+struct CurveOf;
+template <>
+struct CurveOf<PallasFq> {
+  using type = PallasCurve;
+};
+template <>
+struct CurveOf<Bls12381Fq> {
+  using type = Bls12381Curve;
+};
+template <>
+struct CurveOf<VestaFq> {
+  using type = VestaCurve;
+};
+
+// f(Curve{}) for the curve with this id; `unknown` for any other id
+template <class R, class F>
+R with_curve_or(int curve, R unknown, F&& f) {
+  switch (curve) {
+    case AMSM_PALLAS: return f(PallasCurve{});
+    case AMSM_BLS12_381_G1: return f(Bls12381Curve{});
+    case AMSM_VESTA: return f(VestaCurve{});
+    default: return unknown;
+  }
+}
+template <class F>
+auto with_curve(int curve, F&& f) {
+  using R = decltype(f(PallasCurve{}));
+  return with_curve_or<R>(curve, R(AMSM_E_INVALID_ARG), f);
+}
+inline bool curve_known(int curve) {
+  return with_curve_or(curve, false, [](auto) { return true; });
+}
+inline int curve_fq_limbs(int curve) {  // u64 limbs of a base-field element in the C ABI
+  return with_curve(curve, [](auto cv) { return decltype(cv)::Fq::W / 2; });
+}
+
+// the generator of curve `curve`, affine, Montgomery form, words of the C-ABI radix (x then y); empty when Fq is not that
+// curve's base field
+template <class Fq>
+std::vector<u32> generator_mont(int curve) {
+  std::vector<u32> g;
+  with_curve(curve, [&](auto cv) {
+    using C = decltype(cv);
+    if constexpr (std::is_same<typename C::Fq, Fq>::value) {
+      using H = host::HFe<Fq>;
+      static_assert(sizeof(C::gx) == 8 * H::N, "generator limbs");
+      H gx, gy;
+      for (int i = 0; i < H::N; i++) {
+        gx.v[i] = C::gx[i];
+        gy.v[i] = C::gy[i];
+      }
+      gx = host::h_to_mont<Fq>(gx);
+      gy = host::h_to_mont<Fq>(gy);
+      g.resize(2 * Fq::L);
+      memcpy(g.data(), gx.v, 4 * Fq::L);
+      memcpy(g.data() + Fq::L, gy.v, 4 * Fq::L);
+    }
+    return AMSM_OK;
+  });
+  return g;
+}
+template <class Fq>
+std::vector<u32> generator_mont() {
+  return generator_mont<Fq>(CurveOf<Fq>::type::id);
+}
+
+}  // namespace amsm
+
+// Inside a with_curve lambda taking `cv`: the curve's Fq and Fr packs under those names.
+#define AMSM_CURVE_FIELDS(cv)              \
+  using Fq = typename decltype(cv)::Fq;    \
+  using Fr = typename decltype(cv)::Fr;    \
+  (void)cv

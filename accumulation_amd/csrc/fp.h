@@ -80,6 +80,28 @@ struct Bls12381Fr {  // scalar field of BLS12-381; 255 bits
   AMSM_TABLE(r2, 8, 0xf3f29c6du, 0xc999e990u, 0x87925c23u, 0x2b6cedcbu, 0x7254398fu, 0x05d31496u, 0x9f59ff11u, 0x0748d9d9u)
 };
 
+// Vesta (the other half of the Pasta cycle): its base field is Pallas's scalar field and its scalar field Pallas's base field.
+// Separate types with the same tables, so that code dispatching on the type (DevField, is_same) sees a third curve.
+struct VestaFq {  // base field of Vesta (= Pallas Fr); 255 bits
+  static constexpr int L = 8;  // register limbs
+  static constexpr int W = 8;  // 32-bit words in memory
+  static constexpr bool UNSAT = false;
+  static constexpr u32 INV = 0xffffffffu;
+  AMSM_TABLE(mod, 8, 0x00000001u, 0x8c46eb21u, 0x0994a8ddu, 0x224698fcu, 0x00000000u, 0x00000000u, 0x00000000u, 0x40000000u)
+  AMSM_TABLE(one, 8, 0xfffffffdu, 0x5b2b3e9cu, 0xe3420567u, 0x992c350bu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0x3fffffffu)
+  AMSM_TABLE(r2, 8, 0x0000000fu, 0xfc9678ffu, 0x891a16e3u, 0x67bb433du, 0x04ccf590u, 0x7fae2310u, 0x7ccfdaa9u, 0x096d41afu)
+};
+
+struct VestaFr {  // scalar field of Vesta (= Pallas Fq); 255 bits
+  static constexpr int L = 8;  // register limbs
+  static constexpr int W = 8;  // 32-bit words in memory
+  static constexpr bool UNSAT = false;
+  static constexpr u32 INV = 0xffffffffu;
+  AMSM_TABLE(mod, 8, 0x00000001u, 0x992d30edu, 0x094cf91bu, 0x224698fcu, 0x00000000u, 0x00000000u, 0x00000000u, 0x40000000u)
+  AMSM_TABLE(one, 8, 0xfffffffdu, 0x34786d38u, 0xe41914adu, 0x992c350bu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0x3fffffffu)
+  AMSM_TABLE(r2, 8, 0x0000000fu, 0x8c78ecb3u, 0x8b0de0e7u, 0xd7d30dbdu, 0xc3c95d18u, 0x7797a99bu, 0x7b9cb714u, 0x096d41afu)
+};
+
 // ------------------------------------------------------------------------------------------------
 // Element type and helpers
 // ------------------------------------------------------------------------------------------------
@@ -89,10 +111,10 @@ struct Fe {
 };
 
 }  // namespace amsm
-#include "fpu.h"  // unsaturated-limb packs (PallasFqU) and their u_* primitives
+#include "fpu.h"  // unsaturated-limb packs (PallasFqU, VestaFqU, Bls12381FqU) and their u_* primitives
 namespace amsm {
 
-// Field the DEVICE kernels compute in for a given ABI field: Pallas Fq runs on 9 x 29-bit unsaturated limbs
+// Field the DEVICE kernels compute in for a given ABI field: Pallas and Vesta Fq run on 9 x 29-bit unsaturated limbs
 // (internal Montgomery radix 2^261, fpu.h), BLS12-381 Fq on 14 x 28-bit limbs (radix 2^392).  (The saturated 32-bit-limb
 // schedules serve both scalar fields; for the base fields they measured 21 % / 23 % slower: DESIGN.md 4.1.)
 template <class Fq>
@@ -106,6 +128,10 @@ struct DevField<PallasFq> {
 template <>
 struct DevField<Bls12381Fq> {  // 14 x 28-bit limbs, internal radix 2^392: mixed addition 22.6 k vs 29.4 k cycles
   using type = Bls12381FqU;
+};
+template <>
+struct DevField<VestaFq> {  // the limb shape of Pallas Fq (fpu.h: VestaFqU)
+  using type = VestaFqU;
 };
 
 template <class P>
@@ -233,6 +259,16 @@ AMSM_DEV Fe<P> fe_mul_ref(const Fe<P>& a, const Fe<P>& b) {
 #pragma unroll
   for (int i = 0; i < L; i++) r.v[i] = t[i];
   fe_cond_sub<P>(r, t[L]);
+  return r;
+}
+
+// the same limbs as an element of another pack with the same modulus (fp_mul_gfx950.h: fields that share a generated schedule)
+template <class Q, class P>
+AMSM_DEV Fe<Q> fe_cast(const Fe<P>& a) {
+  static_assert(P::L == Q::L, "same limb count");
+  Fe<Q> r;
+#pragma unroll
+  for (int i = 0; i < P::L; i++) r.v[i] = a.v[i];
   return r;
 }
 

@@ -1,5 +1,5 @@
-// Unsaturated-limb Montgomery arithmetic for the base fields of the MSM hot loop (gfx950): Pallas Fq on 9 x 29 bits,
-// BLS12-381 Fq on 14 x 28 bits.
+// Unsaturated-limb Montgomery arithmetic for the base fields of the MSM hot loop (gfx950): Pallas Fq and Vesta Fq on
+// 9 x 29 bits, BLS12-381 Fq on 14 x 28 bits.
 //
 // gfx950 has no carry-in on v_mad_u64_u32 and a VALU carry write costs wait states, so the saturated 8 x 32-bit
 // schedule (fp_mul_gfx950.h) pays one v_addc per product.  Here an element is L limbs of B bits (Pallas Fq: 9 x 29,
@@ -12,7 +12,7 @@
 //   * "tight"  : limbs 0..L-2 < 2^B, value < 2^(B*L).  Everything held in registers between operations is tight.
 //   * "lazy"   : limbs < 2^(B+1), only allowed as ONE operand of a multiplication.
 //   * values are only bounded, not reduced: a multiplication gives  out < p + A*B / 2^(B*L)  and the group-law
-//     formulas in ec.h carry the bound of every intermediate in comments (cap = 2^261 ~ 128 p for Pallas).
+//     formulas in ec.h carry the bound of every intermediate in comments (cap = 2^261 ~ 128 p for Pallas and Vesta).
 //   * memory holds canonical values (< p), packed into W 32-bit words, in the INTERNAL Montgomery radix R'.  The
 //     C ABI's radix is R = 2^(32 W); fe_import / fe_export convert (one multiplication by a constant) at the
 //     edges (key load / read, the final fold of an MSM, amsm_points_fold), see DESIGN.md.
@@ -37,6 +37,21 @@ struct PallasFqU {
   AMSM_TABLE(one, 9, 0x1fffff81u, 0x14a5d367u, 0x141ad3c0u, 0x1435eec5u, 0x1ffeefefu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x003fffffu)
   AMSM_TABLE(k_import, 9, 0x1ffff001u, 0x10f30767u, 0x0ecfe231u, 0x0db0ce73u, 0x1fddbb8bu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x003fffffu)
   AMSM_TABLE(k_export, 9, 0x1ffffffdu, 0x03c369c7u, 0x06452b4du, 0x186a17c8u, 0x1ffff992u, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x003fffffu)
+};
+
+struct VestaFq;
+struct VestaFqU {  // Vesta Fq = Pallas Fr: the same shape as PallasFqU (p_0 = 1, zero limbs 5-7, top limb 2^22, R' / p = 127.99...)
+  using Sat = VestaFq;
+  static constexpr int L = 9;
+  static constexpr int W = 8;
+  static constexpr int B = 29;
+  static constexpr bool UNSAT = true;
+  static constexpr u32 NINV = 0x1fffffffu;
+  static constexpr bool CHAIN = true;  // Pallas's setting (not measured separately)
+  AMSM_TABLE(mod, 9, 0x00000001u, 0x02375908u, 0x052a3763u, 0x0d31f813u, 0x00000224u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00400000u)
+  AMSM_TABLE(one, 9, 0x1fffff81u, 0x068ad507u, 0x100e85dau, 0x1435ee7eu, 0x1ffeefefu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x003fffffu)
+  AMSM_TABLE(k_import, 9, 0x1ffff001u, 0x0ca6d907u, 0x01b40647u, 0x0db0c57eu, 0x1fddbb8bu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x003fffffu)
+  AMSM_TABLE(k_export, 9, 0x1ffffffdu, 0x1959f4e7u, 0x108159d6u, 0x186a17c6u, 0x1ffff992u, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x003fffffu)
 };
 
 struct Bls12381Fq;

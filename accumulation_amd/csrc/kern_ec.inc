@@ -1,10 +1,11 @@
-// Launcher definitions for the elliptic-curve kernels of ONE curve; included by kern_pallas.hip and
-// kern_bls12_381.hip with AMSM_FQ set to the (C-ABI) base-field parameter pack.  The kernels are instantiated
+// Launcher definitions for the elliptic-curve kernels of ONE curve; included by kern_pallas.hip,
+// kern_bls12_381.hip and kern_vesta.hip with AMSM_FQ set to the (C-ABI) base-field parameter pack.  The kernels are instantiated
 // for FQD = DevField<AMSM_FQ>::type, the field the device computes in (fp.h).
 #include <algorithm>
 #include <atomic>
 #include <vector>
 
+#include "curves.h"
 #include "host_glv.h"
 #include "launch.h"
 #include "msm_kernels.h"
@@ -206,11 +207,13 @@ void launch_precompute_level<AMSM_FQ>(hipStream_t st, u32* table, u32 stride, u3
                        (u32*)nullptr);
   }
 }
+static_assert(CurveOf<AMSM_FQ>::type::id == AMSM_CURVE_ID, "the unit's curve id is its base field's (curves.h)");
+
 // GLV set-up of this curve (host_glv.h), built on first use
 static const host::Glv<AMSM_FQ, AMSM_FR>& curve_glv() {
   static const host::Glv<AMSM_FQ, AMSM_FR> g = [] {
     host::Glv<AMSM_FQ, AMSM_FR> t;
-    std::vector<u32> gen = generator_mont<AMSM_FQ>(AMSM_CURVE_ID);
+    std::vector<u32> gen = generator_mont<AMSM_FQ>();
     std::vector<u64> g64(gen.size() / 2);
     memcpy(g64.data(), gen.data(), gen.size() * 4);
     t.setup(g64.data());

@@ -1,5 +1,5 @@
 // Scalar-field kernels (digit extraction, synthetic vectors, Hadamard / linear-combination / t-vector
-// loops) instantiated for the scalar fields of both curves, plus the curve-independent bounds kernel.
+// loops) instantiated for the scalar fields of every curve, plus the curve-independent bounds kernel.
 #include "launch.h"
 #include "vec_kernels.h"
 #include "prep_kernels.h"
@@ -497,5 +497,6 @@ void launch_tv_probe(hipStream_t st, const u32* scalars, u32 n, u32* out16, cons
 
 AMSM_FR_LAUNCHERS(PallasFr)
 AMSM_FR_LAUNCHERS(Bls12381Fr)
+AMSM_FR_LAUNCHERS(VestaFr)
 
 }  // namespace amsm

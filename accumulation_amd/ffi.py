@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("AMSM_LIB_PATH") or os.path.join(_HERE, "libamsm.so")
 
 AMSM_PALLAS = 0
 AMSM_BLS12_381_G1 = 1
+AMSM_VESTA = 2
 
 AMSM_OK = 0
 AMSM_E_INVALID_ARG = -1

@@ -9,6 +9,7 @@ from . import ffi
 MODULI = {
     ffi.AMSM_PALLAS: 0x40000000000000000000000000000000224698FC0994A8DD8C46EB2100000001,
     ffi.AMSM_BLS12_381_G1: 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
+    ffi.AMSM_VESTA: 0x40000000000000000000000000000000224698FC094CF91B992D30ED00000001,  # = Pallas's base field
 }
 _R = 1 << 256
 _M64 = (1 << 64) - 1

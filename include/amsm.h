@@ -11,7 +11,7 @@
  *
  * Data formats (identical to ark-ff 0.2 memory, so Rust slices can be passed zero-copy):
  *   - field element  : little-endian u64 limbs of x*R mod m (Montgomery form), R = 2^(64*limbs);
- *                      limbs = 4 for Pallas Fq/Fr and BLS12-381 Fr, 6 for BLS12-381 Fq.
+ *                      limbs = 4 for Pallas and Vesta Fq/Fr and BLS12-381 Fr, 6 for BLS12-381 Fq.
  *   - scalar (BigInt): 4 little-endian u64 limbs of the canonical integer in [0, r)  (`into_repr()`),
  *                      or Montgomery form when the `scalars_mont` argument is non-zero (raw `Vec<Fr>`).
  *   - affine point   : 2*limbs u64 = x_mont | y_mont, plus a separate is_inf byte (ark-ec
@@ -50,6 +50,7 @@ typedef struct amsm_bases amsm_bases;
 enum amsm_curve {
   AMSM_PALLAS = 0,       /* ark_pallas::Affine -- the only curve the reference exercises (Cargo.toml:39) */
   AMSM_BLS12_381_G1 = 1, /* BASELINE.json config 3 (384-bit base field); extension, no reference harness */
+  AMSM_VESTA = 2,        /* ark_vesta::Affine -- Pallas's partner in the Pasta cycle (Fq = Pallas Fr, Fr = Pallas Fq); extension */
 };
 
 enum amsm_status {
@@ -171,7 +172,7 @@ int amsm_ctx_pipeline_stats(const amsm_ctx* ctx, unsigned long long* n_bucket_pe
 int amsm_ctx_pipeline_stats_small(const amsm_ctx* ctx, unsigned long long* n_bucket_split, unsigned long long* n_fallbacks);
 void amsm_ctx_destroy(amsm_ctx* ctx);
 int amsm_ctx_curve(const amsm_ctx* ctx);
-/* limbs (u64) of a base-field element: 4 (Pallas) or 6 (BLS12-381). */
+/* limbs (u64) of a base-field element: 4 (Pallas, Vesta) or 6 (BLS12-381). */
 int amsm_ctx_fq_limbs(const amsm_ctx* ctx);
 /* Override the Pippenger window width c (bits); 0 restores the automatic choice. */
 int amsm_ctx_set_window(amsm_ctx* ctx, int c_bits);
@@ -417,9 +418,9 @@ int amsm_fr_from_mont(int curve, const uint64_t* a_mont, size_t n, uint64_t* out
  * src/r1cs_nark_as/data_structures.rs:105,155,217,249, src/ipa_pc_as/data_structures.rs:55,76) and prints
  * `serialized_size()` at examples/scaling-as.rs:123-131.  Host only (no context, no device).  The composite types are
  * assembled from these in include/amsm_serialize.hpp.  PARITY UNPINNED (accumulation_amd/csrc/host_serialize.h).
- *   field element : canonical integer, little-endian, 32 bytes (Fr of both curves)
+ *   field element : canonical integer, little-endian, 32 bytes (Fr of every curve)
  *   point         : compressed = x with 2 flag bits in the top of the last byte (bit 7: y is the larger root, bit 6:
- *                   infinity) -- 33 bytes (Pallas) / 48 (BLS12-381 G1); uncompressed = x | y+flags -- 65 / 96 bytes.
+ *                   infinity) -- 33 bytes (Pallas, Vesta) / 48 (BLS12-381 G1); uncompressed = x | y+flags -- 65 / 96 bytes.
  * Deserialisation returns AMSM_E_INVALID_ARG for a non-canonical integer, an x without a point, a point off the curve or
  * outside the prime-order subgroup, or both flag bits set. */
 size_t amsm_fr_serialized_size(int curve);
@@ -443,7 +444,7 @@ void amsm_poseidon_free(amsm_sponge* s);
 /* `fork(domain)`: a clone that absorbed (domain.len() as u64 LE || domain) as a byte string. */
 int amsm_poseidon_fork(const amsm_sponge* s, const uint8_t* domain, size_t n, amsm_sponge** out);
 /* absorb: native elements (base field, Montgomery); one usize / bool / Option tag; a byte string (31-byte LE chunks for
- * Pallas, 47 for BLS12-381, one element each); affine points (x, y, infinity each; a flagged identity absorbs as 0, 1, 1 whatever
+ * Pallas and Vesta, 47 for BLS12-381, one element each); affine points (x, y, infinity each; a flagged identity absorbs as 0, 1, 1 whatever
  * xy_mont holds: ark-ec ^0.2.0's `GroupAffine::zero()`). */
 int amsm_poseidon_absorb_native(amsm_sponge* s, const uint64_t* fq_mont, size_t n);
 int amsm_poseidon_absorb_u64(amsm_sponge* s, uint64_t v);

@@ -29,6 +29,23 @@ inline void check(int s, const char* where) {
   if (s != AMSM_OK) throw Error(s, where);
 }
 
+// What the wrappers need to know about a curve before they have a context for it, in one table: the u64 limbs of a base-field
+// element (0 for an id the library does not know) and the IPA opening's fold thresholds (ipa_pc_as: fold_rounds) -- the same
+// numbers as accumulation_amd/ipa_pc.py:IPA_FOLD.
+struct CurveInfo {
+  int fq_limbs;
+  int ipa_fold_min_log;  // smallest log2(d + 1) whose opening folds the key at all
+  int ipa_fold_above;    // fold while the key has more than 2^this generators
+};
+inline CurveInfo curve_info(int curve) {
+  switch (curve) {
+    case AMSM_PALLAS: return {4, 18, 15};        // measured on MI355X
+    case AMSM_BLS12_381_G1: return {6, 16, 15};  // measured on MI355X
+    case AMSM_VESTA: return {4, 18, 15};         // Pallas's (same limb shape; not measured separately)
+    default: return {0, 99, 99};
+  }
+}
+
 // Affine point in the ABI's format: x_mont | y_mont (2*limbs u64) + infinity flag.
 struct Affine {
   std::vector<uint64_t> xy;

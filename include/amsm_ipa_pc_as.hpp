@@ -187,9 +187,10 @@ struct InnerProductArgPC {
   }
 
   // Leading rounds that fold the key physically: (smallest log2(d+1) that folds at all, fold while the key has more than
-  // 2^T generators), measured on MI355X -- the same table as accumulation_amd/ipa_pc.py:IPA_FOLD.
+  // 2^T generators), from the curve table (amsm.hpp: curve_info).
   static size_t fold_rounds(int curve, size_t log_n) {
-    size_t min_log = curve == AMSM_PALLAS ? 18 : 16, t = 15;
+    const CurveInfo ci = curve_info(curve);
+    const size_t min_log = (size_t)ci.ipa_fold_min_log, t = (size_t)ci.ipa_fold_above;
     if (const char* e = getenv("AMSM_IPA_FOLD_ABOVE")) {
       int v = atoi(e);
       if (v > 0) return log_n > (size_t)v ? log_n - (size_t)v : 0;

@@ -133,7 +133,7 @@ inline void put_point(Writer& w, const Affine& p) {
   std::vector<uint64_t> zero;
   const uint64_t* xy = p.xy.data();
   if (p.xy.empty()) {  // a default-constructed identity
-    zero.assign(2 * (w.curve == AMSM_PALLAS ? 4 : 6), 0);
+    zero.assign(2 * (size_t)curve_info(w.curve).fq_limbs, 0);
     xy = zero.data();
     inf = 1;
   }
@@ -142,7 +142,7 @@ inline void put_point(Writer& w, const Affine& p) {
 inline Affine get_point(Reader& r) {
   const size_t sz = amsm_point_serialized_size(r.curve, r.compressed ? 1 : 0);
   Affine p;
-  p.xy.assign(2 * (r.curve == AMSM_PALLAS ? 4 : 6), 0);
+  p.xy.assign(2 * (size_t)curve_info(r.curve).fq_limbs, 0);
   uint8_t inf = 0;
   check(amsm_points_deserialize(r.curve, r.take(sz), 1, r.compressed ? 1 : 0, p.xy.data(), &inf), "amsm_points_deserialize");
   p.infinity = inf != 0;

@@ -27,6 +27,8 @@ field("PallasFq", 8, 0x40000000000000000000000000000000224698FC094CF91B992D30ED0
 field("PallasFr", 8, 0x40000000000000000000000000000000224698FC0994A8DD8C46EB2100000001)
 field("Bls12381Fq", 12, 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB)
 field("Bls12381Fr", 8, 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001)
+field("VestaFq", 8, 0x40000000000000000000000000000000224698FC0994A8DD8C46EB2100000001)  # = Pallas Fr
+field("VestaFr", 8, 0x40000000000000000000000000000000224698FC094CF91B992D30ED00000001)  # = Pallas Fq
 
 MAX_TERMS = 11  # terms per asm statement (operand limit 30: 2*terms + acc + c2 + 3 sgpr temps)
 
@@ -76,6 +78,24 @@ def emit_column_stmt(terms, first):
     c2c = '"=&v"' if first else '"+v"'
     outs = f'[acc] "+v"(acc), [c2] {c2c}(c2), [s0] "=&s"(s0), [s1] "=&s"(s1), [s2] "=&s"(s2)'
     return f'  asm volatile("{body}"\n               : {outs}\n               : {", ".join(ops_in)}\n               : "vcc");\n'
+
+
+def twin_of(name):
+    """an earlier field with the same modulus and limb count (Vesta's fields are Pallas's two): its schedule serves this one"""
+    for other in FIELDS:
+        if other == name:
+            return None
+        if FIELDS[other][:2] == FIELDS[name][:2]:
+            return other
+
+
+def gen_twin(name, twin):
+    return "\n".join([
+        f"// ---- {name}: the modulus of {twin}, whose schedule it runs ----",
+        "template <>",
+        f"AMSM_DEV Fe<{name}> fe_mul<{name}>(const Fe<{name}>& a, const Fe<{name}>& b) {{",
+        f"  return fe_cast<{name}>(fe_mul<{twin}>(fe_cast<{twin}>(a), fe_cast<{twin}>(b)));",
+        "}"])
 
 
 def gen_field(name, T=1):
@@ -159,7 +179,7 @@ def main():
     hdr.append("#pragma once")
     hdr.append("namespace amsm {")
     for name in FIELDS:
-        hdr.append(gen_field(name))
+        hdr.append(gen_twin(name, twin_of(name)) if twin_of(name) else gen_field(name))
         hdr.append("")
     for name in ("PallasFr", "Bls12381Fr"):  # the scalar-field vector kernels (vec_kernels.h)
         for T in (2, 3):

@@ -8,7 +8,7 @@
 // configs 4, 5) get the same treatment here.
 //
 //   profile_as <scheme: trivial_pc_as | ipa_pc_as | hp_as | r1cs_nark_as | all> <log_min> <log_max>
-//              [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] [--curve 0|1] [--constant] [--uniform] [--no-roundtrip]
+//              [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] [--curve 0|1|2] [--constant] [--uniform] [--no-roundtrip]
 //              [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold]
 //   --cold       no warm-up repetitions (the prove before the timed ones, the decide before the timed one): the CPU legs of
 //                bench.py, where a repetition costs seconds and there are no clocks or caches to warm.
@@ -460,7 +460,7 @@ int main(int argc, char** argv) {
   Opt o;
   if (argc < 4) {
     fprintf(stderr, "usage: %s <scheme|all> <log_min> <log_max> [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] "
-                    "[--curve 0|1] [--constant] [--uniform] [--no-roundtrip] [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--replicate-below L]\n", argv[0]);
+                    "[--curve 0|1|2] [--constant] [--uniform] [--no-roundtrip] [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--replicate-below L]\n", argv[0]);
     return 2;
   }
   o.scheme = argv[1];
