@@ -403,6 +403,50 @@ int vec_powers(const uint64_t* point_mont, size_t n, void* out) {
   });
   return AMSM_OK;
 }
+// x^e by square-and-multiply
+template <class Fr>
+host::HFe<Fr> fr_pow(host::HFe<Fr> base, size_t e) {
+  host::HFe<Fr> acc = host::h_one<Fr>();
+  for (; e; e >>= 1) {
+    if (e & 1) acc = host::h_mul<Fr>(acc, base);
+    base = host::h_sqr<Fr>(base);
+  }
+  return acc;
+}
+// chunk [lo, hi) of a polynomial by Horner from `acc`: r[i] = c[i] + z r[i+1]; q (may be null) receives q[i-1] = r[i], i >= 1
+template <class Fr>
+host::HFe<Fr> poly_chunk(const void* c, size_t lo, size_t hi, const host::HFe<Fr>& z, host::HFe<Fr> acc, void* q) {
+  for (size_t i = hi; i-- > lo;) {
+    acc = host::h_add<Fr>(ld<Fr>(c, i), host::h_mul<Fr>(z, acc));
+    if (q && i) st<Fr>(q, i - 1, acc);
+  }
+  return acc;
+}
+// vec_kernels.h k_poly_*: the same three passes over chunks of the host pool (chunk values, a serial recurrence over the few
+// chunks with the multipliers z^(chunk length), the chunks again from their carries); quot == null: evaluation only
+template <class Fq, class Fr>
+int poly_div_linear_batch(const void* const* coeffs, const size_t* lens, size_t n_polys, const uint64_t* z_mont, bool one_point,
+                          void* const* quot, uint64_t* rem_mont) {
+  using H = host::HFe<Fr>;
+  for (size_t k = 0; k < n_polys; k++) {
+    const size_t n = lens[k];
+    const H z = ld<Fr>(z_mont, one_point ? 0 : k);
+    void* q = quot ? quot[k] : nullptr;
+    const size_t chunks = std::max<size_t>(1, std::min<size_t>((n + 4095) / 4096, 4 * (HostPool::get().workers.size() + 1)));
+    auto bound = [&](size_t t) { return n * t / chunks; };
+    std::vector<H> val(chunks), carry(chunks + 1, host::h_zero<Fr>());
+    if (chunks > 1) {
+      HostPool::get().run(chunks, [&](size_t t) { val[t] = poly_chunk<Fr>(coeffs[k], bound(t), bound(t + 1), z, host::h_zero<Fr>(), nullptr); });
+      for (size_t t = chunks; t-- > 0;)  // carry[t] = r[bound(t)]
+        carry[t] = host::h_add<Fr>(val[t], host::h_mul<Fr>(fr_pow<Fr>(z, bound(t + 1) - bound(t)), carry[t + 1]));
+      if (q) HostPool::get().run(chunks, [&](size_t t) { (void)poly_chunk<Fr>(coeffs[k], bound(t), bound(t + 1), z, carry[t + 1], q); });
+    } else {
+      carry[0] = poly_chunk<Fr>(coeffs[k], 0, n, z, host::h_zero<Fr>(), q);
+    }
+    if (rem_mont) memcpy(rem_mont + 4 * k, carry[0].v, 32);
+  }
+  return AMSM_OK;
+}
 // coefficient p of prod_{i=1..k} (1 + xi_i X^(2^(k-i))) = product of the xi_i whose bit (k - i) is set in p
 template <class Fq, class Fr>
 int check_poly_coeffs(const uint64_t* xi, size_t k, void* out) {

@@ -408,6 +408,38 @@ int amsm_vec_powers(amsm_ctx* c, const uint64_t* point_mont, size_t n, void* d_o
   return AMSM_OK;
 }
 
+static bool poly_args_ok(const void* const* d_coeffs, const size_t* lens, size_t n_polys, void* const* d_quot, bool div) {
+  if (!n_polys) return true;
+  if (!d_coeffs || !lens || (div && !d_quot)) return false;
+  for (size_t k = 0; k < n_polys; k++) {
+    if (lens[k] >= (1ull << 32) || (lens[k] && !d_coeffs[k])) return false;
+    if (div && lens[k] > 1 && !d_quot[k]) return false;
+  }
+  return true;
+}
+int amsm_poly_evaluate_batch(amsm_ctx* c, const void* const* d_coeffs, const size_t* lens, size_t n_polys, const uint64_t* point_mont,
+                             uint64_t* out_mont) {
+  if (!c || (n_polys && (!point_mont || !out_mont)) || !poly_args_ok(d_coeffs, lens, n_polys, nullptr, false)) return AMSM_E_INVALID_ARG;
+  if (c->host_only) return CPU_CALL(c, poly_div_linear_batch, d_coeffs, lens, n_polys, point_mont, true, nullptr, out_mont);
+  TRY(bind_device(c));
+  if (!n_polys) return AMSM_OK;
+  return DISPATCH(c, poly_impl<Fr>(c, d_coeffs, lens, n_polys, point_mont, true, nullptr, out_mont));
+}
+int amsm_poly_evaluate(amsm_ctx* c, const void* d_coeffs, size_t n, const uint64_t* point_mont, uint64_t* out_mont) {
+  return amsm_poly_evaluate_batch(c, &d_coeffs, &n, 1, point_mont, out_mont);
+}
+int amsm_poly_div_linear_batch(amsm_ctx* c, const void* const* d_coeffs, const size_t* lens, size_t n_polys, const uint64_t* z_mont,
+                               void* const* d_quot, uint64_t* rem_mont) {
+  if (!c || (n_polys && !z_mont) || !poly_args_ok(d_coeffs, lens, n_polys, d_quot, true)) return AMSM_E_INVALID_ARG;
+  if (c->host_only) return CPU_CALL(c, poly_div_linear_batch, d_coeffs, lens, n_polys, z_mont, false, d_quot, rem_mont);
+  TRY(bind_device(c));
+  if (!n_polys) return AMSM_OK;
+  return DISPATCH(c, poly_impl<Fr>(c, d_coeffs, lens, n_polys, z_mont, false, d_quot, rem_mont));
+}
+int amsm_poly_div_linear(amsm_ctx* c, const void* d_coeffs, size_t n, const uint64_t* z_mont, void* d_quot, uint64_t* rem_mont) {
+  return amsm_poly_div_linear_batch(c, &d_coeffs, &n, 1, z_mont, &d_quot, rem_mont);
+}
+
 int amsm_ipa_jump_fold(amsm_ctx* c, const amsm_bases* key, size_t log_key, const uint64_t* xi_mont, size_t j, uint64_t* out_xy,
                        uint8_t* out_inf) {
   if (!c || !key || !out_xy || (j && !xi_mont) || log_key == 0 || log_key > 30 || j > log_key || !key_matches(c, key)) return AMSM_E_INVALID_ARG;

@@ -232,6 +232,97 @@ int vec_combine_impl(amsm_ctx* ctx, const void* const* d_vecs, const size_t* len
   return AMSM_OK;
 }
 
+// the point and the scan multipliers (z^POLY_E)^(2^k) of one polynomial; returns z^POLY_T
+template <class Fr>
+host::HFe<Fr> poly_powers(const host::HFe<Fr>& z, u32 z_out[8], u32 pw[8][8]) {
+  host::HFe<Fr> x = z;
+  memcpy(z_out, x.v, 32);
+  for (u32 i = 0; i < POLY_LOG_E; i++) x = host::h_sqr<Fr>(x);
+  for (int k = 0; k < 8; k++) {
+    memcpy(pw[k], x.v, 32);
+    x = host::h_sqr<Fr>(x);
+  }
+  return x;
+}
+// amsm_poly_evaluate_batch (d_quot == null; out_mont = the values) and amsm_poly_div_linear_batch (out_mont = the remainders, may be
+// null: then nothing is waited for).  Workspace in slot 0's red_out: tile values | carries | remainders.
+template <class Fr>
+int poly_impl(amsm_ctx* ctx, const void* const* d_coeffs, const size_t* lens, size_t n_polys, const uint64_t* z_mont, bool one_point,
+              void* const* d_quot, uint64_t* out_mont) {
+  using H = host::HFe<Fr>;
+  const bool eval = d_quot == nullptr;
+  std::vector<u32> off(n_polys), nt(n_polys);
+  size_t total = 0;
+  for (size_t k = 0; k < n_polys; k++) {
+    nt[k] = (u32)((lens[k] + POLY_T - 1) / POLY_T);
+    off[k] = (u32)total;
+    total += nt[k];
+  }
+  if (total >= (1ull << 32)) return AMSM_E_INVALID_ARG;
+  if (out_mont) memset(out_mont, 0, n_polys * 32);
+  if (!total) return AMSM_OK;
+  Slot* sl = &ctx->slot[0];
+  TRY(ensure(sl->red_out, (2 * total + n_polys) * 32 + 4096));
+  if (out_mont) TRY(ensure_pinned(sl, (eval ? total : n_polys) * 32));
+  u32* d_h = (u32*)sl->red_out.p;
+  u32* d_carry = d_h + total * 8;
+  u32* d_rem = d_carry + total * 8;
+  if (!eval && out_mont) HIP_TRY(hipMemsetAsync(d_rem, 0, n_polys * 32, ctx->stream));
+  for (size_t first = 0; first < n_polys; first += POLY_MAX) {
+    const u32 m = (u32)std::min<size_t>(POLY_MAX, n_polys - first);
+    PolyArgs a, b;
+    memset(&a, 0, sizeof(a));
+    memset(&b, 0, sizeof(b));
+    u32 max_t = 0;
+    for (u32 j = 0; j < m; j++) {
+      const size_t k = first + j;
+      H z;
+      memcpy(z.v, z_mont + (one_point ? 0 : 4 * k), 32);
+      a.c[j] = (const u32*)d_coeffs[k];
+      a.q[j] = eval ? nullptr : (u32*)d_quot[k];
+      a.len[j] = (u32)lens[k];
+      a.off[j] = off[k];
+      const H zt = poly_powers<Fr>(z, a.z[j], a.pw[j]);
+      memcpy(a.zt, zt.v, 32);  // (read by the evaluation only: one point for all)
+      b.c[j] = d_h + (size_t)off[k] * 8;
+      b.q[j] = d_carry + (size_t)off[k] * 8;
+      b.len[j] = nt[k];
+      (void)poly_powers<Fr>(zt, b.z[j], b.pw[j]);
+      max_t = std::max(max_t, nt[k]);
+    }
+    if (!max_t) continue;
+    if (eval) {
+      launch_poly_tile_values<Fr>(ctx->stream, a, m, max_t, true, d_h);
+    } else {
+      a.rem = out_mont ? d_rem + first * 8 : nullptr;
+      if (max_t > 1) {  // (the grid covers the one-tile polynomials of a mixed batch too: their value is written and never read)
+        launch_poly_tile_values<Fr>(ctx->stream, a, m, max_t, false, d_h);
+        launch_poly_carries<Fr>(ctx->stream, b, m);
+      }
+      launch_poly_div_tiles<Fr>(ctx->stream, a, m, max_t, d_carry);
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  if (!out_mont) return AMSM_OK;
+  const size_t n_back = eval ? total : n_polys;
+  HIP_TRY(hipMemcpyAsync(sl->h_pinned, eval ? d_h : d_rem, n_back * 32, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const u64* h = (const u64*)sl->h_pinned;
+  if (!eval) {
+    memcpy(out_mont, h, n_polys * 32);
+    return AMSM_OK;
+  }
+  for (size_t k = 0; k < n_polys; k++) {
+    H acc = host::h_zero<Fr>(), t;
+    for (u32 i = 0; i < nt[k]; i++) {
+      memcpy(t.v, h + 4 * ((size_t)off[k] + i), 32);
+      acc = host::h_add<Fr>(acc, t);
+    }
+    memcpy(out_mont + 4 * k, acc.v, 32);
+  }
+  return AMSM_OK;
+}
+
 template <class Fr>
 int t_vecs_blocked(amsm_ctx* ctx, const void* const* d_a, const size_t* a_lens, const void* const* d_b, const size_t* b_lens,
                    size_t n_in, const uint64_t* mu, size_t n_mu, const void* d_ha, size_t ha_len, const void* d_hb,

@@ -439,6 +439,19 @@ void launch_tv_probe(hipStream_t st, const u32* scalars, u32 n, u32* out16, cons
     hipLaunchKernelGGL((k_vec_powers<FR>), dim3(cdiv_(n, 256)), dim3(256), 0, st, a, out);                           \
   }                                                                                                                  \
   template <>                                                                                                        \
+  void launch_poly_tile_values<FR>(hipStream_t st, const PolyArgs& a, u32 n_polys, u32 max_tiles, bool eval, u32* out) { \
+    if (eval) hipLaunchKernelGGL((k_poly_tile_values<FR, true>), dim3(max_tiles, n_polys), dim3(256), 0, st, a, out); \
+    else hipLaunchKernelGGL((k_poly_tile_values<FR, false>), dim3(max_tiles, n_polys), dim3(256), 0, st, a, out);    \
+  }                                                                                                                  \
+  template <>                                                                                                        \
+  void launch_poly_carries<FR>(hipStream_t st, const PolyArgs& a, u32 n_polys) {                                     \
+    hipLaunchKernelGGL((k_poly_carries<FR>), dim3(1, n_polys), dim3(256), 0, st, a);                                 \
+  }                                                                                                                  \
+  template <>                                                                                                        \
+  void launch_poly_div_tiles<FR>(hipStream_t st, const PolyArgs& a, u32 n_polys, u32 max_tiles, const u32* carries) { \
+    hipLaunchKernelGGL((k_poly_div_tiles<FR>), dim3(max_tiles, n_polys), dim3(256), 0, st, a, carries);              \
+  }                                                                                                                  \
+  template <>                                                                                                        \
   void launch_vec_inner_product<FR>(hipStream_t st, const u32* a, const u32* b, u32 n, u32 blocks, u32* out) {       \
     hipLaunchKernelGGL((k_vec_inner_product<FR>), dim3(blocks), dim3(256), 0, st, a, b, n, out);                     \
   }                                                                                                                  \

@@ -176,6 +176,15 @@ void launch_spmv(hipStream_t st, const u32* row_ptr, const u32* col, const u32* 
 
 template <class Fr>
 void launch_vec_powers(hipStream_t st, const u32 point_mont[8], u32 n, u32* out);
+// Polynomial division by (X - z) / evaluation over up to POLY_MAX polynomials (vec_kernels.h: k_poly_*; grid.y = polynomial).
+// tile_values: out[a.off[k] + b] = value of tile b (eval: times point^(b POLY_T)); carries: `a` describes the polynomials of tile
+// values; div_tiles: the quotients (and a.rem) from the carries.
+template <class Fr>
+void launch_poly_tile_values(hipStream_t st, const PolyArgs& a, u32 n_polys, u32 max_tiles, bool eval, u32* out);
+template <class Fr>
+void launch_poly_carries(hipStream_t st, const PolyArgs& a, u32 n_polys);
+template <class Fr>
+void launch_poly_div_tiles(hipStream_t st, const PolyArgs& a, u32 n_polys, u32 max_tiles, const u32* carries);
 template <class Fr>
 void launch_vec_inner_product(hipStream_t st, const u32* a, const u32* b, u32 n, u32 blocks, u32* out);
 template <class Fr>

@@ -124,6 +124,21 @@ struct CombineArgs {
   u32 n;
 };
 
+// Batched polynomial division by (X - z) / evaluation (vec_kernels.h: k_poly_*).  A workgroup owns a tile of POLY_T
+// consecutive coefficients, each of its 256 lanes a run of POLY_E; up to POLY_MAX polynomials per launch (blockIdx.y).
+constexpr int POLY_MAX = 8;
+constexpr u32 POLY_LOG_E = 2, POLY_E = 1u << POLY_LOG_E, POLY_T = 256u * POLY_E;
+struct PolyArgs {
+  const u32* c[POLY_MAX];  // coefficients, little-endian in the degree
+  u32* q[POLY_MAX];        // quotient (len - 1 elements); unused by the evaluation
+  u32 len[POLY_MAX];
+  u32 off[POLY_MAX];       // first tile of polynomial k in the per-tile workspace
+  u32 z[POLY_MAX][8];      // the point (Montgomery)
+  u32 pw[POLY_MAX][8][8];  // (z^POLY_E)^(2^k), k < 8: the multipliers of the scan over the lanes' runs
+  u32 zt[8];               // evaluation: point^POLY_T
+  u32* rem;                // POLY_MAX elements, p_k(z_k) (may be null)
+};
+
 struct TVecArgs {
   const u32* a[HP_MAX_INPUTS];
   const u32* b[HP_MAX_INPUTS];

@@ -345,6 +345,138 @@ __global__ void __launch_bounds__(256)
   if (threadIdx.x == 0) fe_store<Fr>(out + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8, fe_load<Fr>(lds));
 }
 
+// ---- polynomial division by (X - z) and evaluation: the witness polynomial (p(X) - v) / (X - z) of
+// src/trivial_pc_as/mod.rs:198-202 and the `evaluate` calls at :402-403, :441 ------------------------------------
+// With r[i] = c[i] + z r[i+1] (r[n] = 0) the quotient is q[i-1] = r[i] and r[0] = p(z): an inclusive suffix scan whose
+// combine step is one multiplication by a power of z and one addition.  Reduce-then-scan over tiles of POLY_T coefficients in
+// separate launches (no workgroup waits for another):
+//   k_poly_tile_values : tile b's local value h_b = sum_j c[lo_b + j] z^j   (evaluation: times x^(b T), summed on the host)
+//   k_poly_carries     : one workgroup per polynomial runs the same recurrence over the h_b with multiplier z^T, from the top
+//                        tile down: carry[b] = r[lo_b + T], what enters tile b from above
+//   k_poly_div_tiles   : each tile redoes its scan from its carry and writes q (tile 0 also p(z))
+// Inside a tile lane position p owns the run [lo + p E, lo + (p + 1) E): Horner inside the run, then a Hillis-Steele suffix scan
+// over the 256 run values with the multipliers (z^E)^(2^k).  Position p sits on lane p / 4 of wave p % 4, so that the steps of
+// distance 4 .. 128 are __shfl_down by 1 .. 32 inside a wave and only the distances 1 and 2 go through LDS.
+template <class Fr>
+AMSM_DEV Fe<Fr> fe_from_arg(const u32 w[8]) {
+  Fe<Fr> x;
+#pragma unroll
+  for (int k = 0; k < 8; k++) x.v[k] = w[k];
+  return x;
+}
+AMSM_DEV u32 poly_pos() { return (threadIdx.x & 63u) * 4u + (threadIdx.x >> 6); }
+
+// r[e] = sum_{j >= i} c[j] z^(j - i) + z^(lo + T - i) carry for i = lo + p E + e: the suffix values of this lane's run.
+// `scan` = false: only the tile's value, returned in r[0] of position 0 (the other lanes' r is their run alone).
+// lds: 256 elements.  Every lane of the workgroup must call (barriers inside).
+template <class Fr>
+AMSM_DEV void poly_tile_suffix(const u32* __restrict__ c, u32 n, u32 lo, const Fe<Fr>& carry, const PolyArgs& a, u32 k, bool scan,
+                               u32* lds, Fe<Fr> r[POLY_E]) {
+  const u32 p = poly_pos(), lane = threadIdx.x & 63u;
+  const u64 i0 = (u64)lo + (u64)p * POLY_E;
+  const Fe<Fr> z = fe_from_arg<Fr>(a.z[k]);
+  Fe<Fr> x[POLY_E];
+#pragma unroll
+  for (u32 e = 0; e < POLY_E; e++) x[e] = i0 + e < n ? fe_load<Fr>(c + (size_t)(i0 + e) * 8) : fe_zero<Fr>();
+  Fe<Fr> acc = p == 255u ? carry : fe_zero<Fr>();
+#pragma unroll
+  for (int e = POLY_E - 1; e >= 0; e--) acc = fe_add<Fr>(x[e], fe_mul<Fr>(z, acc));
+  // S_p = sum_{u >= p} v_u m^(u - p), m = z^E
+#pragma unroll 1
+  for (u32 s = 0; s < 2; s++) {
+    fe_store<Fr>(lds + p * 8, acc);
+    __syncthreads();
+    if (p + (1u << s) < 256u) acc = fe_add<Fr>(acc, fe_mul<Fr>(fe_from_arg<Fr>(a.pw[k][s]), fe_load<Fr>(lds + (p + (1u << s)) * 8)));
+    __syncthreads();
+  }
+#pragma unroll 1
+  for (u32 s = 2; s < 8; s++) {
+    const u32 d = 1u << (s - 2);
+    Fe<Fr> y;
+#pragma unroll
+    for (int w = 0; w < 8; w++) y.v[w] = (u32)__shfl_down((int)acc.v[w], d, 64);
+    y = fe_add<Fr>(acc, fe_mul<Fr>(fe_from_arg<Fr>(a.pw[k][s]), y));
+    if (lane + d < 64u) acc = y;
+  }
+  r[0] = acc;
+  if (!scan) return;
+  // what enters this run from above is S_(p+1); Horner again from there
+  fe_store<Fr>(lds + p * 8, acc);
+  __syncthreads();
+  acc = p == 255u ? carry : fe_load<Fr>(lds + (p + 1u) * 8);
+  __syncthreads();
+#pragma unroll
+  for (int e = POLY_E - 1; e >= 0; e--) {
+    acc = fe_add<Fr>(x[e], fe_mul<Fr>(z, acc));
+    r[e] = acc;
+  }
+}
+
+// r[e] belongs to index i = lo + p E + e: q[i - 1] = r[i], r[0] is the remainder
+template <class Fr>
+AMSM_DEV void poly_store_quotient(const Fe<Fr> r[POLY_E], u32 n, u32 lo, u32* __restrict__ q, u32* __restrict__ rem) {
+  const u64 i0 = (u64)lo + (u64)poly_pos() * POLY_E;
+#pragma unroll
+  for (u32 e = 0; e < POLY_E; e++) {
+    const u64 i = i0 + e;
+    if (i >= n) continue;
+    if (i) fe_store<Fr>(q + (size_t)(i - 1) * 8, r[e]);
+    else if (rem) fe_store<Fr>(rem, r[e]);
+  }
+}
+
+// out[off_k + b] = h_b (EVAL: h_b x^(b T), x^T in a.zt); grid (max tiles, polynomials)
+template <class Fr, bool EVAL>
+__global__ void __launch_bounds__(256) k_poly_tile_values(PolyArgs a, u32* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) u32 lds[256 * 8];
+  const u32 k = blockIdx.y, n = a.len[k], b = blockIdx.x;
+  if ((u64)b * POLY_T >= n) return;  // (uniform over the workgroup)
+  Fe<Fr> r[POLY_E];
+  poly_tile_suffix<Fr>(a.c[k], n, b * POLY_T, fe_zero<Fr>(), a, k, false, lds, r);
+  if (threadIdx.x != 0) return;
+  Fe<Fr> h = r[0];
+  if (EVAL) {
+    Fe<Fr> base = fe_from_arg<Fr>(a.zt), acc = fe_one<Fr>();
+    for (u32 e = b; e != 0; e >>= 1) {
+      if (e & 1u) acc = fe_mul<Fr>(acc, base);
+      base = fe_sqr<Fr>(base);
+    }
+    h = fe_mul<Fr>(h, acc);
+  }
+  fe_store<Fr>(out + ((size_t)a.off[k] + b) * 8, h);
+}
+
+// the arguments describe the polynomials of tile values (c = h, q = carries, z = z^T): one workgroup each, top tile first
+template <class Fr>
+__global__ void __launch_bounds__(256) k_poly_carries(PolyArgs a) {
+  __shared__ __attribute__((aligned(16))) u32 lds[257 * 8];
+  const u32 k = blockIdx.y, n = a.len[k];
+  if (n < 2u) return;
+  Fe<Fr> carry = fe_zero<Fr>();
+  for (u32 t = (n - 1u) / POLY_T + 1u; t-- > 0u;) {
+    Fe<Fr> r[POLY_E];
+    poly_tile_suffix<Fr>(a.c[k], n, t * POLY_T, carry, a, k, true, lds, r);
+    poly_store_quotient<Fr>(r, n, t * POLY_T, a.q[k], nullptr);
+    if (threadIdx.x == 0) fe_store<Fr>(lds + 256 * 8, r[0]);
+    __syncthreads();
+    carry = fe_load<Fr>(lds + 256 * 8);
+    __syncthreads();
+  }
+}
+
+// carries[off_k + b] = what enters tile b of polynomial k (read only when tile b is not the top one)
+template <class Fr>
+__global__ void __launch_bounds__(256) k_poly_div_tiles(PolyArgs a, const u32* __restrict__ carries) {
+  __shared__ __attribute__((aligned(16))) u32 lds[256 * 8];
+  const u32 k = blockIdx.y, n = a.len[k], b = blockIdx.x;
+  if ((u64)b * POLY_T >= n) return;
+  const bool top = ((u64)b + 1u) * POLY_T >= n;
+  const Fe<Fr> carry = top ? fe_zero<Fr>() : fe_load<Fr>(carries + ((size_t)a.off[k] + b) * 8);
+  Fe<Fr> r[POLY_E];
+  poly_tile_suffix<Fr>(a.c[k], n, b * POLY_T, carry, a, k, true, lds, r);
+  poly_store_quotient<Fr>(r, n, b * POLY_T, a.q[k], a.rem ? a.rem + (size_t)k * 8 : nullptr);
+}
+
 // An IPA round's vector work in ONE launch (three dispatches otherwise, each a launch latency on an idle GPU): the previous
 // round's fold, in place, c[i] += x^-1 c[cur + i], z[i] += x z[cur + i] (i < cur = 2 half), and on the folded vectors the
 // two inner products <c_r, z_l>, <c_l, z_r> (halves of length `half`).  Lane i owns elements i and half + i of both

@@ -169,6 +169,31 @@ class Context:
         ffi.check(self._lib.amsm_vec_random(self._h, seed, n, 1 if mont else 0, v.ptr), "amsm_vec_random")
         return v
 
+    # ---- polynomials (coefficient vectors, little-endian in the degree) ----
+    def poly_evaluate(self, vectors: Sequence["FrVector"], point_mont: np.ndarray) -> np.ndarray:
+        """p_k(point) for every vector in one call (amsm_poly_evaluate_batch) -> (k, 4) uint64, Montgomery."""
+        k = len(vectors)
+        ptrs = (C.c_void_p * max(k, 1))(*[v.ptr for v in vectors])
+        lens = (C.c_size_t * max(k, 1))(*[v.n for v in vectors])
+        pt = np.ascontiguousarray(point_mont, dtype=np.uint64).reshape(4)
+        out = np.zeros((k, 4), dtype=np.uint64)
+        ffi.check(self._lib.amsm_poly_evaluate_batch(self._h, ptrs, lens, k, _ptr(pt), _ptr(out)), "amsm_poly_evaluate_batch")
+        return out
+
+    def poly_div_linear(self, vectors: Sequence["FrVector"], zs_mont: np.ndarray, remainders: bool = True):
+        """Quotients of p_k by (X - z_k) as new FrVectors (amsm_poly_div_linear_batch) and, unless `remainders` is False
+        (then the call does not wait for the device), the values p_k(z_k) as a (k, 4) array."""
+        k = len(vectors)
+        zs = np.ascontiguousarray(zs_mont, dtype=np.uint64).reshape(k, 4)
+        quots = [FrVector(self, max(v.n - 1, 0)) for v in vectors]
+        ptrs = (C.c_void_p * max(k, 1))(*[v.ptr for v in vectors])
+        lens = (C.c_size_t * max(k, 1))(*[v.n for v in vectors])
+        qptrs = (C.c_void_p * max(k, 1))(*[q.ptr for q in quots])
+        rem = np.zeros((k, 4), dtype=np.uint64) if remainders else None
+        ffi.check(self._lib.amsm_poly_div_linear_batch(self._h, ptrs, lens, k, _ptr(zs), qptrs, _ptr(rem)),
+                  "amsm_poly_div_linear_batch")
+        return quots, rem
+
 
 class _ShardContext(Context):
     """Borrowed single-device context of one shard of a MultiContext (amsm_ctx_shard): allocate / fill vectors ON that

@@ -148,6 +148,10 @@ SIGNATURES = {
     "amsm_bases_fold": (C.c_int, [_vp, _vp, _sz, _vp, C.c_uint, C.POINTER(_vp)]),
     "amsm_vec_inner_product": (C.c_int, [_vp, _vp, _vp, _sz, _vp]),
     "amsm_vec_powers": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "amsm_poly_evaluate_batch": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), _sz, _vp, _vp]),
+    "amsm_poly_evaluate": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
+    "amsm_poly_div_linear_batch": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), _sz, _vp, C.POINTER(_vp), _vp]),
+    "amsm_poly_div_linear": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "amsm_ipa_check_poly_coeffs": (C.c_int, [_vp, _vp, _sz, _vp]),
     "amsm_ipa_round_scalars": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "amsm_ipa_round": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -5,26 +5,46 @@ Pedersen commitment of the coefficient vector and whose opening "proof" is the p
 SURVEY.md section 8(a) row a10 (BASELINE config 1): every commitment the scheme issues is an MSM of at most d+1 <=
 2^10 pairs through the same ABI as the large ones (`amsm_pedersen_commit_device`); the O(d) polynomial work per
 claim -- the quotient (p(X) - v) / (X - z), evaluations at the challenge point, the linear combination of the
-witness polynomials -- is small sequential host arithmetic in the reference too and stays on the host here
-(Python integers).  The sponge is pluggable like in the other mirrors (the SHA-256 stand-in, or sponge.PoseidonSponge: the reference's
+witness polynomials -- is sequential host arithmetic in the reference.  Here it is host arithmetic (Python integers) while
+the widest polynomial of a call has fewer than TRIVIAL_PC_DEVICE_MIN coefficients (config 1 is below it); from there on
+it runs on the device as in include/amsm_trivial_pc_as.hpp: one upload per witness polynomial, amsm_poly_div_linear_batch,
+the quotients committed from their device vectors, amsm_poly_evaluate_batch, amsm_vec_combine, one download of the combined
+polynomial.  This mirror's polynomials stay lists of integers, so it pays a conversion on each side of the device calls: it
+is the correctness mirror, speed is the C++ driver's business.  The sponge is pluggable like in the other mirrors (the SHA-256 stand-in, or sponge.PoseidonSponge: the reference's
 sponge with ark-sponge's parameters restated as recalled); what is absorbed and squeezed, and in which order, follows the reference's
 `absorb!` lists and is compared with their restatement outside the product in tests/test_transcripts_vs_oracle.py.
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from .engine import CommitterKey, Context, PedersenCommitment, VariableBaseMSM
-from .hp_as import ASForHadamardProducts, MalformedAccumulator, MalformedInput, _pt_eq
+from .hp_as import ASForHadamardProducts, MalformedAccumulator, MalformedInput, _pt_eq, combine_vectors
 from .scalar_field import Fr
 from .sponge import CryptographicSponge, Sha256Sponge
 
 LINEAR_COMBINATION_CHALLENGE_SIZE = 126  # :31
 CHALLENGE_POINT_SIZE = 184               # :32
 _lincomb = ASForHadamardProducts._lincomb
+# polynomials of at least this many coefficients take the device path (include/amsm.hpp: TRIVIAL_PC_DEVICE_MIN, the same number)
+TRIVIAL_PC_DEVICE_MIN = 1 << 11
+
+
+def _on_device(width: int) -> bool:
+    """AMSM_TRIVIAL_PC_DEVICE=0: never; =1: always; unset, empty or anything else: the threshold (the same rule as
+    include/amsm_trivial_pc_as.hpp: TrivialPC::on_device)"""
+    e = os.environ.get("AMSM_TRIVIAL_PC_DEVICE")
+    return e == "1" if e in ("0", "1") else width >= TRIVIAL_PC_DEVICE_MIN
+
+
+def _ints_of(fr: Fr, limbs: np.ndarray) -> List[int]:
+    """(n, 4) Montgomery limbs -> canonical integers"""
+    b = np.ascontiguousarray(limbs, dtype="<u8").tobytes()
+    return [int.from_bytes(b[i:i + 32], "little") * fr._rinv % fr.r for i in range(0, len(b), 32)]
 
 
 @dataclass
@@ -144,6 +164,17 @@ class TrivialPC:
         fr = Fr(vk.ctx.curve)
         if polynomial.degree() > cls.supported_degree(vk):
             return False
+        if not hasattr(vk, "sharded") and _on_device(len(polynomial.coeffs)):  # one upload serves the commitment and the evaluation
+            ctx = vk.ctx
+            vec = ctx.upload(fr.to_limbs_many(polynomial.coeffs))
+            try:
+                # (trailing zeros beyond the key, or no coefficients at all: commit() knows what to do with them)
+                fits = 0 < vec.n <= len(vk)
+                cm = PedersenCommitment.commit(vk, vec, None) if fits else cls.commit(vk, polynomial).elem
+                ev = fr.from_limbs(ctx.poly_evaluate([vec], fr.to_limbs(point))[0])
+            finally:
+                vec.free()
+            return _pt_eq(cm, commitment.elem) and ev == value % fr.r
         return _pt_eq(cls.commit(vk, polynomial).elem, commitment.elem) and polynomial.evaluate(fr, point) == value % fr.r
 
 
@@ -227,6 +258,8 @@ class ASForTrivialPC:
                     [cls._check_instance(a.instance, True) for a in accs]
         witnesses = [cls._check_witness(i.witness, pk, False) for i in inputs] + \
                     [cls._check_witness(a.witness, pk, True) for a in accs]
+        if not hasattr(pk, "sharded") and _on_device(max(len(w.coeffs) for w in witnesses)):  # (a dist.ShardedCommitterKey -- a Python-only key type with no C++ twin -- keeps the host path)
+            return cls._prove_device(pk, fr, sponge, instances, witnesses)
         # steps 1c-1d: witness polynomials w = (p - v) / (X - z) and their commitments (:181-222)
         wit_polys = [LabeledPolynomial(_poly_div_linear(fr, w.coeffs, inst.eval, inst.point))
                      for inst, w in zip(instances, witnesses)]
@@ -249,6 +282,43 @@ class ASForTrivialPC:
         combined_comm = _lincomb(ctx, comms, ch, fr)
         acc = Accumulator(InputInstance(LabeledCommitment(combined_comm), z, combined_eval), combined_poly)
         return acc, proof
+
+    @classmethod
+    def _prove_device(cls, pk: CommitterKey, fr: Fr, sponge, instances, witnesses):
+        """The same steps with the polynomials on the device (the header of this file says when).  A constant witness has the
+        quotient [0], as _poly_div_linear gives it."""
+        ctx = pk.ctx
+        K = len(instances)
+        live = []  # every device vector of this call: released whatever happens in between
+
+        def keep(v):
+            live.append(v)
+            return v
+
+        try:
+            wit_vecs = [keep(ctx.upload(fr.to_limbs_many(w.coeffs))) for w in witnesses]
+            points = np.stack([fr.to_limbs(inst.point) for inst in instances])
+            quots, _ = ctx.poly_div_linear(wit_vecs, points, remainders=False)  # steps 1c-1d (:181-222)
+            live.extend(quots)
+            for k in range(K):
+                if quots[k].n == 0:
+                    quots[k] = keep(ctx.upload(np.zeros((1, 4), dtype=np.uint64)))
+            pts, infs = VariableBaseMSM.multi_scalar_mul_multi(pk, [(0, q.view(0, min(q.n, len(pk)))) for q in quots], mont=True)
+            wit_comms = [LabeledCommitment((pts[k].copy(), bool(infs[k]))) for k in range(K)]
+            z = cls._challenge_point(fr, sponge, TrivialPC.supported_degree(pk), instances, wit_comms)  # step 2
+            polys = wit_vecs + quots
+            evals = ctx.poly_evaluate(polys, fr.to_limbs(z))  # steps 3-4
+            proof = [SingleProof(wit_comms[k], fr.from_limbs(evals[K + k]), fr.from_limbs(evals[k])) for k in range(K)]
+            ch = cls._lc_challenges(fr, sponge, z, proof)
+            combined = keep(combine_vectors(ctx, polys, np.stack([fr.to_limbs(c) for c in ch])))  # steps 5-7
+            combined_eval = fr.from_limbs(ctx.poly_evaluate([combined], fr.to_limbs(z))[0])
+            combined_poly = LabeledPolynomial(_ints_of(fr, combined.download()))
+        finally:
+            for v in live:
+                v.free()
+        comms = [i.commitment.elem for i in instances] + [wc.elem for wc in wit_comms]
+        combined_comm = _lincomb(ctx, comms, ch, fr)
+        return Accumulator(InputInstance(LabeledCommitment(combined_comm), z, combined_eval), combined_poly), proof
 
     # ---- verify (:470-609) --------------------------------------------------------------------------------
     @classmethod

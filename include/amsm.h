@@ -479,6 +479,21 @@ int amsm_bases_fold(amsm_ctx* ctx, const amsm_bases* key, size_t n_half, const u
 int amsm_vec_inner_product(amsm_ctx* ctx, const void* d_a, const void* d_b, size_t n, uint64_t* out_mont);
 /* d_out[i] = point^i, i < n  (the evaluation vector z of the opening). */
 int amsm_vec_powers(amsm_ctx* ctx, const uint64_t* point_mont, size_t n, void* d_out);
+/* p(point) for n_polys device vectors of Montgomery Fr coefficients, little-endian in the degree: the `evaluate` calls of
+ * src/trivial_pc_as/mod.rs:402-403 and :441 and of examples/scaling-as.rs:179, one launch for all polynomials of a prove.
+ * out_mont: n_polys x 4 u64.  lens[k] == 0 gives 0.  Blocks until the values are on the host. */
+int amsm_poly_evaluate_batch(amsm_ctx* ctx, const void* const* d_coeffs, const size_t* lens, size_t n_polys,
+                             const uint64_t* point_mont, uint64_t* out_mont);
+int amsm_poly_evaluate(amsm_ctx* ctx, const void* d_coeffs, size_t n, const uint64_t* point_mont, uint64_t* out_mont);
+/* Quotient of each polynomial by (X - z_k), the `Div` of the witness polynomial (p(X) - v) / (X - z) at
+ * src/trivial_pc_as/mod.rs:198-202 (the constant v only changes the remainder): d_quot[k] receives lens[k] - 1 elements
+ * (nothing when lens[k] <= 1); rem_mont (nullable, n_polys x 4 u64) receives p_k(z_k).  z_mont: n_polys x 4 u64.
+ * d_quot[k] must not overlap d_coeffs[k].  Stream-ordered on the context's stream like amsm_vec_powers; blocks only when
+ * rem_mont is given. */
+int amsm_poly_div_linear_batch(amsm_ctx* ctx, const void* const* d_coeffs, const size_t* lens, size_t n_polys,
+                               const uint64_t* z_mont, void* const* d_quot, uint64_t* rem_mont);
+int amsm_poly_div_linear(amsm_ctx* ctx, const void* d_coeffs, size_t n, const uint64_t* z_mont, void* d_quot,
+                         uint64_t* rem_mont);
 /* Scalars of the two cross commitments L_j = <c_r, key_l>, R_j = <c_l, key_r> of opening round j (0-based) expressed
  * over the ORIGINAL key of n = 2^log_n generators, so that no key is folded between rounds: with xi_0..xi_{j-1} the
  * previous rounds' challenges (key_l += xi * key_r each round) and d_coeffs the current coefficient vector of

@@ -45,6 +45,10 @@ inline CurveInfo curve_info(int curve) {
     default: return {0, 99, 99};
   }
 }
+// trivial_pc_as: a prove / decide whose widest polynomial has at least this many coefficients divides, evaluates and combines on
+// the device (amsm_poly_*); below it the polynomial arithmetic stays on the host.  The same number as
+// accumulation_amd/trivial_pc_as.py:TRIVIAL_PC_DEVICE_MIN; AMSM_TRIVIAL_PC_DEVICE=0|1 overrides it (never / always).
+constexpr size_t TRIVIAL_PC_DEVICE_MIN = (size_t)1 << 11;  // measured on MI355X
 
 // Affine point in the ABI's format: x_mont | y_mont (2*limbs u64) + infinity flag.
 struct Affine {
@@ -229,12 +233,14 @@ struct MsmBatch {
     }, "amsm_msm_batch_device");
   }
   // windows of one key: job = (first generator, scalars)
-  static std::vector<Affine> windows(const CommitterKey& bases, const std::vector<std::pair<size_t, const FrVector*>>& jobs) {
+  // (max_len: a job uses at most that many of its scalars -- a polynomial with more coefficients than the key has generators)
+  static std::vector<Affine> windows(const CommitterKey& bases, const std::vector<std::pair<size_t, const FrVector*>>& jobs,
+                                     size_t max_len = (size_t)-1) {
     std::vector<size_t> offs, ns;
     std::vector<const void*> ptrs;
     for (auto& j : jobs) {
       offs.push_back(j.first);
-      ns.push_back(j.second->len());
+      ns.push_back(std::min(j.second->len(), max_len));
       ptrs.push_back(j.second->ptr());
     }
     return run(bases, jobs.size(), [&](uint64_t* xy, uint8_t* inf) {
@@ -355,6 +361,42 @@ struct PedersenCommitment {
     return out;
   }
 };
+
+// Polynomials as device vectors of coefficients, little-endian in the degree (src/trivial_pc_as/mod.rs:198-202, :402-403, :441).
+// p_k(point) for every vector in one call: amsm_poly_evaluate_batch
+inline std::vector<Fr> poly_evaluate(Context& ctx, const std::vector<const FrVector*>& vectors, const Fr& point) {
+  std::vector<const void*> ptrs;
+  std::vector<size_t> lens;
+  for (auto* v : vectors) {
+    ptrs.push_back(v->ptr());
+    lens.push_back(v->len());
+  }
+  std::vector<Fr> out(vectors.size());
+  check(amsm_poly_evaluate_batch(ctx.get(), ptrs.data(), lens.data(), vectors.size(), point.data(), reinterpret_cast<uint64_t*>(out.data())),
+        "amsm_poly_evaluate_batch");
+  return out;
+}
+// quotients of p_k by (X - z_k) as new vectors (len - 1 elements; none for a constant) and, when `remainders` is given, the values
+// p_k(z_k) -- without it the call does not wait for the device: amsm_poly_div_linear_batch
+inline std::vector<FrVector> poly_div_linear(Context& ctx, const std::vector<const FrVector*>& vectors, const std::vector<Fr>& zs,
+                                             std::vector<Fr>* remainders = nullptr) {
+  if (zs.size() != vectors.size()) throw Error(AMSM_E_INVALID_ARG, "poly_div_linear: one point per polynomial");
+  std::vector<FrVector> quots;
+  std::vector<const void*> ptrs;
+  std::vector<void*> qptrs;
+  std::vector<size_t> lens;
+  for (auto* v : vectors) {
+    quots.emplace_back(ctx, v->len() ? v->len() - 1 : 0);
+    ptrs.push_back(v->ptr());
+    lens.push_back(v->len());
+  }
+  for (auto& q : quots) qptrs.push_back(q.ptr());
+  if (remainders) remainders->assign(vectors.size(), Fr{0, 0, 0, 0});
+  check(amsm_poly_div_linear_batch(ctx.get(), ptrs.data(), lens.data(), vectors.size(), reinterpret_cast<const uint64_t*>(zs.data()),
+                                   qptrs.data(), remainders ? reinterpret_cast<uint64_t*>(remainders->data()) : nullptr),
+        "amsm_poly_div_linear_batch");
+  return quots;
+}
 
 // The scalar-field vector loops of ASForHadamardProducts (src/hp_as/mod.rs).
 namespace hp_as {

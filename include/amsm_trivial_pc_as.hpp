@@ -3,9 +3,15 @@
 // the C ABI of include/amsm.h.  SURVEY.md section 8(a) row a10 / BASELINE config 1: every commitment is a Pedersen
 // commitment of a coefficient vector (an MSM of at most d+1 pairs through amsm_pedersen_commit_device); the O(d)
 // polynomial work per claim -- the quotient (p(X) - v) / (X - z), evaluations at the challenge point, the linear
-// combination of the witness polynomials -- is sequential host arithmetic in the reference and here (amsm_fr_*).
+// combination of the witness polynomials -- is sequential host arithmetic in the reference.  Here it is host arithmetic
+// (amsm_fr_*) while the widest polynomial of a call has fewer than TRIVIAL_PC_DEVICE_MIN coefficients (amsm.hpp; config 1 is
+// below it), and from there on it runs on the device: every witness polynomial is uploaded once, divided (amsm_poly_div_linear_batch),
+// the quotients are committed from their device vectors, witnesses and quotients are evaluated in one call
+// (amsm_poly_evaluate_batch), combined (amsm_vec_combine), and the combined polynomial comes back once -- the accumulator's witness
+// stays a host vector.  Both paths compute the same field elements: proofs and accumulators do not depend on the choice.
 // Same structure and same stand-in sponge as accumulation_amd/trivial_pc_as.py; tests compare the two byte for byte.
 #pragma once
+#include <cstdlib>
 #include <memory>
 
 #include "amsm_hp_as.hpp"
@@ -96,11 +102,25 @@ struct TrivialPC {  // setup / trim / commit / check (ext)
     for (size_t j = 0; j < which.size(); j++) out[which[j]] = LabeledCommitment{pts[j], {}};
     return out;
   }
+  // polynomials of at least TRIVIAL_PC_DEVICE_MIN coefficients take the device path.  AMSM_TRIVIAL_PC_DEVICE=0: never; =1: always;
+  // unset, empty or anything else: the threshold (the same rule as accumulation_amd/trivial_pc_as.py:_on_device)
+  static bool on_device(size_t width) {
+    const char* e = std::getenv("AMSM_TRIVIAL_PC_DEVICE");
+    if (e && e[0] && !e[1] && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
+    return width >= TRIVIAL_PC_DEVICE_MIN;
+  }
   // check_individual_opening_challenges with one commitment and opening challenge 1: the proof IS the polynomial
   static bool check(const CommitterKey& vk, const LabeledCommitment& c, const Fr& point, const Fr& value,
                     const LabeledPolynomial& polynomial) {
     FrOps fr{amsm_ctx_curve(vk.ctx().get())};
     if (polynomial.degree() > supported_degree(vk)) return false;
+    if (on_device(polynomial.coeffs.size())) {  // one upload serves the commitment and the evaluation
+      FrVector v(vk.ctx(), polynomial.coeffs);
+      // (trailing zeros beyond the key, or no coefficients at all: commit() knows what to do with them)
+      const bool fits = v.len() > 0 && v.len() <= vk.supported_num_elems();
+      Affine cm = fits ? PedersenCommitment::commit(vk, v) : commit(vk, polynomial).elem;
+      return cm == c.elem && poly_evaluate(vk.ctx(), {&v}, point)[0] == value;
+    }
     return commit(vk, polynomial).elem == c.elem && polynomial.evaluate(fr, point) == value;
   }
 };
@@ -147,6 +167,9 @@ class ASForTrivialPC {
       instances.push_back(&check_instance(a.instance, true));
       witnesses.push_back(&check_witness(a.witness, pk, true));
     }
+    size_t widest = 0;
+    for (auto* w : witnesses) widest = std::max(widest, w->coeffs.size());
+    if (TrivialPC::on_device(widest)) return prove_device(pk, fr, sponge, instances, witnesses);
     // steps 1c-1d: witness polynomials w = (p - v) / (X - z) and their commitments (:181-222)
     std::vector<LabeledPolynomial> wit_polys;
     for (size_t k = 0; k < instances.size(); k++)
@@ -174,6 +197,44 @@ class ASForTrivialPC {
     for (auto& w : wit_comms) comms.push_back(&w.elem);
     Affine cc = lincomb(ctx, comms, ch);
     return {Accumulator{InputInstance{LabeledCommitment{cc, {}}, z, combined_eval}, combined}, proof};
+  }
+
+  // The same steps with the polynomials on the device (the header of this file says when).  A constant witness has the
+  // quotient [0], as poly_div_linear gives it.
+  static std::pair<Accumulator, Proof> prove_device(const CommitterKey& pk, const FrOps& fr, Sponge& sponge,
+                                                    const std::vector<const InputInstance*>& instances,
+                                                    const std::vector<const LabeledPolynomial*>& witnesses) {
+    Context& ctx = pk.ctx();
+    const size_t K = instances.size();
+    std::vector<FrVector> wit_vecs;
+    std::vector<const FrVector*> polys;
+    std::vector<Fr> points;
+    for (size_t k = 0; k < K; k++) {
+      wit_vecs.emplace_back(ctx, witnesses[k]->coeffs);
+      points.push_back(instances[k]->point);
+    }
+    for (auto& v : wit_vecs) polys.push_back(&v);
+    std::vector<FrVector> quots = poly_div_linear(ctx, polys, points);  // steps 1c-1d (:181-222)
+    for (size_t k = 0; k < K; k++)
+      if (quots[k].len() == 0) quots[k] = FrVector(ctx, std::vector<Fr>{fr.zero()});
+    std::vector<std::pair<size_t, const FrVector*>> jobs;
+    for (auto& q : quots) jobs.push_back({0, &q});
+    std::vector<Affine> wit_pts = MsmBatch::windows(pk, jobs, pk.supported_num_elems());
+    std::vector<LabeledCommitment> wit_comms;
+    for (auto& p : wit_pts) wit_comms.push_back(LabeledCommitment{p, {}});
+    Fr z = challenge_point(fr, sponge, TrivialPC::supported_degree(pk), instances, wit_comms);  // step 2
+    for (auto& q : quots) polys.push_back(&q);
+    std::vector<Fr> evals = poly_evaluate(ctx, polys, z);  // steps 3-4
+    Proof proof;
+    for (size_t k = 0; k < K; k++) proof.push_back(SingleProof{wit_comms[k], evals[K + k], evals[k]});
+    std::vector<Fr> ch = lc_challenges(fr, sponge, z, proof);
+    FrVector combined = hp_as::combine_vectors(ctx, polys, ch);  // steps 5-7
+    Fr combined_eval = poly_evaluate(ctx, {&combined}, z)[0];
+    std::vector<const Affine*> comms;
+    for (auto* i : instances) comms.push_back(&i->commitment.elem);
+    for (auto& w : wit_comms) comms.push_back(&w.elem);
+    Affine cc = lincomb(ctx, comms, ch);
+    return {Accumulator{InputInstance{LabeledCommitment{cc, {}}, z, combined_eval}, LabeledPolynomial{combined.to_host(), {}, {}}}, proof};
   }
 
   // ---- verify (:470-609) ---------------------------------------------------------------------------------------
