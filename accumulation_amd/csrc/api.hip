@@ -29,6 +29,7 @@
 #include "host_field.h"
 #include "host_glv.h"
 #include "host_poseidon.h"
+#include "host_sample.h"
 #include "host_serialize.h"
 #include "launch.h"
 #include "msm_select.h"

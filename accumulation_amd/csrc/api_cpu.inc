@@ -96,6 +96,26 @@ int bases_generate(amsm_ctx* c, uint64_t seed, size_t n, unsigned flags, amsm_ba
   *out = b;
   return AMSM_OK;
 }
+// G_(first + i) of the derivation "amsm-sample-v1" (host_sample.h: sample_point; the kernels of sample_kernels.h give the same bits)
+template <class Fq, class Fr>
+int bases_sample(amsm_ctx* c, const uint8_t* domain, size_t domain_len, uint64_t first, size_t n, unsigned flags, amsm_bases** out) {
+  if (flags > 31u) return AMSM_E_INVALID_ARG;
+  amsm_bases* b = bases_new<Fq>(c, n);
+  if (!b) return AMSM_E_OOM;
+  constexpr size_t PW = pt_words<Fq>();
+  const b2s::SamplePrefix prefix = b2s::sample_prefix(CurveOf<Fq>::type::id, domain, domain_len);
+  std::atomic<int> exhausted{0};
+  par_for(n, 16, [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; i++)
+      if (!host::sample_point<Fq>(prefix, first + i, 0, (u64*)b->d_table + i * PW, nullptr)) exhausted.store(1, std::memory_order_relaxed);
+  });
+  if (exhausted.load()) {  // an index used up its 256 attempts: no key
+    amsm_bases_free(b);
+    return AMSM_E_UNSUPPORTED;
+  }
+  *out = b;
+  return AMSM_OK;
+}
 template <class Fq>
 int bases_read(const amsm_bases* b, size_t off, size_t n, uint64_t* xy, uint8_t* is_inf) {
   if (off > b->n || n > b->n - off) return AMSM_E_INVALID_ARG;

@@ -34,6 +34,22 @@ int amsm_bases_generate(amsm_ctx* c, uint64_t seed, size_t n, unsigned flags, am
     });
   return DISPATCH(c, bases_generate_impl<Fq, Fr>(c, seed, n, flags, out));
 }
+int amsm_bases_sample(amsm_ctx* c, const uint8_t* domain, size_t domain_len, uint64_t first, size_t n, unsigned flags, amsm_bases** out) {
+  if (!c || !out || domain_len > (size_t)b2s::SAMPLE_MAX_DOMAIN || (domain_len && !domain) || flags > 31u) return AMSM_E_INVALID_ARG;
+  if (n >= (1ull << 31)) return AMSM_E_UNSUPPORTED;
+  if (c->host_only) return CPU_CALL(c, bases_sample, c, domain, domain_len, first, n, flags, out);
+  TRY(bind_device(c));
+  if (wants_replicas(c, n, flags))  // every device samples the whole key
+    return bases_create_replicated(c, out, [&](size_t, amsm_ctx* cg, amsm_bases** o) {
+      return DISPATCH(cg, bases_sample_impl<Fq, Fr>(cg, domain, domain_len, first, n, flags & ~(unsigned)AMSM_BASES_REPLICATE, o));
+    });
+  flags &= ~(unsigned)AMSM_BASES_REPLICATE;
+  if (ctx_shards_keys(c))  // shard g samples its own index range
+    return bases_create_sharded(c, n, out, [&](size_t, amsm_ctx* cg, size_t lo, size_t cnt, amsm_bases** o) {
+      return DISPATCH(cg, bases_sample_impl<Fq, Fr>(cg, domain, domain_len, first + lo, cnt, flags, o));
+    });
+  return DISPATCH(c, bases_sample_impl<Fq, Fr>(c, domain, domain_len, first, n, flags, out));
+}
 int amsm_bases_read(amsm_ctx* c, const amsm_bases* b, size_t off, size_t n, uint64_t* xy, uint8_t* is_inf) {
   if (!c || !b || (n && !xy) || b->curve != c->curve) return AMSM_E_INVALID_ARG;
   if (key_sharded(b)) {

@@ -302,6 +302,89 @@ int bases_generate_impl(amsm_ctx* ctx, uint64_t seed, size_t n, unsigned flags, 
   return AMSM_OK;
 }
 
+// Transparent key: table[t] = G_(first + t) of the derivation "amsm-sample-v1" (include/amsm.h: amsm_bases_sample), sampled on the
+// device (sample_kernels.h).  Search passes over the shrinking list of unsolved indices, one square test per index and pass,
+// while the list is long; the last few thousand loop per lane; then one finishing pass over every index.  Working memory: 20 bytes
+// per generator (two lists and the winning attempts), freed on return.
+template <class Fq, class Fr>
+int bases_sample_impl(amsm_ctx* ctx, const uint8_t* domain, size_t domain_len, uint64_t first, size_t n, unsigned flags,
+                      amsm_bases** out) {
+  constexpr u32 TAIL = 4096;    // a list this short is finished by one launch whose lanes loop
+  constexpr int MAX_PASSES = 24;  // (the list halves per pass: 2^31 indices are down to TAIL after 19)
+  amsm_bases* b = new (std::nothrow) amsm_bases();
+  if (!b) return AMSM_E_OOM;
+  b->curve = ctx->curve;
+  b->device = ctx->device;
+  b->n = n;
+  u32* jwin = nullptr;
+  u64* pend[2] = {nullptr, nullptr};
+  u32* counters = nullptr;
+  auto release = [&](int rc) {
+    if (jwin) (void)hipFree(jwin);
+    if (pend[0]) (void)hipFree(pend[0]);
+    if (pend[1]) (void)hipFree(pend[1]);
+    if (counters) (void)hipFree(counters);
+    if (rc != AMSM_OK) {
+      if (b->d_table) (void)hipFree(b->d_table);
+      delete b;
+    }
+    return rc;
+  };
+  if (hipMalloc((void**)&b->d_table, std::max<size_t>(n, 1) * affine_bytes<Fq>()) != hipSuccess) {
+    (void)hipGetLastError();
+    b->d_table = nullptr;
+    return release(AMSM_E_OOM);
+  }
+  if (n) {
+    if (hipMalloc((void**)&jwin, n * 4) != hipSuccess || hipMalloc((void**)&pend[0], n * 8) != hipSuccess ||
+        hipMalloc((void**)&pend[1], n * 8) != hipSuccess || hipMalloc((void**)&counters, SAMPLE_CNT_WORDS * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      return release(AMSM_E_OOM);
+    }
+    const SampleConsts k = host::sample_consts<Fq>(domain, domain_len);
+    hipStream_t st = ctx->stream;
+    u32 cnt[SAMPLE_CNT_WORDS] = {0};
+    auto read_counters = [&]() {
+      return hipMemcpyAsync(cnt, counters, sizeof(cnt), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess &&
+             hipGetLastError() == hipSuccess;
+    };
+    if (hipMemsetAsync(counters, 0, SAMPLE_CNT_WORDS * 4, st) != hipSuccess) return release(AMSM_E_HIP);
+    // pass 0 takes the indices themselves (no list); pass p reads list (p - 1) & 1 and writes list p & 1
+    u32 pending = (u32)n;
+    for (int pass = 0; pending; pass++) {
+      const bool last = pass > 0 && (pending <= TAIL || pass >= MAX_PASSES);
+      launch_sample_search<Fq>(st, b->d_table, jwin, pass ? pend[(pass - 1) & 1] : nullptr, pending, pend[pass & 1], counters, k, first,
+                               last ? (u32)b2s::SAMPLE_MAX_ATTEMPTS : 1u);
+      if (!read_counters()) return release(AMSM_E_HIP);
+      if (cnt[SAMPLE_CNT_EXHAUSTED]) return release(AMSM_E_UNSUPPORTED);  // an index used up its 256 attempts: no key
+      if (last && cnt[SAMPLE_CNT_PENDING]) return release(AMSM_E_HIP);    // (cannot happen: the looping pass leaves nothing)
+      pending = cnt[SAMPLE_CNT_PENDING];
+      if (hipMemsetAsync(counters + SAMPLE_CNT_PENDING, 0, 4, st) != hipSuccess) return release(AMSM_E_HIP);
+    }
+    launch_sample_finish<Fq>(st, b->d_table, jwin, (u32)n, counters, k, first);
+    if (!read_counters()) return release(AMSM_E_HIP);
+    if (cnt[SAMPLE_CNT_IDENTITY]) {
+      // a candidate whose cofactor multiple is the identity (one in 2^250 or so) is a rejection the finishing kernel cannot act on:
+      // those indices are derived again on the host, past that attempt, and written into the table
+      std::vector<u32> hj(n);
+      if (hipMemcpy(hj.data(), jwin, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return release(AMSM_E_HIP);
+      std::vector<u64> xy(2 * host::HFe<Fq>::N);
+      for (size_t t = 0; t < n; t++) {
+        if (!(hj[t] & 0x80000000u)) continue;
+        if (!host::sample_point<Fq>(k.prefix, first + t, (hj[t] & 0x7fffffffu) + 1u, xy.data(), nullptr)) return release(AMSM_E_UNSUPPORTED);
+        u32* slot = b->d_table + t * (affine_bytes<Fq>() / 4);
+        if (hipMemcpy(slot, xy.data(), affine_bytes<Fq>(), hipMemcpyHostToDevice) != hipSuccess) return release(AMSM_E_HIP);
+        launch_points_import<Fq>(st, slot, slot, 1);
+        if (hipStreamSynchronize(st) != hipSuccess) return release(AMSM_E_HIP);
+      }
+    }
+    const int s = bases_finish<Fq, Fr>(ctx, b, flags);
+    if (s != AMSM_OK) return release(s);
+  }
+  *out = b;
+  return release(AMSM_OK);
+}
+
 template <class Fq>
 int bases_read_impl(amsm_ctx* ctx, const amsm_bases* b, size_t off, size_t n, uint64_t* xy, uint8_t* is_inf) {
   if (off > b->n || n > b->n - off) return AMSM_E_INVALID_ARG;

@@ -20,6 +20,7 @@ struct PallasCurve {  // ark-pallas 0.2: y^2 = x^3 + 5, cofactor 1
   static constexpr bool subgroup_check = false;
   static constexpr u64 gx[4] = {0x992d30ed00000000ull, 0x224698fc094cf91bull, 0, 0x4000000000000000ull};  // -1
   static constexpr u64 gy[4] = {2, 0, 0, 0};
+  static constexpr u64 cofactor[2] = {1, 0};
 };
 struct Bls12381Curve {  // ark-bls12-381 0.2 G1: y^2 = x^3 + 4, cofactor != 1
   using Fq = Bls12381Fq;
@@ -31,6 +32,7 @@ struct Bls12381Curve {  // ark-bls12-381 0.2 G1: y^2 = x^3 + 4, cofactor != 1
                                 0xc3688c4f9774b905ull, 0x2695638c4fa9ac0full, 0x17f1d3a73197d794ull};
   static constexpr u64 gy[6] = {0x0caa232946c5e7e1ull, 0xd03cc744a2888ae4ull, 0x00db18cb2c04b3edull,
                                 0xfcf5e095d5d00af6ull, 0xa09e30ed741d8ae4ull, 0x08b3f481e3aaa0f1ull};
+  static constexpr u64 cofactor[2] = {0x8c00aaab0000aaabull, 0x396c8c005555e156ull};  // #E(Fq) / r
 };
 struct VestaCurve {  // ark-vesta 0.2: y^2 = x^3 + 5, cofactor 1; Fq = Pallas Fr, Fr = Pallas Fq
   using Fq = VestaFq;
@@ -40,6 +42,7 @@ struct VestaCurve {  // ark-vesta 0.2: y^2 = x^3 + 5, cofactor 1; Fq = Pallas Fr
   static constexpr bool subgroup_check = false;
   static constexpr u64 gx[4] = {0x8c46eb2100000000ull, 0x224698fc0994a8ddull, 0, 0x4000000000000000ull};  // -1
   static constexpr u64 gy[4] = {2, 0, 0, 0};
+  static constexpr u64 cofactor[2] = {1, 0};
 };
 
 // base field pack -> its curve

@@ -9,6 +9,7 @@
 #include "host_glv.h"
 #include "launch.h"
 #include "msm_kernels.h"
+#include "sample_kernels.h"
 
 namespace amsm {
 
@@ -364,6 +365,18 @@ void launch_generate_bases<AMSM_FQ>(hipStream_t st, u32* table, u64 seed, u32 fi
   AffineWords<FQD> gen;
   for (int i = 0; i < 2 * FQD::W; i++) gen.w[i] = gen_xy_mont[i];
   hipLaunchKernelGGL((k_generate_bases<FQD>), dim3(cdiv_(n, 256)), dim3(256), 0, st, table, seed, first, n, gen);
+}
+template <>
+void launch_sample_search<AMSM_FQ>(hipStream_t st, u32* table, u32* jwin, const u64* pend_in, u32 n_in, u64* pend_out, u32* counters,
+                                   const SampleConsts& k, u64 first, u32 max_tests) {
+  if (n_in == 0) return;
+  hipLaunchKernelGGL((k_sample_search<FQD>), dim3(cdiv_(n_in, 256)), dim3(256), 0, st, table, jwin, pend_in, n_in, pend_out, counters, k,
+                     first, max_tests);
+}
+template <>
+void launch_sample_finish<AMSM_FQ>(hipStream_t st, u32* table, u32* jwin, u32 n, u32* counters, const SampleConsts& k, u64 first) {
+  if (n == 0) return;
+  hipLaunchKernelGGL((k_sample_finish<FQD>), dim3(cdiv_(n, 256)), dim3(256), 0, st, table, jwin, n, counters, k, first);
 }
 template <>
 bool device_internal_radix<AMSM_FQ>() {

@@ -71,6 +71,15 @@ template <class Fq>
 void launch_apply_inf(hipStream_t st, u32* table, const uint8_t* is_inf, u32 n);
 template <class Fq>
 void launch_generate_bases(hipStream_t st, u32* table, u64 seed, u32 first, u32 n, const u32* gen_xy_mont);
+// Transparent keys (sample_kernels.h).  One SEARCH pass gives every listed index (pend_in: n_in words (attempt << 32 | t); null: t =
+// 0 .. n_in - 1 from attempt 0) up to `max_tests` square tests: a winner leaves its attempt in jwin[t] and its candidate in table[t],
+// a loser is appended to pend_out (counters[SAMPLE_CNT_PENDING]) with its next attempt.  FINISH turns the candidates into the points
+// G_(first + t), in the device radix.
+template <class Fq>
+void launch_sample_search(hipStream_t st, u32* table, u32* jwin, const u64* pend_in, u32 n_in, u64* pend_out, u32* counters,
+                          const SampleConsts& k, u64 first, u32 max_tests);
+template <class Fq>
+void launch_sample_finish(hipStream_t st, u32* table, u32* jwin, u32 n, u32* counters, const SampleConsts& k, u64 first);
 
 // The device may keep points in an internal Montgomery radix (fpu.h): key tables, partials and buckets are in it,
 // everything the C ABI exposes is not.  import/export convert a point array (src may equal dst); they do

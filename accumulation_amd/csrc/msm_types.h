@@ -2,10 +2,29 @@
 #pragma once
 #include <stdint.h>
 
+#include "blake2s.h"
+
 namespace amsm {
 
 typedef uint32_t u32;
 typedef uint64_t u64;
+
+// Arguments of the key sampling kernels (sample_kernels.h), filled by host_sample.h: sample_consts from the modulus.  Field elements
+// are C-ABI Montgomery words (12 hold the widest base field), integers little-endian words.
+struct SampleConsts {
+  b2s::SamplePrefix prefix;  // the part of the hashed message in front of the index
+  u32 b[12];                 // the curve's b
+  u32 r2[12];                // R^2 mod p: the Montgomery form of R (takes a canonical integer into the field)
+  u32 root[12];              // a primitive 2^two_adicity-th root of unity
+  u32 half[12];              // the integer (p - 1) / 2: y > p - y  <=>  y > half
+  u32 exp[12];               // two_adicity 1: (p + 1) / 4, the square root's exponent; else (t - 1) / 2, p - 1 = 2^two_adicity t
+  u32 exp_bits;
+  u32 two_adicity;
+  u32 cofactor[4];
+  u32 cofactor_bits;
+};
+// counters of one sampling call (device words)
+enum { SAMPLE_CNT_PENDING = 0, SAMPLE_CNT_EXHAUSTED = 1, SAMPLE_CNT_IDENTITY = 2, SAMPLE_CNT_WORDS = 3 };
 
 constexpr int VEC_MAX = 8;        // max vectors combined in one launch (reference uses 2..4)
 constexpr int HP_MAX_INPUTS = 8;  // max inputs+accumulators of one hp_as t-vector launch (reference tests reach 6)

@@ -406,6 +406,16 @@ class CommitterKey:
         ffi.check(ctx._lib.amsm_bases_generate(ctx._h, seed, n, flags, C.byref(h)), "amsm_bases_generate")
         return cls(ctx, h)
 
+    @classmethod
+    def sample(cls, ctx: Context, domain: bytes, n: int, flags: int = ffi.AMSM_BASES_DEFAULT, first: int = 0) -> "CommitterKey":
+        """Transparent key: generators `first .. first + n - 1` of the derivation "amsm-sample-v1" over `domain` (at most 32 bytes),
+        hashed to the curve on the device (amsm_bases_sample).  Nobody knows a discrete logarithm between two of them -- unlike
+        generate(), whose generators are public multiples of one point."""
+        domain = bytes(domain)
+        h = C.c_void_p()
+        ffi.check(ctx._lib.amsm_bases_sample(ctx._h, domain, len(domain), first, n, flags, C.byref(h)), "amsm_bases_sample")
+        return cls(ctx, h)
+
     def fold(self, n_half: int, x_limbs: np.ndarray, nbits: int = 255) -> "CommitterKey":
         """New (plain) key of n_half generators: out[i] = self[i] + x * self[n_half + i] -- the key fold
         `key_l += key_r * xi` of the IPA opening (ark_poly_commit::ipa_pc ext, under src/ipa_pc_as/mod.rs:454),
@@ -578,8 +588,18 @@ class PedersenCommitment:
     """ark_poly_commit::trivial_pc::PedersenCommitment (ext): setup / commit."""
 
     @staticmethod
-    def setup(ctx: Context, n: int, seed: int = 0x5EED1001, flags: int = ffi.AMSM_BASES_DEFAULT) -> CommitterKey:
-        """n generators + one hiding generator (the (n+1)-th point of the synthetic stream)."""
+    def setup(ctx: Context, n: int, seed: int = 0x5EED1001, flags: int = ffi.AMSM_BASES_DEFAULT,
+              domain: Optional[bytes] = None) -> CommitterKey:
+        """n generators + one hiding generator (the (n+1)-th point of the synthetic stream).  With `domain` the key is a transparent
+        one instead (CommitterKey.sample): generators G_0 .. G_(n-1) of that domain, sampled into the resident key, and the hiding
+        generator G_n; `seed` is not used then."""
+        if domain is not None:
+            hid = CommitterKey.sample(ctx, domain, 1, ffi.AMSM_BASES_NO_PRECOMPUTE, first=n)
+            hxy, _ = hid.read(0, 1)
+            hid.free()
+            out = CommitterKey.sample(ctx, domain, n, flags)
+            out.hiding_generator = hxy[0].copy()
+            return out
         ck = CommitterKey.generate(ctx, seed, n + 1, ffi.AMSM_BASES_NO_PRECOMPUTE)
         xy, _ = ck.read(0, n + 1)
         ck.free()

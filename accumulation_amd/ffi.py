@@ -71,6 +71,7 @@ SIGNATURES = {
     "amsm_ctx_stage_ms": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_float)]),
     "amsm_bases_load": (C.c_int, [_vp, _vp, _vp, _sz, C.c_uint, C.POINTER(_vp)]),
     "amsm_bases_generate": (C.c_int, [_vp, C.c_uint64, _sz, C.c_uint, C.POINTER(_vp)]),
+    "amsm_bases_sample": (C.c_int, [_vp, C.c_char_p, _sz, C.c_uint64, _sz, C.c_uint, C.POINTER(_vp)]),
     "amsm_bases_read": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "amsm_bases_len": (_sz, [_vp]),
     "amsm_bases_num_shards": (C.c_int, [_vp]),

@@ -115,9 +115,16 @@ class InnerProductArgPC:
 
     # ---- keys -------------------------------------------------------------------------------------
     @classmethod
-    def setup(cls, ctx: Context, max_degree: int, seed: int = 0x1BA5EED) -> CommitterKey:
-        """UniversalParams: max_degree+1 generators + h + s (synthetic stream; ark-poly-commit hashes to the curve)."""
+    def setup(cls, ctx: Context, max_degree: int, seed: int = 0x1BA5EED, domain: Optional[bytes] = None) -> CommitterKey:
+        """UniversalParams: max_degree+1 generators + h + s (synthetic stream; ark-poly-commit hashes to the curve).  With `domain`:
+        a transparent key (EngineKey.sample) -- generators G_0 .. G_(n-1) of that domain, h = G_n, s = G_(n+1); `seed` is not used."""
         n = 1 << (max_degree + 1 - 1).bit_length()  # (max_degree + 1).next_power_of_two()
+        if domain is not None:
+            tmp = EngineKey.sample(ctx, domain, 2, ffi.AMSM_BASES_NO_PRECOMPUTE, first=n)
+            hs, _ = tmp.read()
+            tmp.free()
+            key = EngineKey.sample(ctx, domain, n, ffi.AMSM_BASES_DEFAULT)
+            return CommitterKey(key, (hs[0].copy(), False), (hs[1].copy(), False), n - 1)
         tmp = EngineKey.generate(ctx, seed, n + 2, ffi.AMSM_BASES_NO_PRECOMPUTE)
         xy, _ = tmp.read()
         tmp.free()

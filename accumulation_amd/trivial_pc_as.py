@@ -106,8 +106,9 @@ class TrivialPC:
     """ark_poly_commit::trivial_pc::TrivialPC (ext): setup / trim / commit / check."""
 
     @staticmethod
-    def setup(ctx: Context, max_degree: int, seed: int = 0x7121A1) -> CommitterKey:
-        return PedersenCommitment.setup(ctx, max_degree + 1, seed)
+    def setup(ctx: Context, max_degree: int, seed: int = 0x7121A1, domain: Optional[bytes] = None) -> CommitterKey:
+        """`domain`: a transparent key over that domain (PedersenCommitment.setup) instead of the seeded synthetic one"""
+        return PedersenCommitment.setup(ctx, max_degree + 1, seed, domain=domain)
 
     @staticmethod
     def trim(pp: CommitterKey, supported_degree: int) -> Tuple[CommitterKey, CommitterKey]:

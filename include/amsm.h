@@ -64,7 +64,7 @@ enum amsm_status {
   AMSM_E_RCCL = -7,         /* the RCCL collective of a multi-device context failed */
 };
 
-/* flags for amsm_bases_load / amsm_bases_generate */
+/* flags for amsm_bases_load / amsm_bases_generate / amsm_bases_sample */
 enum amsm_bases_flags {
   AMSM_BASES_DEFAULT = 0,      /* library picks: precomputed whenever the table fits (round 4: at every size -- keys of up to
                                   2^15 generators also get the direct-sum table, see amsm_ctx_direct_sum_msms) */
@@ -226,6 +226,24 @@ int amsm_bases_load(amsm_ctx* ctx, const uint64_t* xy_mont, const uint8_t* is_in
  * (ext; ark-poly-commit hashes to the curve -- any fixed set of distinct subgroup points is
  * equivalent for this path). */
 int amsm_bases_generate(amsm_ctx* ctx, uint64_t seed, size_t n, unsigned flags, amsm_bases** out);
+/* Transparent ("nothing up my sleeve") key: out[t] = G_(first + t), where G_i depends only on the context's curve, the caller's
+ * domain string (at most 32 bytes; an empty one is legal) and i, and nobody knows a discrete logarithm between two of them.
+ * Derivation "amsm-sample-v1" (the library's OWN definition, shaped after ark-poly-commit's `sample_generators` -- a BLAKE2s
+ * digest of a protocol name and the index, retried with a counter, times the cofactor -- and NOT byte-compatible with it):
+ *     M(i,j,k) = "amsm-sample-v1" || u8 curve_id || u8 domain_len || domain || u64_le(i) || u32_le(j) || u8(k)
+ *     v = BLAKE2s-256(M(i,j,0)) || BLAKE2s-256(M(i,j,1)) as a little-endian integer (RFC 7693, unkeyed)
+ *     x = v mod 2^bits, bits = bit length of p;  sign = bit 511 of v;  reject x >= p;  reject x^3 + b not a non-zero square
+ *     y = the root with (y > p - y) == sign (canonical integers: the wire format's "larger root" rule)
+ *     G_i = (x, y) on Pallas and Vesta;  G_i = [h](x, y), h = 0x396c8c005555e1568c00aaab0000aaab, on BLS12-381 G1 (reject the identity)
+ * for the first attempt j = 0, 1, ... that is not rejected.  At most 256 attempts are made per index; should an index exhaust them
+ * (probability below 2^-100 per key) the call returns AMSM_E_UNSUPPORTED and creates no key.  Sampled on the device straight into
+ * the resident key (host backend: on the host pool, the same bits).  Flags, error codes, the n >= 2^31 rule and n == 0 as for
+ * amsm_bases_generate; domain_len > 32, a null domain with a non-zero length or an unknown flag bit: AMSM_E_INVALID_ARG.  On a
+ * multi-device context every shard samples its own index range.  The key is an ordinary key (tables, twin, folds, amsm_bases_read).
+ * amsm_bases_generate stays the default of every setup(): its generators have PUBLIC discrete logarithms -- fine for benchmarks and
+ * tests, binding nothing. */
+int amsm_bases_sample(amsm_ctx* ctx, const uint8_t* domain, size_t domain_len, uint64_t first, size_t n, unsigned flags,
+                      amsm_bases** out);
 /* Copy generators [off, off+n) back to the host (affine, Montgomery). */
 int amsm_bases_read(amsm_ctx* ctx, const amsm_bases* bases, size_t off, size_t n, uint64_t* xy_mont, uint8_t* is_inf);
 size_t amsm_bases_len(const amsm_bases* bases);

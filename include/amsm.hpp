@@ -138,6 +138,19 @@ class CommitterKey {
           "amsm_bases_load");
     return k;
   }
+  // Transparent key: generators first .. first + n - 1 of the derivation "amsm-sample-v1" over `domain` (at most 32 bytes), hashed
+  // to the curve on the device, straight into the resident key (amsm_bases_sample)
+  static CommitterKey sample(Context& ctx, const std::string& domain, size_t n, unsigned flags = AMSM_BASES_DEFAULT, uint64_t first = 0) {
+    CommitterKey k(ctx);
+    check(amsm_bases_sample(ctx.get(), reinterpret_cast<const uint8_t*>(domain.data()), domain.size(), first, n, flags, &k.h_),
+          "amsm_bases_sample");
+    return k;
+  }
+  // generators [first, first + count) of that derivation on the host (a setup's hiding generators): affine x|y words, Montgomery
+  static std::vector<uint64_t> sample_points(Context& ctx, const std::string& domain, uint64_t first, size_t count) {
+    CommitterKey k = sample(ctx, domain, count, AMSM_BASES_NO_PRECOMPUTE, first);
+    return k.read(0, count);
+  }
   ~CommitterKey() { amsm_bases_free(h_); }
   CommitterKey(CommitterKey&& o) noexcept : hiding_generator(std::move(o.hiding_generator)), ctx_(o.ctx_), h_(o.h_) {
     o.h_ = nullptr;
@@ -287,6 +300,13 @@ struct PedersenCommitment {
     CommitterKey k(ctx);
     check(amsm_bases_load(ctx.get(), xy.data(), nullptr, n, flags, &k.h_), "amsm_bases_load");
     k.hiding_generator.assign(xy.begin() + (long)(n * w), xy.end());
+    return k;
+  }
+  // setup over a transparent key (amsm_bases_sample): generators G_0 .. G_(n-1) of `domain`, the hiding generator G_n -- the
+  // positions the seeded setup gives them in its stream
+  static CommitterKey setup_transparent(Context& ctx, size_t n, const std::string& domain, unsigned flags = AMSM_BASES_DEFAULT) {
+    CommitterKey k = CommitterKey::sample(ctx, domain, n, flags);
+    k.hiding_generator = CommitterKey::sample_points(ctx, domain, n, 1);
     return k;
   }
   // commit(ck, elems, randomizer): elems Montgomery; randomizer == nullptr <=> None

@@ -160,6 +160,19 @@ struct InnerProductArgPC {
     k.max_degree = n - 1;
     return k;
   }
+  // UniversalParams over a transparent key (amsm_bases_sample): generators G_0 .. G_(n-1) of `domain`, h = G_n, s = G_(n+1)
+  static CommitterKey setup_transparent(Context& ctx, size_t max_degree, const std::string& domain) {
+    size_t n = next_pow2(max_degree + 1), w = 2 * (size_t)ctx.fq_limbs();
+    CommitterKey k;
+    k.comm_key = std::make_shared<amsm::CommitterKey>(amsm::CommitterKey::sample(ctx, domain, n));
+    std::vector<uint64_t> hs = amsm::CommitterKey::sample_points(ctx, domain, n, 2);
+    k.h.xy.assign(hs.begin(), hs.begin() + (long)w);
+    k.h.infinity = false;
+    k.s.xy.assign(hs.begin() + (long)w, hs.end());
+    k.s.infinity = false;
+    k.max_degree = n - 1;
+    return k;
+  }
   static CommitterKey trim(const CommitterKey& pp, size_t supported_degree) {  // ck == vk
     size_t n = next_pow2(supported_degree + 1);
     if (n == pp.comm_key->supported_num_elems()) return pp;

@@ -70,6 +70,9 @@ struct TrivialPC {  // setup / trim / commit / check (ext)
   static CommitterKey setup(Context& ctx, size_t max_degree, uint64_t seed = 0x7121A1) {
     return PedersenCommitment::setup(ctx, max_degree + 1, seed);
   }
+  static CommitterKey setup_transparent(Context& ctx, size_t max_degree, const std::string& domain) {
+    return PedersenCommitment::setup_transparent(ctx, max_degree + 1, domain);
+  }
   static CommitterKey trim(const CommitterKey& pp, size_t supported_degree) {
     std::vector<uint64_t> xy = pp.read(0, supported_degree + 1);
     CommitterKey ck = CommitterKey::load(pp.ctx(), xy, nullptr);

@@ -9,7 +9,9 @@
 //
 //   profile_as <scheme: trivial_pc_as | ipa_pc_as | hp_as | r1cs_nark_as | all> <log_min> <log_max>
 //              [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] [--curve 0|1|2] [--constant] [--uniform] [--no-roundtrip]
-//              [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold]
+//              [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--transparent DOMAIN]
+//   --transparent DOMAIN  every committer key is a transparent one over DOMAIN (amsm.h amsm_bases_sample, the setup_transparent of
+//                the headers) instead of the seeded synthetic key; the Python mirrors take the same key from setup(domain=...).
 //   --cold       no warm-up repetitions (the prove before the timed ones, the decide before the timed one): the CPU legs of
 //                bench.py, where a repetition costs seconds and there are no clocks or caches to warm.
 //   --devices 0,1,2,3  one context over four GPUs (sharded keys; a repeated id puts two shards on one GPU).
@@ -47,6 +49,8 @@ struct Opt {
   uint64_t seed = 0;
   int replicate_log2 = -1;  // --replicate-below
   std::string dump;
+  bool transparent = false;  // --transparent DOMAIN
+  std::string domain;
 };
 
 static Context make_context(const Opt& o) {
@@ -142,7 +146,8 @@ static void profile_hp(const Opt& o, int lg, bool harness_shape) {
   hp_as::Rng zk_rng = harness_shape ? hp_as::Rng([&hr]() { return hr.field(); }) : hp_as::Rng();
   Result r;
   auto t0 = Clock::now();
-  CommitterKey ck = PedersenCommitment::setup(ctx, n, 0x5EED1001ull, AMSM_BASES_PRECOMPUTE);
+  CommitterKey ck = o.transparent ? PedersenCommitment::setup_transparent(ctx, n, o.domain, AMSM_BASES_PRECOMPUTE)
+                                  : PedersenCommitment::setup(ctx, n, 0x5EED1001ull, AMSM_BASES_PRECOMPUTE);
   auto keys = AS::index(ck);
   r.index_ms = ms_since(t0);
   auto make_input = [&](uint64_t seed) {
@@ -223,6 +228,8 @@ static void profile_nark_as(const Opt& o, int lg, bool harness_shape) {
   B.push_back({});
   C.push_back({});
   r1cs_nark::IndexProverKey ipk = Nark::index(ctx, A, B, C, n_inst, n_inst + n_wit, 31337);
+  if (o.transparent)
+    ipk.ck = std::make_unique<CommitterKey>(PedersenCommitment::setup_transparent(ctx, ipk.ck->supported_num_elems(), o.domain));
   auto keys = AS::index(ipk);
   r.index_ms = ms_since(t0);
   uint64_t wit_seed = 0x77A0 + o.seed;
@@ -309,6 +316,8 @@ static void profile_nark(const Opt& o, int lg, bool make_zk) {
   B.push_back({});
   C.push_back({});
   r1cs_nark::IndexProverKey ipk = Nark::index(ctx, A, B, C, n_inst, n_inst + n_wit, 31337);
+  if (o.transparent)
+    ipk.ck = std::make_unique<CommitterKey>(PedersenCommitment::setup_transparent(ctx, ipk.ck->supported_num_elems(), o.domain));
   r.index_ms = ms_since(t0);
   std::vector<Fr> inst{one, ab};
   for (size_t k = 1; k < n_inputs; k++) inst.push_back(a);
@@ -345,7 +354,7 @@ static void profile_ipa(const Opt& o, int lg, bool harness_shape) {
   hp_as::Rng prng([&hr]() { return hr.field(); });
   hp_as::Rng zk_rng = harness_shape ? prng : hp_as::Rng();
   Result r;
-  ipa_pc::CommitterKey pp = Ipa::setup(ctx, degree, 0x1BA5EED);
+  ipa_pc::CommitterKey pp = o.transparent ? Ipa::setup_transparent(ctx, degree, o.domain) : Ipa::setup(ctx, degree, 0x1BA5EED);
   auto t0 = Clock::now();
   auto keys = AS::index(pp, degree);
   r.index_ms = ms_since(t0);
@@ -396,7 +405,7 @@ static void profile_trivial(const Opt& o, int lg, bool harness_shape) {
   const size_t degree = ((size_t)1 << lg) - 1;
   HarnessRng hr(0x7121A1 ^ o.seed);
   Result r;
-  CommitterKey pp = TrivialPC::setup(ctx, degree, 0x7121A1);
+  CommitterKey pp = o.transparent ? TrivialPC::setup_transparent(ctx, degree, o.domain) : TrivialPC::setup(ctx, degree, 0x7121A1);
   CommitterKey ck = TrivialPC::trim(pp, degree);
   auto t0 = Clock::now();
   auto keys = AS::index(pp, degree);
@@ -460,7 +469,7 @@ int main(int argc, char** argv) {
   Opt o;
   if (argc < 4) {
     fprintf(stderr, "usage: %s <scheme|all> <log_min> <log_max> [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] "
-                    "[--curve 0|1|2] [--constant] [--uniform] [--no-roundtrip] [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--replicate-below L]\n", argv[0]);
+                    "[--curve 0|1|2] [--constant] [--uniform] [--no-roundtrip] [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--replicate-below L] [--transparent DOMAIN]\n", argv[0]);
     return 2;
   }
   o.scheme = argv[1];
@@ -486,6 +495,10 @@ int main(int argc, char** argv) {
     else if (a == "--replicate-below" && i + 1 < argc) o.replicate_log2 = atoi(argv[++i]);
     else if (a == "--seed" && i + 1 < argc) o.seed = strtoull(argv[++i], nullptr, 0);
     else if (a == "--dump" && i + 1 < argc) o.dump = argv[++i];
+    else if (a == "--transparent" && i + 1 < argc) {
+      o.transparent = true;
+      o.domain = argv[++i];
+    }
     else {
       fprintf(stderr, "unknown option %s\n", a.c_str());
       return 2;
