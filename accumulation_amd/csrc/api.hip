@@ -28,6 +28,7 @@
 #include "fp.h"
 #include "host_field.h"
 #include "host_glv.h"
+#include "host_points_check.h"
 #include "host_poseidon.h"
 #include "host_sample.h"
 #include "host_serialize.h"

@@ -57,9 +57,38 @@ amsm_bases* bases_new(const amsm_ctx* c, size_t n) {
   }
   return b;
 }
+// amsm_points_check on the host pool: host_points_check.h point_status, the definition itself (a 255-bit multiplication by r per
+// BLS12-381 point).  report: counts of status 1, 2, 3 and the first bad index (n: none); status: n bytes or null
+template <class Fq, class Fr>
+int points_check(const uint64_t* xy, const uint8_t* is_inf, size_t n, uint64_t report[4], uint8_t* status) {
+  constexpr size_t PW = pt_words<Fq>();
+  std::mutex mu;
+  uint64_t cnt[4] = {0, 0, 0, n};
+  par_for(n, 16, [&](size_t lo, size_t hi) {
+    uint64_t mine[4] = {0, 0, 0, n};
+    for (size_t i = lo; i < hi; i++) {
+      const uint8_t st = host::point_status<Fq, Fr>(xy + i * PW, is_inf && is_inf[i]);
+      if (status) status[i] = st;
+      if (st) {
+        mine[st - 1]++;
+        mine[3] = std::min<uint64_t>(mine[3], i);
+      }
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    for (int k = 0; k < 3; k++) cnt[k] += mine[k];
+    cnt[3] = std::min(cnt[3], mine[3]);
+  });
+  memcpy(report, cnt, sizeof(cnt));
+  return AMSM_OK;
+}
 template <class Fq, class Fr>
 int bases_load(amsm_ctx* c, const uint64_t* xy, const uint8_t* is_inf, size_t n, unsigned flags, amsm_bases** out) {
-  if (flags > 31u) return AMSM_E_INVALID_ARG;  // (every flag is a hint here: host keys carry no tables)
+  if (flags > 63u) return AMSM_E_INVALID_ARG;  // (every other flag is a hint here: host keys carry no tables)
+  if (flags & AMSM_BASES_CHECK) {
+    uint64_t report[4];
+    TRY((points_check<Fq, Fr>(xy, is_inf, n, report, nullptr)));
+    if (report[0] | report[1] | report[2]) return AMSM_E_INVALID_POINT;
+  }
   amsm_bases* b = bases_new<Fq>(c, n);
   if (!b) return AMSM_E_OOM;
   constexpr size_t PW = pt_words<Fq>();

@@ -10,6 +10,7 @@ const char* amsm_strerror(int s) {
     case AMSM_E_NO_DEVICE: return "no usable gfx950 device (the host backend is never chosen implicitly: ask for AMSM_DEVICE_HOST)";
     case AMSM_E_SCALAR_RANGE: return "scalar out of range (not a canonical into_repr value)";
     case AMSM_E_RCCL: return "RCCL collective failed";
+    case AMSM_E_INVALID_POINT: return "invalid point (non-canonical, off the curve or outside the prime-order subgroup)";
     default: return "unknown error";
   }
 }
@@ -99,6 +100,7 @@ int amsm_ctx_create(amsm_ctx** out, int curve, int device_id, void* stream) {
   if (const char* e = getenv("AMSM_SHARE_BUCKETS")) c->share_buckets = atoi(e) != 0;
   if (const char* e = getenv("AMSM_FUSED_FOLD")) c->fused_fold = atoi(e) != 0;
   if (const char* e = getenv("AMSM_HOST_HALVES")) c->host_halves = atoi(e) != 0;
+  if (const char* e = getenv("AMSM_SUBGROUP_LADDER")) c->subgroup_ladder = atoi(e) == 2 ? 2 : 1;
   *out = c;
   return AMSM_OK;
 }

@@ -5,8 +5,10 @@ int amsm_bases_load(amsm_ctx* c, const uint64_t* xy, const uint8_t* is_inf, size
   if (c->host_only) return CPU_CALL(c, bases_load, c, xy, is_inf, n, flags, out);
   TRY(bind_device(c));
   if (wants_replicas(c, n, flags))  // (round 6) every device loads the whole key
-    return bases_create_replicated(c, out, [&](size_t, amsm_ctx* cg, amsm_bases** o) {
-      return DISPATCH(cg, bases_load_impl<Fq, Fr>(cg, xy, is_inf, n, flags & ~(unsigned)AMSM_BASES_REPLICATE, o));
+    return bases_create_replicated(c, out, [&](size_t g, amsm_ctx* cg, amsm_bases** o) {
+      // (AMSM_BASES_CHECK: the points are the same on every device -- the primary checks them, once)
+      const unsigned f = flags & ~(unsigned)(AMSM_BASES_REPLICATE | (g ? AMSM_BASES_CHECK : 0));
+      return DISPATCH(cg, bases_load_impl<Fq, Fr>(cg, xy, is_inf, n, f, o));
     });
   flags &= ~(unsigned)AMSM_BASES_REPLICATE;
   if (ctx_shards_keys(c)) {  // shard g copies its own range of the caller's arrays
@@ -19,7 +21,7 @@ int amsm_bases_load(amsm_ctx* c, const uint64_t* xy, const uint8_t* is_inf, size
   return DISPATCH(c, bases_load_impl<Fq, Fr>(c, xy, is_inf, n, flags, out));
 }
 int amsm_bases_generate(amsm_ctx* c, uint64_t seed, size_t n, unsigned flags, amsm_bases** out) {
-  if (!c || !out) return AMSM_E_INVALID_ARG;
+  if (!c || !out || (flags & AMSM_BASES_CHECK)) return AMSM_E_INVALID_ARG;  // (its points are valid by construction)
   if (n >= (1ull << 31)) return AMSM_E_UNSUPPORTED;
   if (c->host_only) return CPU_CALL(c, bases_generate, c, seed, n, flags, out);
   TRY(bind_device(c));
@@ -49,6 +51,19 @@ int amsm_bases_sample(amsm_ctx* c, const uint8_t* domain, size_t domain_len, uin
       return DISPATCH(cg, bases_sample_impl<Fq, Fr>(cg, domain, domain_len, first + lo, cnt, flags, o));
     });
   return DISPATCH(c, bases_sample_impl<Fq, Fr>(c, domain, domain_len, first, n, flags, out));
+}
+int amsm_points_check(amsm_ctx* c, const uint64_t* xy, const uint8_t* is_inf, size_t n, uint64_t* report, uint8_t* status) {
+  if (!c || !report || (n && !xy)) return AMSM_E_INVALID_ARG;
+  if (c->host_only) return CPU_CALL(c, points_check, xy, is_inf, n, report, status);
+  TRY(bind_device(c));  // (a multi-device context: its primary device)
+  return DISPATCH(c, points_check_host_impl<Fq>(c, xy, is_inf, n, report, status));
+}
+int amsm_points_check_device(amsm_ctx* c, const void* d_xy, size_t n, uint64_t* report, void* d_status) {
+  if (!c || !report || (n && !d_xy)) return AMSM_E_INVALID_ARG;
+  if (n >= (1ull << 31)) return AMSM_E_UNSUPPORTED;
+  if (c->host_only) return CPU_CALL(c, points_check, (const uint64_t*)d_xy, nullptr, n, report, (uint8_t*)d_status);
+  TRY(bind_device(c));
+  return DISPATCH(c, points_check_device_impl<Fq>(c, d_xy, n, report, (uint8_t*)d_status));
 }
 int amsm_bases_read(amsm_ctx* c, const amsm_bases* b, size_t off, size_t n, uint64_t* xy, uint8_t* is_inf) {
   if (!c || !b || (n && !xy) || b->curve != c->curve) return AMSM_E_INVALID_ARG;

@@ -237,12 +237,13 @@ int amsm_bases_from_device(amsm_ctx* c, const void* d_xy, size_t n, unsigned fla
   int s = AMSM_OK;
   if (n) {
     if (hipMemcpyAsync(b->d_table, d_xy, n * pb, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) s = AMSM_E_HIP;
+    if (s == AMSM_OK && (flags & AMSM_BASES_CHECK)) s = DISPATCH(c, points_check_for_key<Fq>(c, b->d_table, nullptr, n));
     if (s == AMSM_OK) {
       DISPATCH_DO(c, launch_points_import<Fq>(c->stream, b->d_table, b->d_table, (u32)n));
       if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) s = AMSM_E_HIP;
     }
     if (s == AMSM_OK)
-      s = DISPATCH(c, bases_finish<Fq, Fr>(c, b, flags ? flags : AMSM_BASES_NO_PRECOMPUTE));
+      s = DISPATCH(c, bases_finish<Fq, Fr>(c, b, (flags & ~(unsigned)AMSM_BASES_CHECK) ? flags : AMSM_BASES_NO_PRECOMPUTE));
   }
   if (s != AMSM_OK) {
     (void)hipFree(b->d_table);

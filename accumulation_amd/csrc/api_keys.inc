@@ -227,6 +227,83 @@ int bases_alt(amsm_ctx* ctx, const amsm_bases* b, const amsm_bases** out) {
   return AMSM_OK;
 }
 
+// ---- point validation (include/amsm.h: amsm_points_check; points_check_kernels.h) -------------------------------------------------
+// One run of the kernels over n < 2^32 device points (C-ABI radix; d_inf: their infinity bytes or null): every status byte written,
+// cnt = the three counts and the smallest bad index (0xffffffff: none).  Ends in a synchronise.
+template <class Fq>
+int points_check_run(amsm_ctx* ctx, const u32* d_xy, const uint8_t* d_inf, size_t n, uint8_t* d_status, u32* d_counters,
+                     u32 cnt[PCHK_WORDS]) {
+  hipStream_t st = ctx->stream;
+  HIP_TRY(hipMemsetAsync(d_counters, 0, 4 * PCHK_FIRST_BAD, st));
+  HIP_TRY(hipMemsetAsync(d_counters + PCHK_FIRST_BAD, 0xff, 4, st));
+  launch_points_check<Fq>(st, d_xy, d_inf, (u32)n, d_status, d_counters, host::points_check_consts<Fq>(), ctx->subgroup_ladder);
+  HIP_TRY(hipMemcpyAsync(cnt, d_counters, 4 * PCHK_WORDS, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return AMSM_OK;
+}
+constexpr size_t PCHK_HEAD = 256;  // the counters' place in front of a check's working memory
+inline void points_check_add(uint64_t report[4], const u32 cnt[PCHK_WORDS], size_t off) {
+  for (int k = 0; k < 3; k++) report[k] += cnt[k];
+  if (cnt[PCHK_FIRST_BAD] != 0xffffffffu) report[3] = std::min<uint64_t>(report[3], off + cnt[PCHK_FIRST_BAD]);
+}
+// amsm_points_check_device: working memory (the counters, and the status bytes when the caller wants none) in ctx->check_ws
+template <class Fq>
+int points_check_device_impl(amsm_ctx* ctx, const void* d_xy, size_t n, uint64_t report[4], uint8_t* d_status) {
+  report[0] = report[1] = report[2] = 0;
+  report[3] = n;
+  if (!n) return AMSM_OK;
+  TRY(ensure(ctx->check_ws, PCHK_HEAD + (d_status ? 0 : n)));
+  u32 cnt[PCHK_WORDS];
+  TRY((points_check_run<Fq>(ctx, (const u32*)d_xy, nullptr, n, d_status ? d_status : (uint8_t*)ctx->check_ws.p + PCHK_HEAD,
+                            (u32*)ctx->check_ws.p, cnt)));
+  points_check_add(report, cnt, 0);
+  return AMSM_OK;
+}
+// amsm_points_check: host slices in pieces of 2^18 points (24 MiB of BLS12-381 points: past the size where an upload runs at the
+// link's rate, a quarter of the 2^20 bound of include/amsm.h) through ctx->check_ws (counters | status | flags | points)
+template <class Fq>
+int points_check_host_impl(amsm_ctx* ctx, const uint64_t* xy, const uint8_t* is_inf, size_t n, uint64_t report[4], uint8_t* status) {
+  constexpr size_t PIECE = (size_t)1 << 18;
+  report[0] = report[1] = report[2] = 0;
+  report[3] = n;
+  if (!n) return AMSM_OK;
+  const size_t piece = std::min(n, PIECE), bytes_pt = affine_bytes<Fq>();
+  const size_t flags_at = PCHK_HEAD + ((piece + 255) & ~(size_t)255), pts_at = flags_at + ((piece + 255) & ~(size_t)255);
+  TRY(ensure(ctx->check_ws, pts_at + piece * bytes_pt));
+  char* ws = (char*)ctx->check_ws.p;
+  for (size_t off = 0; off < n; off += piece) {
+    const size_t cnt_pts = std::min(piece, n - off);
+    HIP_TRY(hipMemcpyAsync(ws + pts_at, (const char*)xy + off * bytes_pt, cnt_pts * bytes_pt, hipMemcpyHostToDevice, ctx->stream));
+    if (is_inf) HIP_TRY(hipMemcpyAsync(ws + flags_at, is_inf + off, cnt_pts, hipMemcpyHostToDevice, ctx->stream));
+    u32 cnt[PCHK_WORDS];
+    TRY((points_check_run<Fq>(ctx, (const u32*)(ws + pts_at), is_inf ? (const uint8_t*)(ws + flags_at) : nullptr, cnt_pts,
+                              (uint8_t*)ws + PCHK_HEAD, (u32*)ws, cnt)));
+    if (status) {
+      HIP_TRY(hipMemcpyAsync(status + off, ws + PCHK_HEAD, cnt_pts, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    points_check_add(report, cnt, off);
+  }
+  return AMSM_OK;
+}
+// AMSM_BASES_CHECK: the points a key is about to be made of, where they lie on the device before the import.  Working memory of its
+// own, freed on return (a refused key leaves the context as it found it).  AMSM_E_INVALID_POINT when one is bad.
+template <class Fq>
+int points_check_for_key(amsm_ctx* ctx, const u32* d_xy, const uint8_t* d_inf, size_t n) {
+  if (!n) return AMSM_OK;
+  char* tmp = nullptr;
+  if (hipMalloc((void**)&tmp, PCHK_HEAD + n) != hipSuccess) {
+    (void)hipGetLastError();
+    return AMSM_E_OOM;
+  }
+  u32 cnt[PCHK_WORDS] = {0, 0, 0, 0};
+  int s = points_check_run<Fq>(ctx, d_xy, d_inf, n, (uint8_t*)tmp + PCHK_HEAD, (u32*)tmp, cnt);
+  (void)hipFree(tmp);
+  if (s == AMSM_OK && (cnt[0] | cnt[1] | cnt[2])) s = AMSM_E_INVALID_POINT;
+  return s;
+}
+
 template <class Fq, class Fr>
 int bases_load_impl(amsm_ctx* ctx, const uint64_t* xy, const uint8_t* is_inf, size_t n, unsigned flags,
                     amsm_bases** out) {
@@ -255,8 +332,12 @@ int bases_load_impl(amsm_ctx* ctx, const uint64_t* xy, const uint8_t* is_inf, si
           s = AMSM_E_HIP;
           break;
         }
-        launch_apply_inf<Fq>(ctx->stream, b->d_table, (const uint8_t*)ctx->scalars.p, (u32)n);
       }
+      if (flags & AMSM_BASES_CHECK) {
+        s = points_check_for_key<Fq>(ctx, b->d_table, is_inf ? (const uint8_t*)ctx->scalars.p : nullptr, n);
+        if (s) break;
+      }
+      if (is_inf) launch_apply_inf<Fq>(ctx->stream, b->d_table, (const uint8_t*)ctx->scalars.p, (u32)n);
       launch_points_import<Fq>(ctx->stream, b->d_table, b->d_table, (u32)n);  // C-ABI radix -> device radix
       if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
         s = AMSM_E_HIP;

@@ -242,6 +242,8 @@ struct amsm_ctx {
   // amsm_msm_oneshot (round 6): the generators arrive WITH the call (`multi_scalar_mul(&[G], &[BigInt])`); they are imported range by
   // range into this grow-only buffer (the call's temporary plain key) behind the copy stream, and their infinity flags here
   DevBuf oneshot_table, oneshot_inf;
+  DevBuf check_ws;      // amsm_points_check[_device]: counters, status bytes and the uploaded piece (api_keys.inc)
+  int subgroup_ladder = 1;  // AMSM_SUBGROUP_LADDER: the shape of the BLS12-381 subgroup ladder (points_check_kernels.h; 2: the A/B's other side)
   DevBuf xyzz_scratch;  // unconverted sums of large key folds / precompute levels (launch.h: batch_affine_pays)
   // two-valued device vectors (api_pipeline.inc: msm_two_valued_pass): every scalar is 0 or one value v -> v * (sum of the
   // generators with a non-zero scalar), on its own stream beside the batch's other MSMs.  AMSM_TWO_VALUED=0 turns it off.
@@ -293,7 +295,7 @@ void for_each_slot_buf(S* sl, F&& f) {
 template <class C, class F>  // C: amsm_ctx or const amsm_ctx
 void for_each_ctx_buf(C* c, F&& f) {
   for (auto* b : {&c->scalars, &c->probe_flags, &c->xyzz_scratch, &c->tv_flags, &c->tv_parts, &c->tv_out, &c->shared_buckets[0],
-                  &c->shared_buckets[1], &c->oneshot_table, &c->oneshot_inf, &c->rec_send, &c->rec_recv, &c->stage})
+                  &c->shared_buckets[1], &c->oneshot_table, &c->oneshot_inf, &c->rec_send, &c->rec_recv, &c->stage, &c->check_ws})
     f(*b);
   for (auto& b : c->stage_ring) f(b);
 }

@@ -9,6 +9,7 @@
 #include "host_glv.h"
 #include "launch.h"
 #include "msm_kernels.h"
+#include "points_check_kernels.h"
 #include "sample_kernels.h"
 
 namespace amsm {
@@ -377,6 +378,18 @@ template <>
 void launch_sample_finish<AMSM_FQ>(hipStream_t st, u32* table, u32* jwin, u32 n, u32* counters, const SampleConsts& k, u64 first) {
   if (n == 0) return;
   hipLaunchKernelGGL((k_sample_finish<FQD>), dim3(cdiv_(n, 256)), dim3(256), 0, st, table, jwin, n, counters, k, first);
+}
+template <>
+void launch_points_check<AMSM_FQ>(hipStream_t st, const u32* xy, const uint8_t* is_inf, u32 n, uint8_t* status, u32* counters,
+                                  const PointsCheckConsts& k, int ladder) {
+  if (n == 0) return;
+  hipLaunchKernelGGL((k_points_check_curve<FQD>), dim3(cdiv_(n, 256)), dim3(256), 0, st, xy, is_inf, n, status, counters, k);
+  if constexpr (CurveOf<AMSM_FQ>::type::subgroup_check) {
+    if (ladder == 2)
+      hipLaunchKernelGGL((k_points_check_subgroup<FQD, 2>), dim3(cdiv_(n, 256)), dim3(256), 0, st, xy, is_inf, n, status, counters, k);
+    else
+      hipLaunchKernelGGL((k_points_check_subgroup<FQD, 1>), dim3(cdiv_(n, 256)), dim3(256), 0, st, xy, is_inf, n, status, counters, k);
+  }
 }
 template <>
 bool device_internal_radix<AMSM_FQ>() {

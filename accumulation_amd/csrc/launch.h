@@ -81,6 +81,13 @@ void launch_sample_search(hipStream_t st, u32* table, u32* jwin, const u64* pend
 template <class Fq>
 void launch_sample_finish(hipStream_t st, u32* table, u32* jwin, u32 n, u32* counters, const SampleConsts& k, u64 first);
 
+// Point validation (points_check_kernels.h; include/amsm.h: amsm_points_check): status[i] (n bytes, every one written) of the n points
+// at xy (C-ABI radix; is_inf: their infinity bytes or null), the counts of status 1, 2, 3 added to counters[0..2] and the smallest bad
+// index min-ed into counters[PCHK_FIRST_BAD].  Two launches where the curve needs the subgroup test; ladder: 1 or 2, its shape.
+template <class Fq>
+void launch_points_check(hipStream_t st, const u32* xy, const uint8_t* is_inf, u32 n, uint8_t* status, u32* counters,
+                         const PointsCheckConsts& k, int ladder);
+
 // The device may keep points in an internal Montgomery radix (fpu.h): key tables, partials and buckets are in it,
 // everything the C ABI exposes is not.  import/export convert a point array (src may equal dst); they do
 // nothing when device_internal_radix<Fq>() is false.

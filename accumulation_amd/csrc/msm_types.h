@@ -26,6 +26,16 @@ struct SampleConsts {
 // counters of one sampling call (device words)
 enum { SAMPLE_CNT_PENDING = 0, SAMPLE_CNT_EXHAUSTED = 1, SAMPLE_CNT_IDENTITY = 2, SAMPLE_CNT_WORDS = 3 };
 
+// Arguments of the point validation kernels (points_check_kernels.h), filled by host_points_check.h: points_check_consts.  Field
+// elements are C-ABI Montgomery words.
+struct PointsCheckConsts {
+  u32 b[12];     // the curve's b
+  u32 beta[12];  // BLS12-381: the cube root of unity of the endomorphism phi(x, y) = (beta x, y) with phi(P) = -[z^2]P on G1
+};
+// status byte of one point (include/amsm.h: amsm_points_check) and the device words of one call's report
+enum { POINT_VALID = 0, POINT_NON_CANONICAL = 1, POINT_OFF_CURVE = 2, POINT_OFF_SUBGROUP = 3 };
+enum { PCHK_FIRST_BAD = 3, PCHK_WORDS = 4 };  // words 0..2: the counts of status 1, 2, 3; word 3: atomicMin of the bad indices
+
 constexpr int VEC_MAX = 8;        // max vectors combined in one launch (reference uses 2..4)
 constexpr int HP_MAX_INPUTS = 8;  // max inputs+accumulators of one hp_as t-vector launch (reference tests reach 6)
 

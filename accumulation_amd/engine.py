@@ -36,6 +36,10 @@ def _ptr(a: Optional[np.ndarray]):
     return p
 
 
+def _check_report(report: np.ndarray) -> dict:
+    return {"non_canonical": int(report[0]), "off_curve": int(report[1]), "off_subgroup": int(report[2]), "first_bad": int(report[3])}
+
+
 class Context:
     """One GPU + one HIP stream + workspace (amsm_ctx)."""
 
@@ -138,6 +142,17 @@ class Context:
 
     def synchronize(self):
         ffi.check(self._lib.amsm_ctx_synchronize(self._h), "amsm_ctx_synchronize")
+
+    def check_points(self, xy_mont: np.ndarray, is_inf: Optional[np.ndarray] = None, want_status: bool = False):
+        """Validate host points on the device (amsm_points_check): returns the report {"non_canonical", "off_curve", "off_subgroup",
+        "first_bad"} (first_bad == n: every point is valid) and, with want_status, the status byte of every point."""
+        xy = np.ascontiguousarray(xy_mont, dtype=np.uint64).reshape(-1, 2 * self.fq_limbs)
+        inf = None if is_inf is None else np.ascontiguousarray(is_inf, dtype=np.uint8)
+        report = np.zeros(4, dtype=np.uint64)
+        status = np.zeros(xy.shape[0], dtype=np.uint8) if want_status else None
+        ffi.check(self._lib.amsm_points_check(self._h, _ptr(xy), _ptr(inf), xy.shape[0], _ptr(report), _ptr(status)), "amsm_points_check")
+        rep = _check_report(report)
+        return (rep, status) if want_status else rep
 
     # ---- Fr vectors in HBM ----
     def vector(self, n: int) -> "FrVector":
@@ -354,6 +369,23 @@ class PointVector:
         v.ptr = C.c_void_p(ck.ctx._lib.amsm_bases_device_ptr(ck._h))
         v._view_of = ck
         return v
+
+    def check(self, want_status: bool = False):
+        """Validate these device points where they lie (amsm_points_check_device): the report of Context.check_points and, with
+        want_status, the status bytes (computed on the device, downloaded)."""
+        lib, ctx = self.ctx._lib, self.ctx
+        report = np.zeros(4, dtype=np.uint64)
+        d_status = ctx._alloc(max(self.n, 1)) if want_status else None
+        try:
+            ffi.check(lib.amsm_points_check_device(ctx._h, self.ptr, self.n, _ptr(report), d_status), "amsm_points_check_device")
+            status = np.zeros(self.n, dtype=np.uint8)
+            if want_status and self.n:
+                ffi.check(lib.amsm_dev_download(ctx._h, _ptr(status), d_status, self.n), "amsm_dev_download")
+        finally:
+            if d_status is not None:
+                ctx._release(d_status, max(self.n, 1))
+        rep = _check_report(report)
+        return (rep, status) if want_status else rep
 
     def download(self) -> np.ndarray:
         out = np.empty((self.n, 2 * self.ctx.fq_limbs), dtype=np.uint64)

@@ -26,6 +26,7 @@ AMSM_E_UNSUPPORTED = -4
 AMSM_E_NO_DEVICE = -5
 AMSM_E_SCALAR_RANGE = -6
 AMSM_E_RCCL = -7
+AMSM_E_INVALID_POINT = -8
 
 AMSM_DEVICE_HOST = -1
 
@@ -35,6 +36,7 @@ AMSM_BASES_NO_PRECOMPUTE = 2
 AMSM_BASES_NO_DIRECT_TABLE = 4
 AMSM_BASES_NO_TWIN = 8
 AMSM_BASES_REPLICATE = 16
+AMSM_BASES_CHECK = 32
 
 _vp = C.c_void_p
 _u64p = C.POINTER(C.c_uint64)
@@ -72,6 +74,8 @@ SIGNATURES = {
     "amsm_bases_load": (C.c_int, [_vp, _vp, _vp, _sz, C.c_uint, C.POINTER(_vp)]),
     "amsm_bases_generate": (C.c_int, [_vp, C.c_uint64, _sz, C.c_uint, C.POINTER(_vp)]),
     "amsm_bases_sample": (C.c_int, [_vp, C.c_char_p, _sz, C.c_uint64, _sz, C.c_uint, C.POINTER(_vp)]),
+    "amsm_points_check": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    "amsm_points_check_device": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
     "amsm_bases_read": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "amsm_bases_len": (_sz, [_vp]),
     "amsm_bases_num_shards": (C.c_int, [_vp]),

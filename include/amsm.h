@@ -62,9 +62,10 @@ enum amsm_status {
   AMSM_E_NO_DEVICE = -5,
   AMSM_E_SCALAR_RANGE = -6, /* a scalar was >= 2^255 (not a canonical `into_repr()` value) */
   AMSM_E_RCCL = -7,         /* the RCCL collective of a multi-device context failed */
+  AMSM_E_INVALID_POINT = -8 /* AMSM_BASES_CHECK: a point of the key is non-canonical, off the curve or outside the subgroup */
 };
 
-/* flags for amsm_bases_load / amsm_bases_generate / amsm_bases_sample */
+/* flags for amsm_bases_load / amsm_bases_generate / amsm_bases_sample / amsm_bases_from_device */
 enum amsm_bases_flags {
   AMSM_BASES_DEFAULT = 0,      /* library picks: precomputed whenever the table fits (round 4: at every size -- keys of up to
                                   2^15 generators also get the direct-sum table, see amsm_ctx_direct_sum_msms) */
@@ -86,7 +87,13 @@ enum amsm_bases_flags {
    * per MSM (the latency regime), while `r1cs_nark_as::prove` issues 2-8 independent commitments per round
    * (src/r1cs_nark_as/r1cs_nark/mod.rs:216-218,234-236,251,261; src/r1cs_nark_as/mod.rs:394-410).  Every other entry point uses
    * the primary device's copy, so such a key is accepted wherever a single-device key is (grouped MSMs, the IPA round, key folds). */
-  AMSM_BASES_REPLICATE = 16
+  AMSM_BASES_REPLICATE = 16,
+  /* amsm_bases_load and amsm_bases_from_device only (amsm_bases_generate and amsm_bases_sample refuse it with AMSM_E_INVALID_ARG: their
+   * points are valid by construction): validate the points on the device (amsm_points_check below: its rules) before the import and
+   * the tables.  One invalid point: AMSM_E_INVALID_POINT, no key, *out untouched, everything the call allocated freed.  A valid key is
+   * bit for bit the key the same call makes without the flag.  Multi-device contexts: every shard checks its own range, a replicated
+   * key is checked once (on the primary device); one bad point anywhere fails the whole call, no shard or replica stays allocated. */
+  AMSM_BASES_CHECK = 32
 };
 
 const char* amsm_strerror(int status);
@@ -244,6 +251,26 @@ int amsm_bases_generate(amsm_ctx* ctx, uint64_t seed, size_t n, unsigned flags, 
  * tests, binding nothing. */
 int amsm_bases_sample(amsm_ctx* ctx, const uint8_t* domain, size_t domain_len, uint64_t first, size_t n, unsigned flags,
                       amsm_bases** out);
+/* ---- point validation ------------------------------------------------------------------------------------------------------
+ * Whether caller-supplied points may become a key.  A point is given as the rest of the ABI takes it: x | y in Montgomery form
+ * (ark-ff radix) plus an optional infinity byte.  Each point gets ONE status byte; the first rule that applies wins:
+ *     0  valid             the point is flagged infinite (its coordinates are ignored, as amsm_bases_load ignores them), or it is
+ *                          (0, 0) (the ABI's identity), or none of the rules below applies
+ *     1  non-canonical     the integer held in the limbs of x or of y is >= p (the words as they arrive, before any conversion)
+ *     2  not on the curve  y^2 != x^3 + b
+ *     3  outside the prime-order subgroup   [r]P != O -- BLS12-381 G1 only (cofactor about 2^126); Pallas and Vesta have cofactor 1
+ *                          and never report 3
+ * report[0..2]: the number of points of status 1, 2 and 3; report[3]: the index of the first point whose status is not 0 (n when
+ * there is none).  n == 0: AMSM_OK and an all-zero report.  What `GroupAffine::deserialize`'s checks (ark-ec ^0.2.0, ext) do for
+ * bytes -- amsm_points_deserialize, on the host, one 255-bit multiplication per BLS12-381 point -- for callers who hold limbs, on
+ * the device (accumulation_amd/csrc/points_check_kernels.h; the host backend runs the definition itself on the host pool).
+ * amsm_points_check: host slices (is_inf: n bytes or NULL; status: n bytes on the host or NULL), uploaded in pieces of at most 2^20
+ *     points through workspace that amsm_ctx_trim releases; nothing stays resident and no key is made.
+ * amsm_points_check_device: n < 2^31 points already on the device ((0, 0) = identity: what amsm_bases_from_device takes; d_status:
+ *     n bytes of device memory or NULL).
+ * Both run on the primary device of a multi-device context and return once the report is complete. */
+int amsm_points_check(amsm_ctx* ctx, const uint64_t* xy_mont, const uint8_t* is_inf, size_t n, uint64_t* report, uint8_t* status);
+int amsm_points_check_device(amsm_ctx* ctx, const void* d_xy_mont, size_t n, uint64_t* report, void* d_status);
 /* Copy generators [off, off+n) back to the host (affine, Montgomery). */
 int amsm_bases_read(amsm_ctx* ctx, const amsm_bases* bases, size_t off, size_t n, uint64_t* xy_mont, uint8_t* is_inf);
 size_t amsm_bases_len(const amsm_bases* bases);

@@ -78,6 +78,27 @@ class Context {
   amsm_ctx* get() const { return h_; }
   int fq_limbs() const { return amsm_ctx_fq_limbs(h_); }
   void synchronize() { check(amsm_ctx_synchronize(h_), "amsm_ctx_synchronize"); }
+  // amsm_points_check: may these points become a key?  Counts by status and the first bad index (n: none); status (optional): one
+  // byte per point -- 0 valid, 1 non-canonical, 2 not on the curve, 3 outside the prime-order subgroup.  CommitterKey::load with
+  // AMSM_BASES_CHECK runs the same check and throws Error{AMSM_E_INVALID_POINT} on a bad point.
+  struct PointsReport {
+    uint64_t non_canonical = 0, off_curve = 0, off_subgroup = 0, first_bad = 0;
+    bool all_valid() const { return !(non_canonical | off_curve | off_subgroup); }
+  };
+  PointsReport check_points(const std::vector<uint64_t>& xy_mont, const std::vector<uint8_t>* is_inf = nullptr,
+                            std::vector<uint8_t>* status = nullptr) {
+    const size_t n = xy_mont.size() / (2 * (size_t)fq_limbs());
+    if (status) status->assign(n, 0);
+    uint64_t r[4];
+    check(amsm_points_check(h_, xy_mont.data(), is_inf ? is_inf->data() : nullptr, n, r, status ? status->data() : nullptr),
+          "amsm_points_check");
+    PointsReport rep;
+    rep.non_canonical = r[0];
+    rep.off_curve = r[1];
+    rep.off_subgroup = r[2];
+    rep.first_bad = r[3];
+    return rep;
+  }
 
  private:
   amsm_ctx* h_ = nullptr;
