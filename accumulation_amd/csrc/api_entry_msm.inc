@@ -358,8 +358,10 @@ int amsm_msm_multi_device(amsm_ctx* c, const amsm_bases* b, size_t n_msms, const
   for (size_t v = 0; v < n_msms; v++) split = split || (base_offs[v] <= b->n && split_needed(c, b, std::min(ns[v], b->n - base_offs[v])));
   TRY(DISPATCH_DO(c, {
     std::vector<host::HXYZZ<Fq>> r;
-    if (split) TRY((msm_multi_split_xyzz<Fq, Fr>(c, b, n_msms, base_offs, d_scalars, ns, mont, &r)));
-    else TRY((msm_multi_xyzz<Fq, Fr>(c, b, n_msms, base_offs, d_scalars, ns, mont, &r)));
+    std::vector<MsmJob> vecs;
+    TRY(jobs_from_arrays(b, n_msms, base_offs, d_scalars, ns, mont, &vecs));
+    if (split) TRY((msm_multi_split_xyzz<Fq, Fr>(c, vecs, &r)));
+    else TRY((msm_multi_xyzz<Fq, Fr>(c, vecs, &r)));
     write_affine_batch<Fq>(r, out_xy, out_inf);
   }));
   return AMSM_OK;

@@ -121,8 +121,8 @@ int msm_grouped_partial(amsm_ctx* cg, const amsm_bases* shard_key, size_t key_of
     host::HXYZZ<Fq> s[2];
     stage_begin(cg);
     TRY(prep_fork(cg));
-    TRY((msm_enqueue<Fq, Fr>(cg, &cg->slot[0], shard_key, key_off + (p - pos0), (const char*)d_scalars + (p - pos0) * 32, mid_end - p, mont,
-                             (int)shift)));
+    const MsmJob whole = single_job(shard_key, key_off + (p - pos0), (const char*)d_scalars + (p - pos0) * 32, mid_end - p, mont, (int)shift);
+    TRY((msm_enqueue<Fq, Fr>(cg, &cg->slot[0], whole, Place::LONE)));
     int rc = msm_collect<Fq>(cg, &cg->slot[0], s);
     stage_end(cg);
     if (rc != AMSM_OK) return rc;
@@ -365,7 +365,9 @@ int msm_replicated(amsm_ctx* c, const amsm_bases* key, size_t base_off, const si
           at += lens[i] * 32;
         }
       }
-      TRY((msm_multi_split_xyzz<Fq, Fr>(cg, kg, k, offs.data(), ptrs.data(), lens.data(), mont, &r)));
+      std::vector<MsmJob> vecs;
+      TRY(jobs_from_arrays(kg, k, offs.data(), ptrs.data(), lens.data(), mont, &vecs));
+      TRY((msm_multi_split_xyzz<Fq, Fr>(cg, vecs, &r)));
     }
     for (size_t i = 0; i < k; i++) (*out)[mine[i]] = r[i];
     return AMSM_OK;

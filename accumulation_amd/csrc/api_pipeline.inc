@@ -326,17 +326,88 @@ inline bool bps_geom(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, si
 // bucket sets of 2^18 buckets and more reduce as row / column sums (msm_kernels.h: k_red2_*); smaller sets LOSE with that form
 // (measured: 2^15 buckets, 2^16 pairs 280 -> 212 M pairs/s) and keep the running-sum kernels
 inline bool red2_applies(const amsm_ctx*, const MsmGeom& g) { return g.nb >= (1u << 18) && (g.nb & 1023u) == 0u; }
+// one MSM over generators [off, off + n) of `key` (n already clamped to the key), as the single-MSM entry points describe it
+inline MsmJob single_job(const amsm_bases* key, size_t off, const void* scalars, size_t n, int mont, int group_shift = -1) {
+  MsmJob j;
+  j.key = key;
+  j.off = off;
+  j.n = n;
+  j.scalars = scalars;
+  j.mont = mont;
+  j.group_shift = group_shift;
+  return j;
+}
+
+// Direct sum (round 4; msm_kernels.h k_direct_sum): an MSM over (a range of) a small key that carries the table of digit
+// multiples -- ONE launch of mixed additions with its workgroup trees, the quad fold, the records mirrored to the host: three
+// commands on the caller's stream against the ~14 of the sorted pipelines.  Grouped MSMs (two sums) keep the windowed pipelines.
+inline bool direct_sum_applies(const amsm_ctx* ctx, const amsm_bases* bases, size_t n, int group_shift, bool force_chunked) {
+  return !force_chunked && n >= 1 && choose_pipeline(ctx, bases, n, group_shift, false).pipeline == msel::DIRECT_SUM;
+}
+inline bool direct_sum_applies(const amsm_ctx* ctx, const MsmJob& j) { return direct_sum_applies(ctx, j.key, j.n, j.group_shift, j.force_chunked); }
+// Geometry and every allocation of nv direct sums over one key in one launch on slot `sl` (msm_enqueue_direct_batch; nv = 1 may be
+// grouped); nothing is launched
+struct DirectPlan {
+  u32 m;       // windows per lane
+  u32 blocks;  // workgroups per MSM / per class
+};
+template <class Fq>
+int direct_plan(amsm_ctx* ctx, Slot* sl, const MsmJob* jobs, size_t nv, DirectPlan* out) {
+  if (nv == 0 || nv > (size_t)DS_BATCH) return AMSM_E_INVALID_ARG;
+  const int group_shift = jobs[0].group_shift;  // (a batch shares one scalar form and is not grouped: msm_multi_xyzz)
+  if (group_shift >= 0 && nv != 1) return AMSM_E_INVALID_ARG;
+  size_t n_max = 0;
+  for (size_t v = 0; v < nv; v++) n_max = std::max(n_max, jobs[v].n);
+  MsmGeom g;
+  memset(&g, 0, sizeof(g));
+  g.n = (u32)n_max;
+  g.base_off = (u32)jobs[0].off;
+  g.n_sets = group_shift >= 0 ? 2 : (u32)nv;
+  g.groups = g.n_sets;
+  g.group_shift = group_shift >= 0 ? (u32)group_shift : 0u;
+  g.W = 1;
+  g.c = 4;
+  g.precomp = 1;
+  sl->geom = g;
+  // windows per lane: ~2^16 lanes for one MSM (one workgroup per CU) -- fewer lanes lengthen every lane's chain of additions,
+  // more lengthen the fold's; a batch may fill the three waves per SIMD the kernel's registers allow
+  const size_t lane_cap = nv > 1 ? (size_t)3 << 16 : (size_t)1 << 16;
+  u32 m = 4;
+  while (m < DS_W && (nv * n_max * (size_t)(DS_W / m)) > lane_cap) m <<= 1;
+  const size_t rec = xyzz_bytes<Fq>();
+  const u32 blocks = cdiv((u32)((group_shift >= 0 ? n_max / 2 : n_max) * (DS_W / m)), 256);  // per MSM / per class
+  TRY(ensure(sl->red_out, (size_t)g.n_sets * blocks * rec));
+  TRY(ensure(sl->fold_out, g.n_sets * rec + 64));
+  TRY(ensure_pinned(sl, g.n_sets * rec + 64));
+  if (!sl->ds_flags.p) {  // zeroed once: k_fold_quad leaves the words clear behind every MSM
+    TRY(ensure(sl->ds_flags, 64));
+    HIP_TRY(hipMemsetAsync(sl->ds_flags.p, 0, 64, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  out->m = m;
+  out->blocks = blocks;
+  return AMSM_OK;
+}
+
 // Geometry and EVERY allocation of one MSM on slot `sl`: what can fail for lack of memory fails here, so a caller with side effects
 // to apply first (amsm_ipa_round_fused folds its vectors in place) can reserve before it commits.  Nothing of the MSM is launched;
 // when the slot's arrival counters grow, their zeroing is (a memset, and the caller's stream is synchronised: ensure_red_ticket).
-// *eff = the key the MSM runs over: `bases`, or its 17-bit twin when msm_select.h sends a range of a 20-bit key there.
+// *eff = the key the MSM runs over: job.key, or its 17-bit twin when msm_select.h sends a range of a 20-bit key there.
 template <class Fq>
-int msm_plan(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, size_t base_off, size_t n, int group_shift, bool* short_prep_out,
-             const amsm_bases** eff = nullptr, bool force_chunked = false) {
+int msm_plan(amsm_ctx* ctx, Slot* sl, const MsmJob& job, bool* short_prep_out, const amsm_bases** eff = nullptr) {
+  const amsm_bases* bases = job.key;
+  const size_t base_off = job.off, n = job.n;
+  const int group_shift = job.group_shift;
   const bool quad = true;  // (the reduce partials are sized for the quad kernels: msm_enqueue picks per geometry)
   MsmGeom g;
   const size_t rec = xyzz_bytes<Fq>();
-  const msel::Choice ch = choose_pipeline(ctx, bases, n, group_shift, force_chunked);
+  if (direct_sum_applies(ctx, job)) {  // no prep, no buckets
+    DirectPlan dp;
+    if (eff) *eff = bases;
+    *short_prep_out = false;
+    return direct_plan<Fq>(ctx, sl, &job, 1, &dp);
+  }
+  const msel::Choice ch = choose_pipeline(ctx, bases, n, group_shift, job.force_chunked);
   auto common = [&]() -> int {  // what every sorted pipeline needs behind its accumulation
     u32 red_blocks = cdiv(g.red_threads * (quad ? 4u : 1u), 256);
     if (red2_applies(ctx, g)) {  // the row / column reduction's scratch: here, not in msm_enqueue (plan_only callers allocate FIRST)
@@ -420,62 +491,23 @@ int msm_plan(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, size_t base_off, 
 }
 
 // a bucket-per-lane MSM whose prep found a skewed digit distribution: the same MSM through the chunked pipeline over the
-// key's 17-bit-window twin (msm_collect calls this through Slot::Job::rerun)
+// key's 17-bit-window twin (msm_collect calls this through Slot::rerun)
 template <class Fq, class Fr>
 int msm_rerun_chunked(amsm_ctx* ctx, Slot* sl);
 
-// Direct sum (round 4; msm_kernels.h k_direct_sum): an MSM over (a range of) a small key that carries the table of digit
-// multiples -- ONE launch of mixed additions with its workgroup trees, the quad fold, the records mirrored to the host: three
-// commands on the caller's stream against the ~14 of the sorted pipelines.  Grouped MSMs (two sums) keep the windowed pipelines.
-inline bool direct_sum_applies(const amsm_ctx* ctx, const amsm_bases* bases, size_t n, int group_shift, bool force_chunked) {
-  return !force_chunked && n >= 1 && choose_pipeline(ctx, bases, n, group_shift, false).pipeline == msel::DIRECT_SUM;
-}
-// nv <= DS_BATCH MSMs over the key in ONE launch (the provers' batched commits: eight per r1cs_nark prove) -- the slot then carries
-// nv results, msm_collect hands them out as nv "groups" of one record each.  nv = 1: a single MSM, plain or grouped.
+// nv <= DS_BATCH direct sums over one key in ONE launch (the provers' batched commits: eight per r1cs_nark prove) -- the slot then
+// carries nv results, msm_collect hands them out as nv "groups" of one record each.  nv = 1: a single MSM, plain or grouped.
 template <class Fq, class Fr>
-int msm_enqueue_direct_batch(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, const MsmJob* jobs, size_t nv, int scalars_mont,
-                             int group_shift, bool alone, bool plan_only = false) {
-  if (nv == 0 || nv > (size_t)DS_BATCH || (group_shift >= 0 && nv != 1)) return AMSM_E_INVALID_ARG;
-  size_t n_max = 0;
-  for (size_t v = 0; v < nv; v++) n_max = std::max(n_max, jobs[v].n);
-  MsmGeom g;
-  memset(&g, 0, sizeof(g));
-  g.n = (u32)n_max;
-  g.base_off = (u32)jobs[0].off;
-  g.n_sets = group_shift >= 0 ? 2 : (u32)nv;
-  g.groups = g.n_sets;
-  g.group_shift = group_shift >= 0 ? (u32)group_shift : 0u;
-  g.W = 1;
-  g.c = 4;
-  g.precomp = 1;
-  sl->geom = g;
-  // windows per lane: ~2^16 lanes for one MSM (one workgroup per CU) -- fewer lanes lengthen every lane's chain of additions,
-  // more lengthen the fold's; a batch may fill the three waves per SIMD the kernel's registers allow
-  const size_t lane_cap = nv > 1 ? (size_t)3 << 16 : (size_t)1 << 16;
-  u32 m = 4;
-  while (m < DS_W && (nv * n_max * (size_t)(DS_W / m)) > lane_cap) m <<= 1;
-  const size_t rec = xyzz_bytes<Fq>();
-  const u32 blocks = cdiv((u32)((group_shift >= 0 ? n_max / 2 : n_max) * (DS_W / m)), 256);  // per MSM / per class
-  TRY(ensure(sl->red_out, (size_t)g.n_sets * blocks * rec));
-  TRY(ensure(sl->fold_out, g.n_sets * rec + 64));
-  TRY(ensure_pinned(sl, g.n_sets * rec + 64));
-  if (!sl->ds_flags.p) {  // zeroed once: k_fold_quad leaves the words clear behind every MSM
-    TRY(ensure(sl->ds_flags, 64));
-    HIP_TRY(hipMemsetAsync(sl->ds_flags.p, 0, 64, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-  }
-  if (plan_only) return AMSM_OK;  // (msm_plan: every allocation made, nothing launched)
-  sl->job.bases = bases;
-  sl->job.group_shift = group_shift;
-  sl->job.force_chunked = false;
-  sl->job.base_off = jobs[0].off;
-  sl->job.n = jobs[0].n;
-  sl->job.d_scalars = jobs[0].scalars;
-  sl->job.mont = scalars_mont;
-  sl->job.rerun = &msm_rerun_chunked<Fq, Fr>;
+int msm_enqueue_direct_batch(amsm_ctx* ctx, Slot* sl, const MsmJob* jobs, size_t nv, Place place) {
+  DirectPlan dp;
+  TRY(direct_plan<Fq>(ctx, sl, jobs, nv, &dp));
+  const MsmGeom g = sl->geom;
+  const amsm_bases* bases = jobs[0].key;
+  sl->job = jobs[0];
+  sl->rerun = &msm_rerun_chunked<Fq, Fr>;
   // inside a batch the launches alternate between the two streams every caller has ordered behind the scalars' producers (the
   // caller's and the prep stream: prep_fork, the host-slice uploads): a sum kernel fills one wave per SIMD, two run side by side
-  hipStream_t st = (!alone && (ctx->direct_rr++ & 1u)) ? ctx->s_prep : ctx->stream;
+  hipStream_t st = (place != Place::LONE && (ctx->direct_rr++ & 1u)) ? ctx->s_prep : ctx->stream;
   u32* d_err = (u32*)sl->ds_flags.p;
   for (int i = ST_DIGITS; i <= ST_ACCUM_L0; i++) stage_mark(ctx, sl, i, st);
   if (ctx->profiling) (void)hipEventRecord(sl->ev_prep_end, st);
@@ -486,14 +518,14 @@ int msm_enqueue_direct_batch(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, c
     n32[v] = (u32)jobs[v].n;
     o32[v] = (u32)jobs[v].off;
   }
-  launch_direct_sum<Fq>(st, (const u32*)bases->d_small, (u32)bases->n, (u32)nv, sp, n32, o32, scalars_mont, m, group_shift, d_err,
+  launch_direct_sum<Fq>(st, (const u32*)bases->d_small, (u32)bases->n, (u32)nv, sp, n32, o32, jobs[0].mont, dp.m, jobs[0].group_shift, d_err,
                         (u32*)sl->red_out.p);
   if (ctx->profiling) {
     (void)hipEventRecord(sl->ev_l0_end, st);
     (void)hipEventRecord(sl->ev[ST_ACCUM_L12], st);
     (void)hipEventRecord(sl->ev[ST_REDUCE], st);
   }
-  launch_fold_quad<Fq>(st, g.n_sets, (const u32*)sl->red_out.p, blocks, (u32*)sl->fold_out.p, d_err, (u32*)sl->h_pinned, true);
+  launch_fold_quad<Fq>(st, g.n_sets, (const u32*)sl->red_out.p, dp.blocks, (u32*)sl->fold_out.p, d_err, (u32*)sl->h_pinned, true);
   if (ctx->profiling) (void)hipEventRecord(sl->ev[ST_COUNT], st);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(sl->done, st));
@@ -502,31 +534,24 @@ int msm_enqueue_direct_batch(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, c
   ctx->n_direct += nv;
   return AMSM_OK;
 }
-template <class Fq, class Fr>
-int msm_enqueue_direct(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, size_t base_off, const void* d_scalars, size_t n,
-                       int scalars_mont, int group_shift, bool alone, bool plan_only = false) {
-  const MsmJob job{0, bases, base_off, n, d_scalars};
-  return msm_enqueue_direct_batch<Fq, Fr>(ctx, sl, bases, &job, 1, scalars_mont, group_shift, alone, plan_only);
-}
 
 // Enqueue the whole pipeline for one MSM on slot `sl` (asynchronous); leaves n_sets folded XYZZ records
 // in sl->fold_out and queues their D2H into sl->h_pinned.
 template <class Fq, class Fr>
-int msm_enqueue(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, size_t base_off, const void* d_scalars, size_t n,
-                int scalars_mont, int group_shift = -1, bool exposed_tail = true, bool alone = true, bool force_chunked = false,
-                const Share* share = nullptr) {
+int msm_enqueue(amsm_ctx* ctx, Slot* sl, const MsmJob& job, Place place) {
   // exposed_tail: nothing is queued behind this MSM, so the caller waits for its tail (bucket reduce + fold, a chain of
   // dependent point operations on a few waves): run it on the quad-cooperative kernels (-0.08 ms).  Inside a batch the
   // tail is hidden behind the next MSM's accumulation and the one-lane kernels cost less ALU time (measured: 1 % of the
   // batch throughput).
-  if (direct_sum_applies(ctx, bases, n, group_shift, force_chunked))
-    return msm_enqueue_direct<Fq, Fr>(ctx, sl, bases, base_off, d_scalars, n, scalars_mont, group_shift, alone);
+  const bool exposed_tail = place != Place::BATCH_INNER;
+  if (direct_sum_applies(ctx, job)) return msm_enqueue_direct_batch<Fq, Fr>(ctx, sl, &job, 1, place);
   bool short_prep = false;
-  const amsm_bases* key_in = bases;
-  TRY(msm_plan<Fq>(ctx, sl, bases, base_off, n, group_shift, &short_prep, &bases, force_chunked));
-  for (const auto& r : ctx->skip_ones_ranges)  // (msm_multi_split_xyzz: this vector's unit scalars are summed apart)
-    if ((const char*)d_scalars >= r.first && (const char*)d_scalars + n * 32 <= r.second) sl->geom.skip_ones = 1u;
+  const amsm_bases* bases = nullptr;  // the key the MSM runs over: job.key or its 17-bit twin
+  TRY(msm_plan<Fq>(ctx, sl, job, &short_prep, &bases));
+  sl->geom.skip_ones = job.skip_ones ? 1u : 0u;  // (msm_multi_split_xyzz: this vector's unit scalars are summed apart)
   const MsmGeom g = sl->geom;
+  const void* d_scalars = job.scalars;
+  const int scalars_mont = job.mont;
   // Round 4: a HIDDEN tail (inside a batch) also takes the quad kernels when the bucket table is small.  The tails of
   // consecutive MSMs queue on one stream, and the one-lane kernels are latency chains whatever the bucket count -- accumulate
   // L1 80 + reduce 240 + fold 120 us for the 2^15 buckets of a 2^18-pair MSM whose accumulation takes 300 us (rocprofv3, round
@@ -539,139 +564,193 @@ int msm_enqueue(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, size_t base_of
   const bool quad = exposed_tail || small_table;
   const bool tail_hidden = !exposed_tail && !small_table;
   // one range of a longer MSM over ONE bucket set (struct Share): the caller made the decision with bpl_geom, as msm_plan did
-  const bool shared = share && share->buf >= 0;
+  const Share share = job.share;
+  const bool shared = share.buf >= 0;
   if (shared && !(g.bpl == 1u && g.groups == 1u && g.precomp && g.n_sets == 1u)) return AMSM_E_INVALID_ARG;
-  u32* d_buckets = shared ? (u32*)ctx->shared_buckets[share->buf].p : (u32*)sl->buckets.p;
-  sl->job.share = shared ? *share : Share();
+  u32* d_buckets = shared ? (u32*)ctx->shared_buckets[share.buf].p : (u32*)sl->buckets.p;
+  sl->job = job;
   sl->share_overflow = false;
-  sl->job.bases = key_in;
-  sl->job.group_shift = group_shift;
-  sl->job.force_chunked = force_chunked;
-  sl->job.base_off = base_off;
-  sl->job.n = n;
-  sl->job.d_scalars = d_scalars;
-  sl->job.mont = scalars_mont;
-  sl->job.rerun = &msm_rerun_chunked<Fq, Fr>;
+  sl->rerun = &msm_rerun_chunked<Fq, Fr>;
   // alone: the only MSM of a blocking call.  Nothing can overlap, and every hand-over between streams (an event wait on
   // another hardware queue) costs ~10 us of idle GPU -- three of them in a chain of 0.4 ms at 2^16 (rocprofv3 timeline of an
   // IPA round, round 2): the whole chain goes on the caller's stream.
-  const bool one = alone && exposed_tail;
+  const bool one = place == Place::LONE;
   hipStream_t st = one ? ctx->stream : ctx->s_prep;  // digits / sort / bounds
   hipStream_t sm = ctx->stream;                      // accumulate L0
   const u32 red_blocks = cdiv(g.red_threads * (quad ? 4u : 1u), 256);
   const size_t rec = xyzz_bytes<Fq>();
   u32* d_err = short_prep ? (u32*)sl->prep_small.p : (u32*)sl->misc.p;
   u32* d_heavy_count = d_err + 1;
-  u32* keys_a = (u32*)sl->keys_a.p;
-  u32* keys_b = (u32*)sl->keys_b.p;
   u32* vals_a = (u32*)sl->vals_a.p;
   u32* vals_b = (u32*)sl->vals_b.p;
 
-  if (!short_prep) HIP_TRY(hipMemsetAsync(sl->misc.p, 0, 64, st));
-  stage_mark(ctx, sl, ST_DIGITS, st);
-  if (g.bpl == 2) {
-    // bucket-split pipeline (small / medium MSMs): fill, histogram, scan, scatter, splitting local sort | accumulate | reduce, fold
-    PrepBplBuffers pb;
-    pb.d_small = d_err + 16;
-    pb.part = vals_a;
-    pb.ents_t = vals_b;
-    pb.grp = sl->bpl_grp.p;
-    pb.order = (u32*)sl->bpl_order.p;
-    pb.err = d_err;
-    if (launch_prep_bps<Fr>(st, (const u32*)d_scalars, scalars_mont, g, g.bps_log2_l, pb) != 0) return AMSM_E_HIP;
-    stage_mark(ctx, sl, ST_SORT, st);
-    stage_mark(ctx, sl, ST_BOUNDS, st);
-    ctx->n_bps++;
-  } else if (g.bpl) {
-    // bucket-per-lane pipeline: fill, histogram, scan, wide scatter, transposing local sort | accumulate | reduce, fold
-    PrepBplBuffers pb;
-    pb.d_small = d_err + 16;
-    pb.part = vals_a;
-    pb.ents_t = vals_b;
-    pb.grp = sl->bpl_grp.p;
-    pb.order = (u32*)sl->bpl_order.p;
-    pb.err = d_err;
-    if (launch_prep_bpl<Fr>(st, (const u32*)d_scalars, scalars_mont, g, pb) != 0) return AMSM_E_HIP;
-    stage_mark(ctx, sl, ST_SORT, st);
-    stage_mark(ctx, sl, ST_BOUNDS, st);
-    ctx->n_bpl++;
-  } else if (short_prep) {
-    // short prep chain (prep_kernels.h: 5 dispatches + 2 for skewed inputs); the stage marks keep their names: "sort" = scatter + local sort
-    PrepBuffers pb;
-    pb.d_small = d_err + 16;
-    pb.part = vals_a;
-    pb.vals_sorted = vals_b;
-    pb.start = (u32*)sl->start.p;
-    pb.items = (u32*)sl->items.p;
-    pb.item_off = (u32*)sl->item_off.p;
-    pb.err = d_err;
-    if (launch_prep<Fr>(st, (const u32*)d_scalars, scalars_mont, g, pb) != 0) return AMSM_E_HIP;
-    stage_mark(ctx, sl, ST_SORT, st);
-    stage_mark(ctx, sl, ST_BOUNDS, st);
-  } else {
-  TRY(ensure(sl->keys_a, (size_t)g.E * 4));  // only the rocPRIM chain sorts (key, value) pairs
-  TRY(ensure(sl->keys_b, (size_t)g.E * 4));
-  keys_a = (u32*)sl->keys_a.p;
-  keys_b = (u32*)sl->keys_b.p;
-  const bool keys16 = g.B < 65536u;  // every key (incl. the "digit 0" key B) fits 16 bits
-  launch_digits<Fr>(st, (const u32*)d_scalars, scalars_mont, g, keys_a, keys16, vals_a, d_err);
-  stage_mark(ctx, sl, ST_SORT, st);
-  {
-    int bits = 1;
-    while ((1u << bits) <= g.B) bits++;
-    size_t tmp = 0;
-    if (keys16) {
-      uint16_t* ka = (uint16_t*)keys_a;
-      uint16_t* kb = (uint16_t*)keys_b;
-      HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, ka, kb, vals_a, vals_b, (size_t)g.E, 0u, (unsigned)bits, st));
-      TRY(ensure(sl->sort_tmp, tmp));
-      tmp = sl->sort_tmp.bytes;
-      HIP_TRY(rocprim::radix_sort_pairs(sl->sort_tmp.p, tmp, ka, kb, vals_a, vals_b, (size_t)g.E, 0u, (unsigned)bits, st));
+  // ---- prep, on `st`: the scalars' digits sorted by bucket, by one of four chains ----
+  auto prep = [&]() -> int {
+    if (!short_prep) HIP_TRY(hipMemsetAsync(sl->misc.p, 0, 64, st));
+    stage_mark(ctx, sl, ST_DIGITS, st);
+    if (g.bpl) {
+      // bucket-split pipeline (bpl == 2; small / medium MSMs): fill, histogram, scan, scatter, splitting local sort | accumulate | reduce, fold
+      // bucket-per-lane pipeline (bpl == 1): fill, histogram, scan, wide scatter, transposing local sort | accumulate | reduce, fold
+      PrepBplBuffers pb;
+      pb.d_small = d_err + 16;
+      pb.part = vals_a;
+      pb.ents_t = vals_b;
+      pb.grp = sl->bpl_grp.p;
+      pb.order = (u32*)sl->bpl_order.p;
+      pb.err = d_err;
+      const int rc = g.bpl == 2 ? launch_prep_bps<Fr>(st, (const u32*)d_scalars, scalars_mont, g, g.bps_log2_l, pb)
+                                : launch_prep_bpl<Fr>(st, (const u32*)d_scalars, scalars_mont, g, pb);
+      if (rc != 0) return AMSM_E_HIP;
+      stage_mark(ctx, sl, ST_SORT, st);
+      stage_mark(ctx, sl, ST_BOUNDS, st);
+      (g.bpl == 2 ? ctx->n_bps : ctx->n_bpl)++;
+    } else if (short_prep) {
+      // short prep chain (prep_kernels.h: 5 dispatches + 2 for skewed inputs); the stage marks keep their names: "sort" = scatter + local sort
+      PrepBuffers pb;
+      pb.d_small = d_err + 16;
+      pb.part = vals_a;
+      pb.vals_sorted = vals_b;
+      pb.start = (u32*)sl->start.p;
+      pb.items = (u32*)sl->items.p;
+      pb.item_off = (u32*)sl->item_off.p;
+      pb.err = d_err;
+      if (launch_prep<Fr>(st, (const u32*)d_scalars, scalars_mont, g, pb) != 0) return AMSM_E_HIP;
+      stage_mark(ctx, sl, ST_SORT, st);
+      stage_mark(ctx, sl, ST_BOUNDS, st);
     } else {
-      HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, keys_a, keys_b, vals_a, vals_b, (size_t)g.E, 0u, (unsigned)bits, st));
-      TRY(ensure(sl->sort_tmp, tmp));
-      tmp = sl->sort_tmp.bytes;
-      HIP_TRY(rocprim::radix_sort_pairs(sl->sort_tmp.p, tmp, keys_a, keys_b, vals_a, vals_b, (size_t)g.E, 0u,
-                                        (unsigned)bits, st));
+      TRY(ensure(sl->keys_a, (size_t)g.E * 4));  // only the rocPRIM chain sorts (key, value) pairs
+      TRY(ensure(sl->keys_b, (size_t)g.E * 4));
+      u32* keys_a = (u32*)sl->keys_a.p;
+      u32* keys_b = (u32*)sl->keys_b.p;
+      const bool keys16 = g.B < 65536u;  // every key (incl. the "digit 0" key B) fits 16 bits
+      launch_digits<Fr>(st, (const u32*)d_scalars, scalars_mont, g, keys_a, keys16, vals_a, d_err);
+      stage_mark(ctx, sl, ST_SORT, st);
+      {
+        int bits = 1;
+        while ((1u << bits) <= g.B) bits++;
+        size_t tmp = 0;
+        if (keys16) {
+          uint16_t* ka = (uint16_t*)keys_a;
+          uint16_t* kb = (uint16_t*)keys_b;
+          HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, ka, kb, vals_a, vals_b, (size_t)g.E, 0u, (unsigned)bits, st));
+          TRY(ensure(sl->sort_tmp, tmp));
+          tmp = sl->sort_tmp.bytes;
+          HIP_TRY(rocprim::radix_sort_pairs(sl->sort_tmp.p, tmp, ka, kb, vals_a, vals_b, (size_t)g.E, 0u, (unsigned)bits, st));
+        } else {
+          HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, keys_a, keys_b, vals_a, vals_b, (size_t)g.E, 0u, (unsigned)bits, st));
+          TRY(ensure(sl->sort_tmp, tmp));
+          tmp = sl->sort_tmp.bytes;
+          HIP_TRY(rocprim::radix_sort_pairs(sl->sort_tmp.p, tmp, keys_a, keys_b, vals_a, vals_b, (size_t)g.E, 0u, (unsigned)bits, st));
+        }
+      }
+      stage_mark(ctx, sl, ST_BOUNDS, st);
+      launch_bounds(st, (const void*)keys_b, keys16, vals_b, g, (u32*)sl->start.p, (u32*)sl->items.p);
+      {
+        size_t tmp = 0;
+        HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, (u32*)sl->items.p, (u32*)sl->item_off.p, 0u, (size_t)(g.B + 1),
+                                        rocprim::plus<u32>(), st));
+        TRY(ensure(sl->scan_tmp, tmp));
+        tmp = sl->scan_tmp.bytes;
+        HIP_TRY(rocprim::exclusive_scan(sl->scan_tmp.p, tmp, (u32*)sl->items.p, (u32*)sl->item_off.p, 0u, (size_t)(g.B + 1),
+                                        rocprim::plus<u32>(), st));
+      }
+      AMSM_DBG("pre-l0");
     }
-  }
-  stage_mark(ctx, sl, ST_BOUNDS, st);
-  launch_bounds(st, (const void*)keys_b, keys16, vals_b, g, (u32*)sl->start.p, (u32*)sl->items.p);
-  {
-    size_t tmp = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, (u32*)sl->items.p, (u32*)sl->item_off.p, 0u, (size_t)(g.B + 1),
-                                    rocprim::plus<u32>(), st));
-    TRY(ensure(sl->scan_tmp, tmp));
-    tmp = sl->scan_tmp.bytes;
-    HIP_TRY(rocprim::exclusive_scan(sl->scan_tmp.p, tmp, (u32*)sl->items.p, (u32*)sl->item_off.p, 0u,
-                                    (size_t)(g.B + 1), rocprim::plus<u32>(), st));
-  }
-  AMSM_DBG("pre-l0");
-  }
-  if (ctx->profiling) (void)hipEventRecord(sl->ev_prep_end, st);
-  if (!one) {
-    HIP_TRY(hipEventRecord(sl->prep_done, st));
-    HIP_TRY(hipStreamWaitEvent(sm, sl->prep_done, 0));
-  }
-  if (shared && share->first && ctx->shared_used[share->buf])  // the previous user's tail may still be reading the table
-    HIP_TRY(hipStreamWaitEvent(sm, ctx->shared_free[share->buf], 0));
-  stage_mark(ctx, sl, ST_ACCUM_L0, sm);
-  if (g.bpl == 2)
-    launch_accum_bps<Fq>(sm, (const u32*)bases->d_table, (const u32*)vals_b, sl->bpl_grp.p, (const u32*)sl->bpl_order.p,
-                         prep_bps_partitions(g, g.bps_log2_l) * 16u, g.bps_log2_l, d_err, (u32*)sl->buckets.p);
-  else if (g.bpl) {
-    const u32 n_grp = prep_bpl_partitions(g) * prep_bpl_groups_per_partition(), n_wg = cdiv(n_grp, 4u), cus = (u32)std::max(1, ctx->cu_count);
-    // few workgroups: spread them over all CUs (launch_accum_bpl) -- one per CU up to 1.25 CUs' worth, two up to 2.5
-    const u32 per_cu = n_wg * 4u <= cus * 5u ? 1u : (n_wg * 2u <= cus * 5u ? 2u : 0u);
-    launch_accum_bpl<Fq>(sm, (const u32*)bases->d_table, (const u32*)vals_b, sl->bpl_grp.p, (const u32*)sl->bpl_order.p, n_grp,
-                         prep_bpl_groups_per_partition(), d_err, d_buckets, per_cu, shared && !share->first);
-  }
-  else
-  launch_accum_l0<Fq>(sm, (const u32*)bases->d_table, (const u32*)vals_b, (const u32*)sl->start.p,
-                      (const u32*)sl->item_off.p, g, (u32*)sl->partials.p);
-  AMSM_DBG("l0");
-  if (ctx->profiling) (void)hipEventRecord(sl->ev_l0_end, sm);
-  if (shared && !share->last) {
+    if (ctx->profiling) (void)hipEventRecord(sl->ev_prep_end, st);
+    return AMSM_OK;
+  };
+
+  // ---- accumulate, on `sm` behind the prep: the sorted entries' points into buckets (or into partial records: the chunked pipeline) ----
+  auto accumulate = [&]() -> int {
+    if (!one) {
+      HIP_TRY(hipEventRecord(sl->prep_done, st));
+      HIP_TRY(hipStreamWaitEvent(sm, sl->prep_done, 0));
+    }
+    if (shared && share.first && ctx->shared_used[share.buf])  // the previous user's tail may still be reading the table
+      HIP_TRY(hipStreamWaitEvent(sm, ctx->shared_free[share.buf], 0));
+    stage_mark(ctx, sl, ST_ACCUM_L0, sm);
+    if (g.bpl == 2) {
+      launch_accum_bps<Fq>(sm, (const u32*)bases->d_table, (const u32*)vals_b, sl->bpl_grp.p, (const u32*)sl->bpl_order.p,
+                           prep_bps_partitions(g, g.bps_log2_l) * 16u, g.bps_log2_l, d_err, (u32*)sl->buckets.p);
+    } else if (g.bpl) {
+      const u32 n_grp = prep_bpl_partitions(g) * prep_bpl_groups_per_partition(), n_wg = cdiv(n_grp, 4u), cus = (u32)std::max(1, ctx->cu_count);
+      // few workgroups: spread them over all CUs (launch_accum_bpl) -- one per CU up to 1.25 CUs' worth, two up to 2.5
+      const u32 per_cu = n_wg * 4u <= cus * 5u ? 1u : (n_wg * 2u <= cus * 5u ? 2u : 0u);
+      launch_accum_bpl<Fq>(sm, (const u32*)bases->d_table, (const u32*)vals_b, sl->bpl_grp.p, (const u32*)sl->bpl_order.p, n_grp,
+                           prep_bpl_groups_per_partition(), d_err, d_buckets, per_cu, shared && !share.first);
+    } else {
+      launch_accum_l0<Fq>(sm, (const u32*)bases->d_table, (const u32*)vals_b, (const u32*)sl->start.p, (const u32*)sl->item_off.p, g,
+                          (u32*)sl->partials.p);
+    }
+    AMSM_DBG("l0");
+    if (ctx->profiling) (void)hipEventRecord(sl->ev_l0_end, sm);
+    return AMSM_OK;
+  };
+
+  // ---- tail: partial records into buckets (chunked pipeline only), the bucket reduction, the fold; the records mirrored to the host ----
+  auto tail = [&]() -> int {
+    // The tail the caller waits for -- a blocking call's, or the LAST MSM's of a batch -- stays on the caller's stream, behind its own
+    // accumulation: on the tail stream it would queue behind the previous MSM's tail, which runs beside this accumulation and takes
+    // 2-3x its stand-alone time (rocprofv3, a prover's batch of two 2^18-pair MSMs: the second tail started 127 us after its
+    // accumulation had ended; 1.30 ms for the batch).
+    hipStream_t tl = exposed_tail ? ctx->stream : ctx->s_tail;
+    sl->tail = tl;
+    if (tl != sm) {
+      HIP_TRY(hipEventRecord(sl->l0_done, sm));
+      HIP_TRY(hipStreamWaitEvent(tl, sl->l0_done, 0));
+    }
+    if (ctx->profiling) (void)hipEventRecord(sl->ev[ST_ACCUM_L12], tl);
+    if (!g.bpl) {  // the bucket-per-lane accumulation leaves finished buckets: no partial records to fold
+      launch_accum_l1<Fq>(tl, l1_lanes(g, tail_hidden), (const u32*)sl->partials.p, (const u32*)sl->items.p, (const u32*)sl->item_off.p, g,
+                          (u32*)sl->buckets.p, d_heavy_count, (u32*)sl->heavy.p);
+      AMSM_DBG("l1");
+      launch_accum_l2<Fq>(tl, (const u32*)sl->partials.p, (const u32*)sl->items.p, (const u32*)sl->item_off.p, (const u32*)d_heavy_count,
+                          (const u32*)sl->heavy.p, (u32*)sl->heavy_scratch.p, (u32*)sl->buckets.p);
+      AMSM_DBG("l2");
+    }
+    if (ctx->profiling) (void)hipEventRecord(sl->ev[ST_REDUCE], tl);
+    // round 4: bucket sets of 2^18 buckets and more reduce as row / column sums (msm_kernels.h: k_red2_*; AMSM_RED2=0: the
+    // running-sum kernels; AMSM_RED2=2: every set of 1024 buckets and more).  Measured, same box, batches / blocking call: 2^20
+    // pairs over the 20-bit key 908 -> 928 M pairs/s, 1.409 -> 1.381 ms; smaller sets LOSE (2^15 buckets: 2^16 pairs 280 -> 212,
+    // 2^19 pairs 717 -> 598; a plain key's 16 sets of 2^15: 794 -> 731): with few rows the column sums are all butterfly, and
+    // 1024 + A small multiples cost more than the per-lane ones of a short running-sum kernel
+    u32 fold_n = red_blocks;
+    if (red2_applies(ctx, g)) {  // (scratch sized by msm_plan)
+      fold_n = launch_bucket_reduce2<Fq>(tl, (const u32*)d_buckets, g, quad, quad || !tail_hidden, (u32*)sl->red2_rc.p, (u32*)sl->red_out.p);
+    } else if (quad && ctx->fused_fold) {
+      // round 6: the quad reduction and its fold as ONE launch (the last workgroup of a set to arrive folds the set)
+      launch_bucket_reduce_fold_quad<Fq>(tl, red_blocks, (const u32*)d_buckets, g, (u32*)sl->red_out.p, (u32*)sl->red_ticket.p,
+                                         (u32*)sl->fold_out.p, d_err, (u32*)sl->h_pinned);
+      fold_n = 0;
+    } else if (quad) {
+      launch_bucket_reduce_quad<Fq>(tl, red_blocks, (const u32*)d_buckets, g, (u32*)sl->red_out.p);
+    } else {
+      launch_bucket_reduce<Fq>(tl, red_blocks, (const u32*)d_buckets, g, (u32*)sl->red_out.p);
+    }
+    AMSM_DBG("reduce");
+    u32* h = (u32*)sl->h_pinned;
+    // the records and the flag words go straight to the slot's page-locked block (msm_kernels.h: k_fold's mirror): no copy
+    // command between the fold and the slot's `done` event
+    if (fold_n == 0) {
+    } else if (quad) {
+      launch_fold_quad<Fq>(tl, g.n_sets, (const u32*)sl->red_out.p, fold_n, (u32*)sl->fold_out.p, d_err, h);
+    } else {
+      launch_fold<Fq>(tl, g.n_sets, (const u32*)sl->red_out.p, fold_n, (u32*)sl->fold_out.p, d_err, h);
+    }
+    AMSM_DBG("fold");
+    if (ctx->profiling) (void)hipEventRecord(sl->ev[ST_COUNT], tl);
+    HIP_TRY(hipGetLastError());
+    if (shared) {  // the table may be rewritten once this tail has read it
+      HIP_TRY(hipEventRecord(ctx->shared_free[share.buf], tl));
+      ctx->shared_used[share.buf] = true;
+    }
+    HIP_TRY(hipEventRecord(sl->done, tl));
+    return AMSM_OK;
+  };
+
+  TRY(prep());
+  TRY(accumulate());
+  if (shared && !share.last) {
     // its sums stay in the shared table: no tail.  The slot's flag words reach the host behind the accumulation (the place
     // msm_collect reads them: behind the slot's n_sets records)
     if (ctx->profiling)
@@ -680,64 +759,9 @@ int msm_enqueue(amsm_ctx* ctx, Slot* sl, const amsm_bases* bases, size_t base_of
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sl->done, sm));
     sl->tail = sm;
-    sl->busy = true;
-    return AMSM_OK;
+  } else {
+    TRY(tail());
   }
-  // The tail the caller waits for -- a blocking call's, or the LAST MSM's of a batch -- stays on the caller's stream, behind its own
-  // accumulation: on the tail stream it would queue behind the previous MSM's tail, which runs beside this accumulation and takes
-  // 2-3x its stand-alone time (rocprofv3, a prover's batch of two 2^18-pair MSMs: the second tail started 127 us after its
-  // accumulation had ended; 1.30 ms for the batch).
-  hipStream_t tl = (one || exposed_tail) ? ctx->stream : ctx->s_tail;
-  sl->tail = tl;
-  if (tl != sm) {
-    HIP_TRY(hipEventRecord(sl->l0_done, sm));
-    HIP_TRY(hipStreamWaitEvent(tl, sl->l0_done, 0));
-  }
-  if (ctx->profiling) (void)hipEventRecord(sl->ev[ST_ACCUM_L12], tl);
-  if (!g.bpl) {  // the bucket-per-lane accumulation leaves finished buckets: no partial records to fold
-  launch_accum_l1<Fq>(tl, l1_lanes(g, tail_hidden), (const u32*)sl->partials.p, (const u32*)sl->items.p, (const u32*)sl->item_off.p,
-                      g, (u32*)sl->buckets.p, d_heavy_count, (u32*)sl->heavy.p);
-  AMSM_DBG("l1");
-  launch_accum_l2<Fq>(tl, (const u32*)sl->partials.p, (const u32*)sl->items.p, (const u32*)sl->item_off.p,
-                      (const u32*)d_heavy_count, (const u32*)sl->heavy.p, (u32*)sl->heavy_scratch.p,
-                      (u32*)sl->buckets.p);
-  AMSM_DBG("l2");
-  }
-  if (ctx->profiling) (void)hipEventRecord(sl->ev[ST_REDUCE], tl);
-  // round 4: bucket sets of 2^18 buckets and more reduce as row / column sums (msm_kernels.h: k_red2_*; AMSM_RED2=0: the
-  // running-sum kernels; AMSM_RED2=2: every set of 1024 buckets and more).  Measured, same box, batches / blocking call: 2^20
-  // pairs over the 20-bit key 908 -> 928 M pairs/s, 1.409 -> 1.381 ms; smaller sets LOSE (2^15 buckets: 2^16 pairs 280 -> 212,
-  // 2^19 pairs 717 -> 598; a plain key's 16 sets of 2^15: 794 -> 731): with few rows the column sums are all butterfly, and
-  // 1024 + A small multiples cost more than the per-lane ones of a short running-sum kernel
-  u32 fold_n = red_blocks;
-  if (red2_applies(ctx, g))  // (scratch sized by msm_plan)
-    fold_n = launch_bucket_reduce2<Fq>(tl, (const u32*)d_buckets, g, quad, quad || !tail_hidden, (u32*)sl->red2_rc.p, (u32*)sl->red_out.p);
-  else if (quad && ctx->fused_fold) {
-    // round 6: the quad reduction and its fold as ONE launch (the last workgroup of a set to arrive folds the set)
-    launch_bucket_reduce_fold_quad<Fq>(tl, red_blocks, (const u32*)d_buckets, g, (u32*)sl->red_out.p, (u32*)sl->red_ticket.p,
-                                       (u32*)sl->fold_out.p, d_err, (u32*)sl->h_pinned);
-    fold_n = 0;
-  } else if (quad)
-    launch_bucket_reduce_quad<Fq>(tl, red_blocks, (const u32*)d_buckets, g, (u32*)sl->red_out.p);
-  else
-    launch_bucket_reduce<Fq>(tl, red_blocks, (const u32*)d_buckets, g, (u32*)sl->red_out.p);
-  AMSM_DBG("reduce");
-  u32* h = (u32*)sl->h_pinned;
-  // the records and the flag words go straight to the slot's page-locked block (msm_kernels.h: k_fold's mirror): no copy
-  // command between the fold and the slot's `done` event
-  if (fold_n == 0) {
-  } else if (quad)
-    launch_fold_quad<Fq>(tl, g.n_sets, (const u32*)sl->red_out.p, fold_n, (u32*)sl->fold_out.p, d_err, h);
-  else
-    launch_fold<Fq>(tl, g.n_sets, (const u32*)sl->red_out.p, fold_n, (u32*)sl->fold_out.p, d_err, h);
-  AMSM_DBG("fold");
-  if (ctx->profiling) (void)hipEventRecord(sl->ev[ST_COUNT], tl);
-  HIP_TRY(hipGetLastError());
-  if (shared) {  // the table may be rewritten once this tail has read it
-    HIP_TRY(hipEventRecord(ctx->shared_free[share->buf], tl));
-    ctx->shared_used[share->buf] = true;
-  }
-  HIP_TRY(hipEventRecord(sl->done, tl));
   sl->busy = true;
   return AMSM_OK;
 }
@@ -773,7 +797,7 @@ int msm_collect(amsm_ctx* ctx, Slot* sl, host::HXYZZ<Fq>* out) {
   } else if (g.bpl && *(u32*)((char*)h + g.n_sets * rec + 4)) {  // the prep's overflow flag: skewed digits (SURVEY.md F8)
     if (g.bpl == 2) ctx->n_bps_fallbacks++;
     else ctx->n_bpl_fallbacks++;
-    TRY(sl->job.rerun(ctx, sl));
+    TRY(sl->rerun(ctx, sl));
     return msm_collect<Fq>(ctx, sl, out);  // the re-run is chunked: no second fallback
   }
   // one result per group: Horner over the group's window sums (plain key) or its single record (precomputed key)
@@ -801,10 +825,12 @@ int msm_collect(amsm_ctx* ctx, Slot* sl, host::HXYZZ<Fq>* out) {
 template <class Fq, class Fr>
 int msm_rerun_chunked(amsm_ctx* ctx, Slot* sl) {
   // the same MSM with the chunked pipeline forced: over the key itself, or over its 17-bit twin when the key was precomputed
-  // for 20-bit windows (msm_plan resolves that).  On the per-stage streams (alone = false): other MSMs of a batch may be in
+  // for 20-bit windows (msm_plan resolves that).  On the per-stage streams (not Place::LONE): other MSMs of a batch may be in
   // flight, and the prep stream has already been ordered behind the producers of the scalars by the call's prep_fork.
-  const Slot::Job j = sl->job;
-  return msm_enqueue<Fq, Fr>(ctx, sl, j.bases, j.base_off, j.d_scalars, j.n, j.mont, j.group_shift, true, false, true);
+  MsmJob j = sl->job;
+  j.force_chunked = true;
+  j.share = Share();
+  return msm_enqueue<Fq, Fr>(ctx, sl, j, Place::BATCH_LAST);
 }
 
 void stage_begin(amsm_ctx* ctx) {
@@ -875,8 +901,7 @@ int arm_shared_set(amsm_ctx* ctx, std::vector<MsmJob>& jobs, size_t first, size_
 }
 
 template <class Fq, class Fr>
-int msm_multi_split_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const size_t* offs, const void* const* d_scalars,
-                         const size_t* ns, int scalars_mont, std::vector<host::HXYZZ<Fq>>* out);
+int msm_multi_split_xyzz(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, std::vector<host::HXYZZ<Fq>>* out);
 // Large MSMs run as ranges of the key (msm_select.h: range_of)
 inline size_t split_chunk(const amsm_ctx* ctx, const amsm_bases* bases) {
   const size_t r = msel::range_of(key_desc(bases), ~(size_t)0 >> 1, switches_of(ctx));
@@ -904,31 +929,40 @@ inline DigitWalk key_walk(const amsm_bases* b) {
   }
   return d;
 }
+// Identical vectors (a prover commits to the same accumulator vector more than once; bench.py cycles four) are probed once:
+// first[j] = the first i <= j with the scalars and the length of vecs[cand[j]] (an index into cand).  The offset into the key is
+// deliberately not compared: what the probes say depends on the scalars, their number and the key alone.
+inline std::vector<size_t> first_identical(const std::vector<MsmJob>& vecs, const std::vector<size_t>& cand) {
+  std::vector<size_t> first(cand.size());
+  for (size_t j = 0; j < cand.size(); j++) {
+    first[j] = j;
+    for (size_t i = 0; i < j; i++)
+      if (vecs[cand[i]].scalars == vecs[cand[j]].scalars && vecs[cand[i]].n == vecs[cand[j]].n) {
+        first[j] = first[i];
+        break;
+      }
+  }
+  return first;
+}
 template <class Fr>
-int bpl_probe_enqueue(amsm_ctx* ctx, size_t k, const void* const* d_scalars, const size_t* lens, int mont, DigitWalk walk, size_t min_len,
-                      SkewProbe* p, const u32* const* tv_words = nullptr) {  // tv_words[v]: vector v's two-valued probe words, if probed
-  p->k = k;
+int bpl_probe_enqueue(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, DigitWalk walk, size_t min_len, SkewProbe* p,
+                      const u32* const* tv_words = nullptr) {  // tv_words[v]: vector v's two-valued probe words, if probed
+  p->k = vecs.size();
   p->cand.clear();
-  for (size_t v = 0; v < k; v++)
-    if (lens[v] >= min_len) p->cand.push_back(v);
+  for (size_t v = 0; v < vecs.size(); v++)
+    if (vecs[v].n >= min_len) p->cand.push_back(v);
   const std::vector<size_t>& cand = p->cand;
   if (cand.empty()) return AMSM_OK;
   TRY(ensure(ctx->probe_flags, std::max<size_t>(cand.size() * 4, 4096)));
   Slot* aux = &ctx->slot[N_SLOTS - 1];
   TRY(ensure_pinned(aux, std::max<size_t>(cand.size() * 4, 4096) + 64));
   HIP_TRY(hipMemsetAsync(ctx->probe_flags.p, 0, cand.size() * 4, ctx->stream));
-  // identical vectors (a prover commits to the same accumulator vector more than once; bench.py cycles four) are probed once
-  p->first.assign(cand.size(), 0);
+  p->first = first_identical(vecs, cand);
   for (size_t j = 0; j < cand.size(); j++) {
-    p->first[j] = j;
-    for (size_t i = 0; i < j; i++)
-      if (d_scalars[cand[i]] == d_scalars[cand[j]] && lens[cand[i]] == lens[cand[j]]) {
-        p->first[j] = p->first[i];
-        break;
-      }
+    const MsmJob& vec = vecs[cand[j]];
     if (p->first[j] == j)
-      launch_skew_probe<Fr>(ctx->stream, (const u32*)d_scalars[cand[j]], mont, (u32)std::min<size_t>(lens[cand[j]], 0xffffffffu),
-                            walk, (u32*)ctx->probe_flags.p + j, tv_words ? tv_words[cand[j]] : nullptr);
+      launch_skew_probe<Fr>(ctx->stream, (const u32*)vec.scalars, vec.mont, (u32)std::min<size_t>(vec.n, 0xffffffffu), walk,
+                            (u32*)ctx->probe_flags.p + j, tv_words ? tv_words[cand[j]] : nullptr);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(aux->h_pinned, ctx->probe_flags.p, cand.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -941,24 +975,21 @@ inline void bpl_probe_finish(amsm_ctx* ctx, const SkewProbe& p, std::vector<uint
   for (size_t j = 0; j < p.cand.size(); j++) (*skew)[p.cand[j]] = f[p.first[j]] ? 1 : 0;
 }
 template <class Fr>
-int bpl_probe_device(amsm_ctx* ctx, size_t k, const void* const* d_scalars, const size_t* lens, int mont, std::vector<uint8_t>* skew,
-                     DigitWalk walk, size_t min_len) {
+int bpl_probe_device(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, std::vector<uint8_t>* skew, DigitWalk walk, size_t min_len) {
   SkewProbe p;
-  TRY(bpl_probe_enqueue<Fr>(ctx, k, d_scalars, lens, mont, walk, min_len, &p, nullptr));
+  TRY(bpl_probe_enqueue<Fr>(ctx, vecs, walk, min_len, &p, nullptr));
   if (!p.cand.empty()) HIP_TRY(hipStreamSynchronize(ctx->stream));
   bpl_probe_finish(ctx, p, skew);
   return AMSM_OK;
 }
-// Which skew probe (if any) the pipelines behind msm_multi_split_impl want for this key: 0 none, else the window width / the
-// shortest vector probed.  (msm_multi_split_xyzz launches it together with the two-valued probe: one synchronisation for both.)
-inline int skew_probe_params(const amsm_ctx* ctx, const amsm_bases* bases, const std::vector<size_t>& lens, size_t* min_len,
-                             DigitWalk* walk) {
+// Which skew probe (if any) the pipelines behind msm_multi_split_impl want for these vectors over `bases`: 0 none, else the window
+// width / the shortest vector probed.  (msm_multi_split_xyzz launches it together with the two-valued probe: one synchronisation for both.)
+inline int skew_probe_params(const amsm_ctx* ctx, const amsm_bases* bases, const std::vector<MsmJob>& vecs, size_t* min_len, DigitWalk* walk) {
   if (!ctx->bpl_probe || !bases->precomp) return 0;
   *walk = key_walk(bases);
-  size_t shortest = ~(size_t)0;
-  for (size_t l : lens)
-    if (l && msel::wants_skew_probe(key_desc(bases), l, switches_of(ctx))) shortest = std::min(shortest, l);
-  if (shortest == ~(size_t)0) return 0;
+  bool want = false;
+  for (const MsmJob& v : vecs) want = want || (v.n && msel::wants_skew_probe(key_desc(bases), v.n, switches_of(ctx)));
+  if (!want) return 0;
   *min_len = bases->bpl ? bpl_min_pairs(bases) : BPS_MIN_PAIRS;
   return bases->c;
 }
@@ -999,11 +1030,45 @@ bool bpl_probe_host(const uint64_t* scalars, size_t n, int mont, DigitWalk dw, s
   return false;
 }
 
+// The callers' k vectors over windows of one key -- vector v: generators [offs[v], offs[v] + ns[v]) and the scalars at scalars[v] -- as
+// a job list: one job per vector, owner = its index, lengths clamped to the key
+inline int jobs_from_arrays(const amsm_bases* bases, size_t k, const size_t* offs, const void* const* scalars, const size_t* ns, int mont,
+                            std::vector<MsmJob>* jobs) {
+  jobs->assign(k, MsmJob());
+  for (size_t v = 0; v < k; v++) {
+    if (offs[v] > bases->n) return AMSM_E_INVALID_ARG;
+    MsmJob& j = (*jobs)[v];
+    j.owner = v;
+    j.key = bases;
+    j.off = offs[v];
+    j.n = std::min(ns[v], bases->n - offs[v]);
+    j.scalars = scalars[v];
+    j.mont = mont;
+  }
+  return AMSM_OK;
+}
+// (*out)[jobs[j].owner] += part[j]
+template <class Fq>
+void add_by_owner(const std::vector<MsmJob>& jobs, const std::vector<host::HXYZZ<Fq>>& part, std::vector<host::HXYZZ<Fq>>* out) {
+  for (size_t j = 0; j < jobs.size(); j++) (*out)[jobs[j].owner] = host::hx_add<Fq>((*out)[jobs[j].owner], part[j]);
+}
+// Vector `vec` in ranges of `step` pairs, appended to *jobs (an empty vector: one empty job); every range inherits the vector's fields
+inline void cut_into_ranges(const MsmJob& vec, size_t step, std::vector<MsmJob>* jobs) {
+  size_t lo = 0;
+  do {
+    jobs->push_back(vec);
+    MsmJob& r = jobs->back();
+    r.off = vec.off + lo;
+    r.n = std::min(step, vec.n - lo);
+    r.scalars = (const char*)vec.scalars + lo * 32;
+    lo += step;
+  } while (lo < vec.n);
+}
+
 // The jobs' MSMs through the slot ring; (*part)[j] = job j's result (the identity for an empty job, and for every range of a shared
 // bucket set but its last), (*overflow)[j] = 1 where job j, a range of a shared set, found skewed digits (run_ring)
 template <class Fq, class Fr>
-int msm_multi_xyzz(amsm_ctx* ctx, const std::vector<MsmJob>& jobs, int scalars_mont, std::vector<host::HXYZZ<Fq>>* part,
-                   std::vector<uint8_t>* overflow = nullptr) {
+int msm_multi_xyzz(amsm_ctx* ctx, const std::vector<MsmJob>& jobs, std::vector<host::HXYZZ<Fq>>* part, std::vector<uint8_t>* overflow = nullptr) {
   const size_t k = jobs.size();
   part->assign(k, host::hx_inf<Fq>());
   if (overflow) overflow->assign(k, 0);
@@ -1011,14 +1076,14 @@ int msm_multi_xyzz(amsm_ctx* ctx, const std::vector<MsmJob>& jobs, int scalars_m
   // every MSM a direct sum over this key (small keys: DESIGN.md 4.2g): up to DS_BATCH of them per launch
   const amsm_bases* key = jobs[0].key;
   bool all_direct = k >= 2;
-  for (const MsmJob& j : jobs) all_direct = all_direct && j.n > 0 && j.key == key && direct_sum_applies(ctx, key, j.n, -1, j.force_chunked);
+  for (const MsmJob& j : jobs) all_direct = all_direct && j.key == key && j.mont == jobs[0].mont && j.group_shift < 0 && direct_sum_applies(ctx, j);
   if (all_direct) {
-    const bool one_launch = k <= (size_t)DS_BATCH;
+    const size_t n_launches = (k + DS_BATCH - 1) / DS_BATCH;
     return run_ring(
-        ctx, (k + DS_BATCH - 1) / DS_BATCH,
+        ctx, n_launches,
         [&](size_t b, Slot* sl) {
           const size_t v0 = b * DS_BATCH;
-          return msm_enqueue_direct_batch<Fq, Fr>(ctx, sl, key, &jobs[v0], std::min<size_t>(DS_BATCH, k - v0), scalars_mont, -1, one_launch);
+          return msm_enqueue_direct_batch<Fq, Fr>(ctx, sl, &jobs[v0], std::min<size_t>(DS_BATCH, k - v0), place_of(b, n_launches));
         },
         [&](size_t b, Slot* sl) { return msm_collect<Fq>(ctx, sl, &(*part)[b * DS_BATCH]); });
   }
@@ -1027,34 +1092,19 @@ int msm_multi_xyzz(amsm_ctx* ctx, const std::vector<MsmJob>& jobs, int scalars_m
     if (jobs[j].n) live.push_back(j);
   std::vector<uint8_t> ovf(live.size(), 0);
   const int rc = run_ring(
-      ctx, live.size(),
-      [&](size_t i, Slot* sl) {
-        const MsmJob& j = jobs[live[i]];
-        return msm_enqueue<Fq, Fr>(ctx, sl, j.key, j.off, j.scalars, j.n, scalars_mont, -1, i + 1 == live.size(), live.size() == 1,
-                                   j.force_chunked, &j.share);
-      },
+      ctx, live.size(), [&](size_t i, Slot* sl) { return msm_enqueue<Fq, Fr>(ctx, sl, jobs[live[i]], place_of(i, live.size())); },
       [&](size_t i, Slot* sl) { return msm_collect<Fq>(ctx, sl, &(*part)[live[i]]); }, ovf.data());
   if (overflow)
     for (size_t i = 0; i < live.size(); i++) (*overflow)[live[i]] = ovf[i];
   return rc;
 }
-// k MSMs over windows of one key, one job each: MSM v uses generators [offs[v], offs[v] + ns[v]) and the scalars at d_scalars[v]
-template <class Fq, class Fr>
-int msm_multi_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const size_t* offs, const void* const* d_scalars, const size_t* ns,
-                   int scalars_mont, std::vector<host::HXYZZ<Fq>>* out) {
-  std::vector<MsmJob> jobs(k);
-  for (size_t v = 0; v < k; v++) {
-    if (offs[v] > bases->n) return AMSM_E_INVALID_ARG;
-    jobs[v] = MsmJob{v, bases, offs[v], std::min(ns[v], bases->n - offs[v]), d_scalars[v]};
-  }
-  return msm_multi_xyzz<Fq, Fr>(ctx, jobs, scalars_mont, out);
-}
 
 template <class Fq, class Fr>
 int msm_device_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, const void* d_scalars, size_t n,
                     int scalars_mont, host::HXYZZ<Fq>* out) {
-  if (base_off > bases->n) return AMSM_E_INVALID_ARG;
-  n = std::min(n, bases->n - base_off);
+  std::vector<MsmJob> vec;
+  TRY(jobs_from_arrays(bases, 1, &base_off, &d_scalars, &n, scalars_mont, &vec));
+  n = vec[0].n;
   if (n == 0) {
     *out = host::hx_inf<Fq>();
     return AMSM_OK;
@@ -1063,8 +1113,7 @@ int msm_device_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, con
   // (long single vectors are worth the two-valued probe's synchronisation: ~20 us against 0.45 ms and up)
   const bool split = split_needed(ctx, bases, n) || probe_wanted || (ctx->two_valued && n >= ((size_t)1 << 17));  // windows of the key / the probes
   std::vector<host::HXYZZ<Fq>> r;
-  TRY((split ? msm_multi_split_xyzz<Fq, Fr>(ctx, bases, 1, &base_off, &d_scalars, &n, scalars_mont, &r)
-             : msm_multi_xyzz<Fq, Fr>(ctx, bases, 1, &base_off, &d_scalars, &n, scalars_mont, &r)));
+  TRY((split ? msm_multi_split_xyzz<Fq, Fr>(ctx, vec, &r) : msm_multi_xyzz<Fq, Fr>(ctx, vec, &r)));
   *out = r[0];
   return AMSM_OK;
 }
@@ -1076,39 +1125,42 @@ int msm_device_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, con
 // whatever the key's length; the extra bucket reductions hide behind the next window's accumulation, and a blocking call of
 // that size becomes a pipeline.  Measured (batches, M pairs/s, whole / 2^20 windows / 2^21 windows): 2^22 815 / 822 / 845,
 // 2^23 507 / 841 / 868, 2^24 725 / 848 / 874; the workspace of a 2^24-pair MSM drops from 25.6 GB to 1.5 GB.
+// vecs: one job per caller vector, all over one key and in one scalar form (vecs[0].mont); (*out)[i] = the MSM of vecs[i]
 template <class Fq, class Fr>
-int msm_multi_split_impl(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const size_t* offs, const void* const* d_scalars,
-                         const size_t* ns, int scalars_mont, std::vector<host::HXYZZ<Fq>>* out,
+int msm_multi_split_impl(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, std::vector<host::HXYZZ<Fq>>* out,
                          const std::vector<uint8_t>* pre_skew = nullptr);  // the skew probe's verdicts when the caller ran it
 
 // Two-valued vectors first (vec_kernels.h k_tv_probe: EXACT test on the device, one launch per distinct vector, one copy and
 // one synchronisation per call): such a vector's MSM is v * (sum of the generators with a non-zero scalar) -- k_tv_sum + k_fold
 // on a stream of their own beside the other MSMs of the call, the scalar multiplication on the host when they are collected.
 // Everything else goes on as before.  Vectors below 2^14 pairs are not probed (their whole MSM is a few launches).
+// Four steps, plain data between them: tv_probe (launch the probes, one synchronisation), msel::classify (msm_select.h),
+// tv_launch_sums (the sums on their own stream), then msm_multi_split_xyzz runs the rest and finishes on the host.
 constexpr size_t TV_MIN_PAIRS = (size_t)1 << 14;
-// unit scalars among the probe's 1024 samples from which a vector's ones are summed apart (0.8 %: below the skew probe's 24 of
-// 1024 in one bin, so what that probe no longer sees is always taken out)
-constexpr u32 TV_ONES_MIN_SAMPLES = 8;
+constexpr u32 TV_ONES_MIN_SAMPLES = msel::TV_ONES_MIN_SAMPLES;
+constexpr size_t TV_PW = TV_PROBE_WORDS, TV_PB = TV_PROBE_WORDS * 4;  // probe block per vector: words, bytes
+template <class Fq>
+constexpr size_t tv_exc_rec() { return (8 + 2 * Fq::W) * 4; }  // one exception record: the scalar, its generator
+template <class Fq>
+constexpr size_t tv_exc_bytes() { return TV_EXC_SLOTS * tv_exc_rec<Fq>(); }  // exception records per vector
+
+struct TvProbes {  // step (a): what the probes said, read back behind one synchronisation
+  std::vector<const u32*> host_words, dev_words;  // per vector: its probe block in ctx->tv_pinned / on the device (null: not probed)
+  std::vector<uint8_t> skew;                       // the skew probe's verdict per vector
+  bool have_skew = false;                          // ... if the pipelines want one for this key
+  size_t cap_vecs = 0;                             // probe blocks the first half of ctx->tv_flags has room for
+  u32 one_words[8] = {1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // the unit scalar as these vectors store it
+};
+// (a) the two-valued probe of the vectors `cand`, and the skew probe the pipelines would run anyway riding on its synchronisation
 template <class Fq, class Fr>
-int msm_multi_split_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const size_t* offs, const void* const* d_scalars,
-                         const size_t* ns, int scalars_mont, std::vector<host::HXYZZ<Fq>>* out) {
-  std::vector<size_t> cand;
-  std::vector<size_t> lens(k, 0);
-  for (size_t v = 0; v < k; v++) {
-    if (offs[v] > bases->n) return AMSM_E_INVALID_ARG;
-    lens[v] = std::min(ns[v], bases->n - offs[v]);
-    // (also over a direct-sum key: at 2^14 pairs a two-valued vector's MSM is still 4x cheaper than the sum of 2^14 * 60 points)
-    if (ctx->two_valued && lens[v] >= TV_MIN_PAIRS && lens[v] < (1ull << 32) && offs[v] + lens[v] < (1ull << 32)) cand.push_back(v);
-  }
-  if (cand.empty()) return msm_multi_split_impl<Fq, Fr>(ctx, bases, k, offs, d_scalars, ns, scalars_mont, out);
+int tv_probe(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, const std::vector<size_t>& cand, TvProbes* p) {
+  const amsm_bases* bases = vecs[0].key;
   const size_t rec = xyzz_bytes<Fq>();
-  constexpr size_t PW = TV_PROBE_WORDS, PB = TV_PROBE_WORDS * 4;                  // probe block per vector
-  constexpr size_t EXC_REC = (8 + 2 * Fq::W) * 4, EXC_B = TV_EXC_SLOTS * EXC_REC;  // exception records per vector
   // (sized for at least 256 vectors: a first call with more vectors than any before it would otherwise re-allocate device and
   // page-locked memory -- milliseconds -- inside that call: the first 20-MSM batch after a 3-MSM warm-up ran 1.8 ms longer)
-  const size_t cap_vecs = std::max<size_t>(cand.size(), 256);
-  TRY(ensure(ctx->tv_flags, 2 * cap_vecs * PB));  // (second half: the synthetic probe blocks of the unit-scalar sums below)
-  const size_t pin_need = 2 * cap_vecs * (PB + rec + EXC_B) + 64;
+  p->cap_vecs = std::max<size_t>(cand.size(), 256);
+  TRY(ensure(ctx->tv_flags, 2 * p->cap_vecs * TV_PB));  // (second half: the synthetic probe blocks of the unit-scalar sums)
+  const size_t pin_need = 2 * p->cap_vecs * (TV_PB + rec + tv_exc_bytes<Fq>()) + 64;
   if (ctx->tv_pinned_bytes < pin_need) {
     if (ctx->tv_pinned) (void)hipHostFree(ctx->tv_pinned);
     ctx->tv_pinned = nullptr;
@@ -1119,172 +1171,152 @@ int msm_multi_split_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const
     }
     ctx->tv_pinned_bytes = pin_need * 2;
   }
-  HIP_TRY(hipMemsetAsync(ctx->tv_flags.p, 0, cand.size() * PB, ctx->stream));
-  u32 one_words[8] = {1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // the unit scalar as these vectors store it
-  if (scalars_mont)
-    for (int i = 0; i < 8; i++) one_words[i] = Fr::one(i);
-  std::vector<size_t> first(cand.size());  // identical vectors are probed once
+  HIP_TRY(hipMemsetAsync(ctx->tv_flags.p, 0, cand.size() * TV_PB, ctx->stream));
+  if (vecs[0].mont)
+    for (int i = 0; i < 8; i++) p->one_words[i] = Fr::one(i);
+  const std::vector<size_t> first = first_identical(vecs, cand);
+  p->host_words.assign(vecs.size(), nullptr);
+  p->dev_words.assign(vecs.size(), nullptr);
   for (size_t j = 0; j < cand.size(); j++) {
-    first[j] = j;
-    for (size_t i = 0; i < j; i++)
-      if (d_scalars[cand[i]] == d_scalars[cand[j]] && lens[cand[i]] == lens[cand[j]]) {
-        first[j] = first[i];
-        break;
-      }
-    if (first[j] == j)
-      launch_tv_probe(ctx->stream, (const u32*)d_scalars[cand[j]], (u32)lens[cand[j]], (u32*)ctx->tv_flags.p + PW * j, one_words);
+    const MsmJob& vec = vecs[cand[j]];
+    if (first[j] == j) launch_tv_probe(ctx->stream, (const u32*)vec.scalars, (u32)vec.n, (u32*)ctx->tv_flags.p + TV_PW * j, p->one_words);
+    p->host_words[cand[j]] = (const u32*)ctx->tv_pinned + TV_PW * first[j];
+    p->dev_words[cand[j]] = (const u32*)ctx->tv_flags.p + TV_PW * first[j];
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(ctx->tv_pinned, ctx->tv_flags.p, cand.size() * PB, hipMemcpyDeviceToHost, ctx->stream));
-  // the skew probe the pipelines would run anyway rides on the same synchronisation
+  HIP_TRY(hipMemcpyAsync(ctx->tv_pinned, ctx->tv_flags.p, cand.size() * TV_PB, hipMemcpyDeviceToHost, ctx->stream));
   SkewProbe sp;
   size_t sp_min = 0;
   DigitWalk sp_walk;
-  const int sp_c = skew_probe_params(ctx, bases, lens, &sp_min, &sp_walk);
-  sp_walk.skip_ones = bases->bpl ? 0u : 1u;  // (numerous unit scalars are summed apart below -- not over a 20-bit table --; a few skew nothing)
-  std::vector<const u32*> tv_words(k, nullptr);
-  for (size_t j = 0; j < cand.size(); j++) tv_words[cand[j]] = (const u32*)ctx->tv_flags.p + PW * first[j];
-  if (sp_c) TRY(bpl_probe_enqueue<Fr>(ctx, k, d_scalars, lens.data(), scalars_mont, sp_walk, sp_min, &sp, tv_words.data()));
+  p->have_skew = skew_probe_params(ctx, bases, vecs, &sp_min, &sp_walk) != 0;
+  sp_walk.skip_ones = bases->bpl ? 0u : 1u;  // (numerous unit scalars are summed apart -- not over a 20-bit table --; a few skew nothing)
+  if (p->have_skew) TRY(bpl_probe_enqueue<Fr>(ctx, vecs, sp_walk, sp_min, &sp, p->dev_words.data()));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  std::vector<uint8_t> skew_all;
-  if (sp_c) bpl_probe_finish(ctx, sp, &skew_all);
-  const std::vector<uint8_t>* pre = sp_c ? &skew_all : nullptr;
-  const u32* fl = (const u32*)ctx->tv_pinned;
-  std::vector<size_t> tv;  // indices into cand
-  std::vector<uint8_t> is_tv(k, 0);
-  for (size_t j = 0; j < cand.size(); j++) {
-    const u32* f = fl + PW * first[j];
-    if (f[0] == 0u && f[1] == 1u) {
-      // canonical-form vectors (mont == 0) whose value is 2^255 or more keep to the windowed pipelines, which report such
-      // scalars (include/amsm.h: AMSM_E_SCALAR_RANGE) -- the shortcut must not turn that error into a result; values in
-      // [r, 2^255) give the same point either way.  The vector's exceptions, a handful of scalars read back after the sum, are
-      // checked when they arrive (tv_bad below)
-      if (!scalars_mont && (f[8 + 7] >> 31) != 0u) continue;
-      tv.push_back(j);
-      is_tv[cand[j]] = 1;
-    } else if (f[0] == 0u && f[2] == 1u) {  // every scalar zero: the identity, nothing to launch
-      is_tv[cand[j]] = 2;
-      ctx->n_two_valued++;
-    }
-  }
-  // Round 5: vectors with a SHARE of unit scalars (the boolean wires of an R1CS witness; ark-ec's multi_scalar_mul adds their bases
-  // directly) are not two-valued, but all their ones would land in bucket 1 of the lowest window (measured, M pairs/s in batches:
-  // 2^18 pairs with 10 % booleans 2.2x slower than uniform, a plain 2^20 key 2.3x).  Their generators are summed apart -- the
-  // two-valued machinery with v = 1, no scalar multiplication -- and the pipelines skip those scalars (MsmGeom::skip_ones).
-  // (not where the MSM would be a direct sum: that form has no buckets to skew)
-  const size_t n_tv_proper = tv.size();
-  std::vector<uint8_t> has_ones(k, 0);
-  for (size_t j = 0; j < cand.size(); j++) {
-    const size_t v = cand[j];
-    if (is_tv[v]) continue;
-    const u32* f = fl + PW * first[j];
-    // (nor over a 20-bit table: the skew probe sends such a vector to the chunked pipeline over the key's 17-bit twin, where the
-    // ones cost little -- 2^20 pairs in batches, 10 / 50 / 90 % booleans: 1.21 / 0.85 / 0.52 ms against 1.13 / 0.91 / 0.75 with the
-    // separate sum, a uniform vector 1.10)
-    if (f[4] >= TV_ONES_MIN_SAMPLES && !bases->bpl && !direct_sum_applies(ctx, bases, lens[v], -1, false)) has_ones[v] = 1;
-  }
-  // msm_enqueue recognises such a vector by where its scalars lie (amsm_ctx::skip_ones_ranges): no vector of this call that keeps
-  // its unit scalars in the pipelines may share memory with one that does not (views into one another's buffers) -- those give up
-  for (bool changed = true; changed;) {
-    changed = false;
-    for (size_t v = 0; v < k; v++) {
-      if (!has_ones[v]) continue;
-      const char *a0 = (const char*)d_scalars[v], *a1 = a0 + lens[v] * 32;
-      for (size_t u = 0; u < k && has_ones[v]; u++) {
-        if (u == v || has_ones[u] || is_tv[u] || lens[u] == 0) continue;
-        const char *b0 = (const char*)d_scalars[u], *b1 = b0 + lens[u] * 32;
-        if (a0 < b1 && b0 < a1) has_ones[v] = 0, changed = true;
-      }
-    }
-  }
-  for (size_t j = 0; j < cand.size(); j++)
-    if (has_ones[cand[j]]) tv.push_back(j);
-  bool any_zero = false;
-  for (size_t v = 0; v < k; v++) any_zero = any_zero || is_tv[v] == 2;
-  if (tv.empty() && !any_zero) return msm_multi_split_impl<Fq, Fr>(ctx, bases, k, offs, d_scalars, ns, scalars_mont, out, pre);
+  if (p->have_skew) bpl_probe_finish(ctx, sp, &p->skew);
+  return AMSM_OK;
+}
+
+struct TvSums {  // step (c): the sums in flight on ctx->s_tv
+  std::vector<size_t> tv;               // the vectors summed there: the two-valued ones, then (from n_proper on) those whose ones are summed apart
+  size_t n_proper = 0;
+  std::vector<std::array<u64, 4>> vals;  // per sum: the value v its result is multiplied by (canonical form)
+  std::vector<u32> n_exc;                // ... and how many exception records come with it
+};
+// (c) the sums of the generators under a two-valued vector's value / under the unit scalars of a vector that sums them apart -- the
+// two-valued machinery with v = 1, no scalar multiplication --: k_tv_sum + the fold on s_tv, the records' copy queued behind them
+template <class Fq, class Fr>
+int tv_launch_sums(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, const TvProbes& p, const std::vector<uint8_t>& verdict, TvSums* s) {
+  const size_t rec = xyzz_bytes<Fq>(), EXC_B = tv_exc_bytes<Fq>();
+  for (size_t v = 0; v < vecs.size(); v++)
+    if (verdict[v] == msel::V_TWO_VALUED) s->tv.push_back(v);
+  s->n_proper = s->tv.size();
+  for (size_t v = 0; v < vecs.size(); v++)
+    if (verdict[v] == msel::V_ONES_APART) s->tv.push_back(v);
+  const std::vector<size_t>& tv = s->tv;
+  if (tv.empty()) return AMSM_OK;
   // the scalars' values, before the pinned block is reused for the records
-  std::vector<std::array<u64, 4>> vals(tv.size());
-  std::vector<u32> n_exc(tv.size());
+  s->vals.resize(tv.size());
+  s->n_exc.resize(tv.size());
   for (size_t t = 0; t < tv.size(); t++) {
-    if (t >= n_tv_proper) {  // a unit-scalar sum: v = 1, no exceptions
-      vals[t] = {1, 0, 0, 0};
-      n_exc[t] = 0;
+    if (t >= s->n_proper) {  // a unit-scalar sum: v = 1, no exceptions
+      s->vals[t] = {1, 0, 0, 0};
+      s->n_exc[t] = 0;
       continue;
     }
-    host::HFe<Fr> s;
-    memcpy(s.v, fl + PW * first[tv[t]] + 8, 32);
-    if (scalars_mont) s = host::h_from_mont<Fr>(s);
-    memcpy(vals[t].data(), s.v, 32);
-    n_exc[t] = std::min<u32>(fl[PW * first[tv[t]] + 3], TV_EXC_SLOTS);
+    const u32* f = p.host_words[tv[t]];
+    host::HFe<Fr> val;
+    memcpy(val.v, f + msel::TVW_VALUE, 32);
+    if (vecs[0].mont) val = host::h_from_mont<Fr>(val);
+    memcpy(s->vals[t].data(), val.v, 32);
+    s->n_exc[t] = std::min<u32>(f[msel::TVW_N_EXC], TV_EXC_SLOTS);
   }
-  if (!tv.empty()) {
   if (!ctx->s_tv) HIP_TRY(hipStreamCreateWithFlags(&ctx->s_tv, hipStreamNonBlocking));
   if (!ctx->tv_done) HIP_TRY(hipEventCreateWithFlags(&ctx->tv_done, hipEventDisableTiming));
   // one launch per group of up to 8 vectors (and one fold for the group): every sum is a short latency-bound chain
   size_t max_len = 0;
-  for (size_t t = 0; t < tv.size(); t++) max_len = std::max(max_len, lens[cand[tv[t]]]);
+  for (size_t t = 0; t < tv.size(); t++) max_len = std::max(max_len, vecs[tv[t]].n);
   // 8 points per lane (r1cs_nark_as 2^18 harness-zk prove with 8 / 4 / 2: 2.04 / 2.15 / 2.46 ms: fewer records to fold wins)
   const u32 blocks = (u32)std::max<size_t>(32, std::min<size_t>(1024, max_len / (256 * 8)));
   TRY(ensure(ctx->tv_parts, tv.size() * (size_t)blocks * rec));
   TRY(ensure(ctx->tv_out, tv.size() * (rec + EXC_B) + 64));  // the folded records, then the vectors' exception records
   u32* d_exc = (u32*)((char*)ctx->tv_out.p + tv.size() * rec);
   // the unit-scalar sums read a synthetic probe block each: [3] = 0 exceptions, [8..15] = the unit as stored
-  std::vector<u32> ones_blocks((tv.size() - n_tv_proper) * PW, 0u);
-  for (size_t t = n_tv_proper; t < tv.size(); t++) memcpy(&ones_blocks[(t - n_tv_proper) * PW + 8], one_words, 32);
-  u32* d_ones_blocks = (u32*)ctx->tv_flags.p + PW * cap_vecs;
+  std::vector<u32> ones_blocks((tv.size() - s->n_proper) * TV_PW, 0u);
+  for (size_t t = s->n_proper; t < tv.size(); t++) memcpy(&ones_blocks[(t - s->n_proper) * TV_PW + msel::TVW_VALUE], p.one_words, 32);
+  u32* d_ones_blocks = (u32*)ctx->tv_flags.p + TV_PW * p.cap_vecs;
   if (!ones_blocks.empty()) {
     HIP_TRY(hipMemcpyAsync(d_ones_blocks, ones_blocks.data(), ones_blocks.size() * 4, hipMemcpyHostToDevice, ctx->s_tv));
     HIP_TRY(hipStreamSynchronize(ctx->s_tv));  // (pageable source: must outlive the copy; only vectors with unit scalars pay this)
   }
-  // (the caller's stream was synchronised above: the scalars are complete, s_tv needs no event to see them)
+  // (the caller's stream was synchronised by tv_probe: the scalars are complete, s_tv needs no event to see them)
   for (size_t t0 = 0; t0 < tv.size(); t0 += 8) {
     const u32 nv = (u32)std::min<size_t>(8, tv.size() - t0);
     const u32 *ptrs[8], *probes[8];
     u32 nn[8], oo[8];
     for (u32 j = 0; j < nv; j++) {
-      const size_t v = cand[tv[t0 + j]];
-      ptrs[j] = (const u32*)d_scalars[v];
-      probes[j] = t0 + j >= n_tv_proper ? d_ones_blocks + PW * (t0 + j - n_tv_proper) : (const u32*)ctx->tv_flags.p + PW * first[tv[t0 + j]];
-      nn[j] = (u32)lens[v];
-      oo[j] = (u32)offs[v];
+      const MsmJob& vec = vecs[tv[t0 + j]];
+      ptrs[j] = (const u32*)vec.scalars;
+      probes[j] = t0 + j >= s->n_proper ? d_ones_blocks + TV_PW * (t0 + j - s->n_proper) : p.dev_words[tv[t0 + j]];
+      nn[j] = (u32)vec.n;
+      oo[j] = (u32)vec.off;
     }
     u32* parts = (u32*)((char*)ctx->tv_parts.p + t0 * (size_t)blocks * rec);
-    launch_tv_sum<Fq>(ctx->s_tv, (const u32*)bases->d_table, nv, ptrs, probes, nn, oo, blocks, parts,
-                      (u32*)((char*)d_exc + t0 * EXC_B));
+    launch_tv_sum<Fq>(ctx->s_tv, (const u32*)vecs[0].key->d_table, nv, ptrs, probes, nn, oo, blocks, parts, (u32*)((char*)d_exc + t0 * EXC_B));
     // (the caller waits for these sums: the quad-cooperative fold, as for an exposed MSM tail)
     launch_fold_quad<Fq>(ctx->s_tv, nv, parts, blocks, (u32*)((char*)ctx->tv_out.p + t0 * rec), nullptr);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(ctx->tv_pinned, ctx->tv_out.p, tv.size() * (rec + EXC_B), hipMemcpyDeviceToHost, ctx->s_tv));
   HIP_TRY(hipEventRecord(ctx->tv_done, ctx->s_tv));
+  return AMSM_OK;
+}
+
+template <class Fq, class Fr>
+int msm_multi_split_xyzz(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, std::vector<host::HXYZZ<Fq>>* out) {
+  const size_t k = vecs.size();
+  std::vector<size_t> cand;
+  // (also over a direct-sum key: at 2^14 pairs a two-valued vector's MSM is still 4x cheaper than the sum of 2^14 * 60 points)
+  for (size_t v = 0; v < k; v++)
+    if (ctx->two_valued && vecs[v].n >= TV_MIN_PAIRS && vecs[v].n < (1ull << 32) && vecs[v].off + vecs[v].n < (1ull << 32)) cand.push_back(v);
+  if (cand.empty()) return msm_multi_split_impl<Fq, Fr>(ctx, vecs, out);
+  const amsm_bases* bases = vecs[0].key;
+  const int scalars_mont = vecs[0].mont;
+  const size_t rec = xyzz_bytes<Fq>(), EXC_REC = tv_exc_rec<Fq>(), EXC_B = tv_exc_bytes<Fq>();
+  TvProbes probes;
+  TRY((tv_probe<Fq, Fr>(ctx, vecs, cand, &probes)));
+  const std::vector<uint8_t>* pre = probes.have_skew ? &probes.skew : nullptr;
+  // (b) two-valued, all zero, unit scalars summed apart, or as it is: msm_select.h
+  std::vector<uint8_t> verdict(k);
+  {
+    std::vector<msel::VecProbe> vp(k);
+    for (size_t v = 0; v < k; v++) vp[v] = msel::VecProbe{probes.host_words[v], vecs[v].n, (const char*)vecs[v].scalars};
+    msel::classify(vp.data(), k, scalars_mont != 0, key_desc(bases), switches_of(ctx), verdict.data());
   }
-  // the other vectors through the regular pipelines meanwhile
-  std::vector<size_t> r_offs, r_ns, r_owner;
-  std::vector<const void*> r_ptrs;
+  bool any_apart = false;  // vectors that skip the pipelines, or run them without their ones
+  for (size_t v = 0; v < k; v++) {
+    any_apart = any_apart || verdict[v] != msel::V_REGULAR;
+    if (verdict[v] == msel::V_ALL_ZERO) ctx->n_two_valued++;
+  }
+  if (!any_apart) return msm_multi_split_impl<Fq, Fr>(ctx, vecs, out, pre);
+  TvSums sums;
+  TRY((tv_launch_sums<Fq, Fr>(ctx, vecs, probes, verdict, &sums)));
+  const std::vector<size_t>& tv = sums.tv;
+  // (d) the other vectors through the regular pipelines meanwhile
+  std::vector<MsmJob> rest;
   std::vector<uint8_t> r_skew;
   for (size_t v = 0; v < k; v++)
-    if (!is_tv[v]) {
-      r_offs.push_back(offs[v]);
-      r_ns.push_back(ns[v]);
-      r_ptrs.push_back(d_scalars[v]);
-      r_owner.push_back(v);
-      if (pre) r_skew.push_back(skew_all[v]);
+    if (verdict[v] == msel::V_REGULAR || verdict[v] == msel::V_ONES_APART) {
+      rest.push_back(vecs[v]);
+      rest.back().owner = v;
+      rest.back().skip_ones = verdict[v] == msel::V_ONES_APART;
+      if (pre) r_skew.push_back(probes.skew[v]);
     }
   out->assign(k, host::hx_inf<Fq>());
   int rc = AMSM_OK;
-  ctx->skip_ones_ranges.clear();
-  for (size_t v = 0; v < k; v++)
-    if (has_ones[v]) ctx->skip_ones_ranges.push_back({(const char*)d_scalars[v], (const char*)d_scalars[v] + lens[v] * 32});
-  struct ClearSkip {  // (every return below)
-    amsm_ctx* c;
-    ~ClearSkip() { c->skip_ones_ranges.clear(); }
-  } clear_skip{ctx};
-  if (!r_owner.empty()) {
+  if (!rest.empty()) {
     std::vector<host::HXYZZ<Fq>> part;
-    rc = msm_multi_split_impl<Fq, Fr>(ctx, bases, r_owner.size(), r_offs.data(), r_ptrs.data(), r_ns.data(), scalars_mont, &part,
-                                      pre ? &r_skew : nullptr);
-    if (rc == AMSM_OK)
-      for (size_t j = 0; j < r_owner.size(); j++) (*out)[r_owner[j]] = part[j];
+    rc = msm_multi_split_impl<Fq, Fr>(ctx, rest, &part, pre ? &r_skew : nullptr);
+    if (rc == AMSM_OK) add_by_owner<Fq>(rest, part, out);
   }
   if (!tv.empty()) HIP_TRY(hipEventSynchronize(ctx->tv_done));
   if (rc != AMSM_OK || tv.empty()) return rc;
@@ -1292,8 +1324,8 @@ int msm_multi_split_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const
   // whose verdict on such scalars stands (an error where the key's windows cannot take them, the integer's multiple where they can)
   std::vector<uint8_t> tv_bad(tv.size(), 0);
   auto finish = [&](size_t t) {
-    if (t >= n_tv_proper) {  // the sum of the generators under unit scalars joins what the pipelines computed without them
-      const size_t v = cand[tv[t]];
+    const size_t v = tv[t];
+    if (t >= sums.n_proper) {  // the sum of the generators under unit scalars joins what the pipelines computed without them
       (*out)[v] = host::hx_add<Fq>((*out)[v], host::hx_from_device<Fq>((const u32*)((const char*)ctx->tv_pinned + t * rec)));
       return;
     }
@@ -1301,9 +1333,9 @@ int msm_multi_split_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const
     host::HXYZZ<Fq> pts[1 + TV_EXC_SLOTS];
     u64 ks[1 + TV_EXC_SLOTS][4];
     pts[0] = host::hx_from_device<Fq>((const u32*)((const char*)ctx->tv_pinned + t * rec));
-    memcpy(ks[0], vals[t].data(), 32);
+    memcpy(ks[0], sums.vals[t].data(), 32);
     const char* ex = (const char*)ctx->tv_pinned + tv.size() * rec + t * EXC_B;
-    for (u32 e = 0; e < n_exc[t]; e++) {
+    for (u32 e = 0; e < sums.n_exc[t]; e++) {
       host::HFe<Fr> s;
       memcpy(s.v, ex + e * EXC_REC, 32);
       if (scalars_mont) s = host::h_from_mont<Fr>(s);
@@ -1313,76 +1345,63 @@ int msm_multi_split_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const
       memcpy(xy, ex + e * EXC_REC + 32, sizeof(xy));
       pts[1 + e] = host::hx_from_affine<Fq>(xy, false);
     }
-    (*out)[cand[tv[t]]] = host::hx_lincomb<Fq>(pts, ks, 1 + n_exc[t], nullptr);
+    (*out)[v] = host::hx_lincomb<Fq>(pts, ks, 1 + sums.n_exc[t], nullptr);
   };
   if (tv.size() > 1) HostPool::get().run(tv.size(), finish);
   else finish(0);
-  std::vector<size_t> b_offs, b_ns, b_owner;
-  std::vector<const void*> b_ptrs;
+  std::vector<MsmJob> bad;
   for (size_t t = 0; t < tv.size(); t++) {
-    if (t >= n_tv_proper) {
-      ctx->n_ones_split++;
-      continue;
+    if (t >= sums.n_proper) ctx->n_ones_split++;
+    else if (!tv_bad[t]) ctx->n_two_valued++;
+    else {
+      bad.push_back(vecs[tv[t]]);
+      bad.back().owner = tv[t];
     }
-    if (!tv_bad[t]) {
-      ctx->n_two_valued++;
-      continue;
-    }
-    const size_t v = cand[tv[t]];
-    b_offs.push_back(offs[v]);
-    b_ns.push_back(ns[v]);
-    b_ptrs.push_back(d_scalars[v]);
-    b_owner.push_back(v);
   }
-  if (!b_owner.empty()) {
+  if (!bad.empty()) {
     std::vector<host::HXYZZ<Fq>> part;
-    TRY((msm_multi_split_impl<Fq, Fr>(ctx, bases, b_owner.size(), b_offs.data(), b_ptrs.data(), b_ns.data(), scalars_mont, &part)));
-    for (size_t j = 0; j < b_owner.size(); j++) (*out)[b_owner[j]] = part[j];
+    TRY((msm_multi_split_impl<Fq, Fr>(ctx, bad, &part)));
+    for (size_t j = 0; j < bad.size(); j++) (*out)[bad[j].owner] = part[j];  // (in place of the shortcut's result)
   }
   return AMSM_OK;
 }
 
 template <class Fq, class Fr>
-int msm_multi_split_impl(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const size_t* offs, const void* const* d_scalars,
-                         const size_t* ns, int scalars_mont, std::vector<host::HXYZZ<Fq>>* out, const std::vector<uint8_t>* pre_skew) {
-  // vectors whose digits look skewed skip the bucket-per-lane attempt: they run chunked over the twin key, cut by ITS rule
-  std::vector<uint8_t> skew(k, 0);
-  const amsm_bases* alt = nullptr;
-  std::vector<size_t> lens(k);
-  for (size_t v = 0; v < k; v++) lens[v] = offs[v] <= bases->n ? std::min(ns[v], bases->n - offs[v]) : 0;
+int msm_multi_split_impl(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, std::vector<host::HXYZZ<Fq>>* out, const std::vector<uint8_t>* pre_skew) {
+  const size_t k = vecs.size();
+  out->assign(k, host::hx_inf<Fq>());
+  if (k == 0) return AMSM_OK;
+  const amsm_bases* bases = vecs[0].key;
   // the digit probe's verdicts (msm_select.h: wants_skew_probe): a skewed vector over a 20-bit key runs chunked over the twin, cut by
   // ITS rule; over any other precomputed key it runs chunked over the same key (force_chunked)
-  bool probed = false;
-  if (ctx->bpl_probe && bases->precomp) {
-    bool want = false;
-    for (size_t v = 0; v < k; v++) want = want || (lens[v] && msel::wants_skew_probe(key_desc(bases), lens[v], switches_of(ctx)));
-    if (want) {
-      if (pre_skew) skew = *pre_skew;
-      else TRY(bpl_probe_device<Fr>(ctx, k, d_scalars, lens.data(), scalars_mont, &skew, key_walk(bases), bases->bpl ? bpl_min_pairs(bases) : BPS_MIN_PAIRS));
-      probed = true;
-    }
+  std::vector<uint8_t> skew(k, 0);
+  const amsm_bases* alt = nullptr;
+  size_t probe_min = 0;
+  DigitWalk probe_walk;
+  const bool probed = skew_probe_params(ctx, bases, vecs, &probe_min, &probe_walk) != 0;
+  if (probed) {
+    if (pre_skew) skew = *pre_skew;
+    else TRY(bpl_probe_device<Fr>(ctx, vecs, &skew, probe_walk, probe_min));
   }
   if (probed && bases->bpl) {
     for (size_t v = 0; v < k; v++)
       if (skew[v] && !alt) TRY(bases_alt<Fq>(ctx, bases, &alt));
   } else if (probed) {
     bool any_split = false;
-    for (size_t v = 0; v < k; v++) any_split = any_split || split_needed(ctx, bases, lens[v]);
+    for (size_t v = 0; v < k; v++) any_split = any_split || split_needed(ctx, bases, vecs[v].n);
     if (any_split) std::fill(skew.begin(), skew.end(), 0);  // (longer than 2^21: ranges of the key, chunked anyway)
   }
-  std::vector<MsmJob> jobs;
+  std::vector<MsmJob> jobs;  // the vectors' ranges; owner: the vector's place in `vecs`
   for (size_t v = 0; v < k; v++) {
-    if (offs[v] > bases->n) return AMSM_E_INVALID_ARG;
-    const amsm_bases* key = skew[v] && bases->bpl ? alt : bases;
-    const size_t len = lens[v];
-    const bool split = split_needed(ctx, key, len);
-    const size_t step = split ? split_chunk(ctx, key) : std::max<size_t>(len, 1);
+    MsmJob vec = vecs[v];
+    vec.owner = v;
+    vec.key = skew[v] && bases->bpl ? alt : bases;
+    vec.force_chunked = skew[v] && !bases->bpl;
+    const amsm_bases* key = vec.key;
+    const bool split = split_needed(ctx, key, vec.n);
     const size_t first_job = jobs.size();
-    size_t lo = 0;
-    do {  // (an empty vector stays one empty job: a batch with one is no batch of direct sums, msm_multi_xyzz)
-      jobs.push_back(MsmJob{v, key, offs[v] + lo, std::min(step, len - lo), (const char*)d_scalars[v] + lo * 32, skew[v] && !bases->bpl});
-      lo += step;
-    } while (lo < len);
+    // (an empty vector stays one empty job: a batch with one is no batch of direct sums, msm_multi_xyzz)
+    cut_into_ranges(vec, split ? split_chunk(ctx, key) : std::max<size_t>(vec.n, 1), &jobs);
     // Round 5: the ranges of one vector over a bucket-per-lane key share ONE bucket set (struct Share) -- every leading range
     // that takes that pipeline; a short last range (below a quarter of the window: the twin's pipelines) stays an MSM of its own
     if (split && ctx->share_buckets && key->bpl && key->precomp && ctx->bpl && jobs.size() - first_job >= 2) {
@@ -1397,9 +1416,7 @@ int msm_multi_split_impl(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const
   }
   std::vector<host::HXYZZ<Fq>> part;
   std::vector<uint8_t> ovf;
-  const int rc = msm_multi_xyzz<Fq, Fr>(ctx, jobs, scalars_mont, &part, &ovf);
-  out->assign(k, host::hx_inf<Fq>());
-  if (rc != AMSM_OK) return rc;
+  TRY((msm_multi_xyzz<Fq, Fr>(ctx, jobs, &part, &ovf)));
   // a range of a shared MSM met skewed digits (what the probe's 1024 samples missed): that vector's shared ranges again, each an
   // MSM of its own with its own fallback -- the result does not depend on the path
   std::vector<uint8_t> redo(k, 0);
@@ -1407,20 +1424,19 @@ int msm_multi_split_impl(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const
   for (size_t j = 0; j < jobs.size(); j++)
     if (ovf[j]) redo[jobs[j].owner] = 1, any_redo = true;
   if (any_redo) {
-    std::vector<MsmJob> again;
-    std::vector<size_t> at;  // where each of them sits in `jobs`
+    std::vector<MsmJob> again;  // (owner: here the place in `jobs` whose part the re-run replaces -- not added: the range's own part is stale)
     for (size_t j = 0; j < jobs.size(); j++)
       if (redo[jobs[j].owner] && jobs[j].share.buf >= 0) {
         again.push_back(jobs[j]);
         again.back().share = Share();
-        at.push_back(j);
+        again.back().owner = j;
       }
     std::vector<host::HXYZZ<Fq>> r;
-    TRY((msm_multi_xyzz<Fq, Fr>(ctx, again, scalars_mont, &r)));
-    for (size_t t = 0; t < at.size(); t++) part[at[t]] = r[t];
+    TRY((msm_multi_xyzz<Fq, Fr>(ctx, again, &r)));
+    for (size_t t = 0; t < again.size(); t++) part[again[t].owner] = r[t];
     ctx->n_bpl_fallbacks++;
   }
-  for (size_t j = 0; j < jobs.size(); j++) (*out)[jobs[j].owner] = host::hx_add<Fq>((*out)[jobs[j].owner], part[j]);
+  add_by_owner<Fq>(jobs, part, out);
   return AMSM_OK;
 }
 
@@ -1501,27 +1517,21 @@ int msm_multi_host_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const 
                         const size_t* ns, int scalars_mont, std::vector<host::HXYZZ<Fq>>* out, const OneshotBases* os = nullptr,
                         bool no_halves = false) {
   out->assign(k, host::hx_inf<Fq>());
+  std::vector<MsmJob> vecs;  // one job per slice (scalars: host pointers)
+  TRY(jobs_from_arrays(bases, k, offs, (const void* const*)h_scalars, ns, scalars_mont, &vecs));
   // What the host learns about the slices before anything is uploaded: 1024 samples each for "looks two-valued" and for the digit
   // histogram of the skew probe.  Round 5: the samples are 1024 cache and TLB misses per look and the histogram 13 windows of
   // them -- ~0.1 ms per slice, serial in front of the first upload: 1.1-1.3 ms of a 17.5 ms call of twelve 2^20-scalar slices
   // (rocprofv3 timeline against the call's wall clock, profiles/r05_host_slices.md).  Now one task per DISTINCT slice on the host pool.
   std::vector<uint8_t> looks_tv(k, 0), skew_bps(k, 0), skew_bpl(k, 0);
   {
-    for (size_t v = 0; v < k; v++)
-      if (offs[v] > bases->n) return AMSM_E_INVALID_ARG;
     const bool want_probe = ctx->bpl_probe && bases->precomp;
-    std::vector<size_t> first(k);
-    for (size_t v = 0; v < k; v++) {
-      first[v] = v;
-      for (size_t u = 0; u < v; u++)
-        if (h_scalars[u] == h_scalars[v] && ns[u] == ns[v] && offs[u] == offs[v]) {
-          first[v] = first[u];
-          break;
-        }
-    }
+    std::vector<size_t> all(k);
+    for (size_t v = 0; v < k; v++) all[v] = v;
+    const std::vector<size_t> first = first_identical(vecs, all);
     HostPool::get().run(k, [&](size_t v) {
       if (first[v] != v || !h_scalars[v]) return;
-      const size_t len = std::min(ns[v], bases->n - offs[v]);
+      const size_t len = vecs[v].n;
       if (ctx->two_valued && len >= TV_MIN_PAIRS) looks_tv[v] = host_looks_two_valued(h_scalars[v], len);
       if (!looks_tv[v] && ctx->two_valued && len >= TV_MIN_PAIRS && !bases->bpl) {  // (a witness with boolean wires goes there too)
         u32 one_words[8] = {1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
@@ -1544,31 +1554,28 @@ int msm_multi_host_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const 
     bool any = false;
     size_t total = 0;
     for (size_t v = 0; v < k; v++) {
-      const size_t len = std::min(ns[v], bases->n - offs[v]);
-      total += len * 32;
+      total += vecs[v].n * 32;
       any = any || looks_tv[v];
     }
     if (any && total <= ((size_t)4 << 30)) {
-      if (os) TRY(oneshot_upload_range<Fq>(ctx, bases, os, offs[0], std::min(ns[0], bases->n - offs[0]), ctx->stream));  // (one vector: k = 1)
+      if (os) TRY(oneshot_upload_range<Fq>(ctx, bases, os, vecs[0].off, vecs[0].n, ctx->stream));  // (one vector: k = 1)
       TRY(ensure(ctx->stage, total));
-      std::vector<const void*> d_ptrs(k);
-      std::vector<size_t> lens(k);
       size_t at = 0;
-      for (size_t v = 0; v < k; v++) {
-        lens[v] = std::min(ns[v], bases->n - offs[v]);
-        d_ptrs[v] = (char*)ctx->stage.p + at;
-        if (lens[v]) HIP_TRY(hipMemcpyAsync((char*)ctx->stage.p + at, h_scalars[v], lens[v] * 32, hipMemcpyHostToDevice, ctx->stream));
-        at += lens[v] * 32;
+      for (MsmJob& vec : vecs) {  // from here on device vectors
+        char* dst = (char*)ctx->stage.p + at;
+        if (vec.n) HIP_TRY(hipMemcpyAsync(dst, vec.scalars, vec.n * 32, hipMemcpyHostToDevice, ctx->stream));
+        vec.scalars = dst;
+        at += vec.n * 32;
       }
-      return msm_multi_split_xyzz<Fq, Fr>(ctx, bases, k, offs, d_ptrs.data(), lens.data(), scalars_mont, out);
+      return msm_multi_split_xyzz<Fq, Fr>(ctx, vecs, out);
     }
   }
-  std::vector<MsmJob> jobs;  // (scalars: host slices)
+  std::vector<MsmJob> jobs;  // the slices' ranges (scalars: host pointers)
   size_t n_max = 0;
   const amsm_bases* alt = nullptr;
   bool halved = false;
   for (size_t v = 0; v < k; v++) {
-    const size_t len = std::min(ns[v], bases->n - offs[v]);
+    const size_t len = vecs[v].n;
     const amsm_bases* key = bases;
     // bucket-split candidates (2^16 .. 2^17 pairs over a precomputed key): the same 1024-sample look at the digits the device
     // vectors get -- a skewed slice (the constant hiding vectors of the zk provers) would pay an aborted prep plus a re-run
@@ -1586,11 +1593,14 @@ int msm_multi_host_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const 
     const bool halve = !no_halves && !os && k == 1 && key == bases && !split && !force_chunked && host_halves_apply(ctx, key, len) &&
                        choose_pipeline(ctx, key, h1, -1, false).pipeline == msel::BUCKET_PER_LANE &&
                        choose_pipeline(ctx, key, len - h1, -1, false).pipeline == msel::BUCKET_PER_LANE &&
-                       bpl_geom(ctx, key, offs[v], h1, -1, 0, &hg) && hg.n_sets == 1u;
+                       bpl_geom(ctx, key, vecs[v].off, h1, -1, 0, &hg) && hg.n_sets == 1u;
     if (halve) step = h1;
-    for (size_t lo = 0; lo < len; lo += step) {
-      jobs.push_back(MsmJob{v, key, offs[v] + lo, std::min(step, len - lo), (const char*)h_scalars[v] + lo * 32, force_chunked});
-      n_max = std::max(n_max, jobs.back().n);
+    if (len) {  // (an empty slice is no job here)
+      MsmJob vec = vecs[v];
+      vec.key = key;
+      vec.force_chunked = force_chunked;
+      cut_into_ranges(vec, step, &jobs);
+      n_max = std::max(n_max, std::min(step, len));
     }
     if (halve && jobs.size() == 2) {
       TRY(arm_shared_set<Fq>(ctx, jobs, 0, 2, hg.B));
@@ -1606,7 +1616,7 @@ int msm_multi_host_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const 
     bool all_direct = J >= 2;
     size_t total = 0;
     for (const MsmJob& j : jobs) {
-      all_direct = all_direct && j.key == bases && direct_sum_applies(ctx, bases, j.n, -1, j.force_chunked);
+      all_direct = all_direct && j.key == bases && direct_sum_applies(ctx, j);
       total += j.n * 32;
     }
     if (all_direct && total <= ((size_t)64 << 20)) {
@@ -1619,8 +1629,8 @@ int msm_multi_host_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const 
         j.scalars = dst;
         at += j.n * 32;
       }
-      TRY((msm_multi_xyzz<Fq, Fr>(ctx, staged, scalars_mont, &part)));
-      for (size_t j = 0; j < J; j++) (*out)[jobs[j].owner] = host::hx_add<Fq>((*out)[jobs[j].owner], part[j]);
+      TRY((msm_multi_xyzz<Fq, Fr>(ctx, staged, &part)));
+      add_by_owner<Fq>(jobs, part, out);
       return AMSM_OK;
     }
   }
@@ -1653,10 +1663,11 @@ int msm_multi_host_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const 
         HIP_TRY(hipStreamWaitEvent(ctx->s_prep, ctx->up_ev[r], 0));
         // (the caller's stream reads scalars only in those two cases: inside a batch it carries the accumulations, and a barrier
         // packet in front of each costs the queue ~10 us)
-        if (J == 1 || direct_sum_applies(ctx, jobs[j].key, jobs[j].n, -1, jobs[j].force_chunked))
+        if (J == 1 || direct_sum_applies(ctx, jobs[j]))
           HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->up_ev[r], 0));
-        TRY((msm_enqueue<Fq, Fr>(ctx, sl, jobs[j].key, jobs[j].off, ctx->stage_ring[r].p, jobs[j].n, scalars_mont, -1, j + 1 == J, J == 1,
-                                 jobs[j].force_chunked, &jobs[j].share)));
+        MsmJob staged = jobs[j];  // the slot's job reads the staging buffer (a re-run too: msm_collect)
+        staged.scalars = ctx->stage_ring[r].p;
+        TRY((msm_enqueue<Fq, Fr>(ctx, sl, staged, place_of(j, J))));
         // ONE upload ahead of the MSM being enqueued, the host copies while the GPU computes MSM j (two ahead were measured slower
         // twice: the ring has N_SLOTS + 2 buffers all the same)
         return j + 1 < J ? upload(j + 1) : AMSM_OK;
@@ -1668,7 +1679,7 @@ int msm_multi_host_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const 
     ctx->n_bpl_fallbacks++;             // with its own fallback -- the result does not depend on the path
     return msm_multi_host_xyzz<Fq, Fr>(ctx, bases, k, offs, h_scalars, ns, scalars_mont, out, os, true);
   }
-  for (size_t j = 0; j < J; j++) (*out)[jobs[j].owner] = host::hx_add<Fq>((*out)[jobs[j].owner], part[j]);
+  add_by_owner<Fq>(jobs, part, out);
   return AMSM_OK;
 }
 
@@ -1677,5 +1688,7 @@ template <class Fq, class Fr>
 int msm_batch_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, const void* const* d_scalars,
                    size_t n_vecs, size_t n, int scalars_mont, std::vector<host::HXYZZ<Fq>>* out) {
   std::vector<size_t> offs(n_vecs, base_off), ns(n_vecs, n);
-  return msm_multi_split_xyzz<Fq, Fr>(ctx, bases, n_vecs, offs.data(), d_scalars, ns.data(), scalars_mont, out);
+  std::vector<MsmJob> vecs;
+  TRY(jobs_from_arrays(bases, n_vecs, offs.data(), d_scalars, ns.data(), scalars_mont, &vecs));
+  return msm_multi_split_xyzz<Fq, Fr>(ctx, vecs, out);
 }

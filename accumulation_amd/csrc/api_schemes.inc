@@ -25,7 +25,7 @@ int msm_grouped_impl(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, co
   if (n) {
     stage_begin(ctx);
     TRY(prep_fork(ctx));
-    TRY((msm_enqueue<Fq, Fr>(ctx, &ctx->slot[0], bases, base_off, d_scalars, n, mont, (int)group_shift)));
+    TRY((msm_enqueue<Fq, Fr>(ctx, &ctx->slot[0], single_job(bases, base_off, d_scalars, n, mont, (int)group_shift), Place::LONE)));
     int rc = msm_collect<Fq>(ctx, &ctx->slot[0], r.data());
     stage_end(ctx);
     if (rc != AMSM_OK) return rc;
@@ -90,11 +90,11 @@ int ipa_round_impl(amsm_ctx* ctx, const amsm_bases* key, const uint64_t* xi_mont
   // vectors as they were (a retry would otherwise fold them twice and produce a wrong proof without any error).  What
   // can still fail after the fold is a scalar outside the field (AMSM_E_SCALAR_RANGE) or a device fault: amsm.h says that
   // d_coeffs / d_z are consumed whenever the call got past its argument checks.
-  if (direct_sum_applies(ctx, key, n, (int)(log_key - 1 - j), false)) {  // a small key: the round is a grouped direct sum
-    TRY((msm_enqueue_direct<Fq, Fr>(ctx, &ctx->slot[0], key, 0, nullptr, n, 1, (int)(log_key - 1 - j), true, true)));
-  } else {
+  // (a small key: the round is a grouped direct sum -- msm_plan reserves for that form too)
+  const MsmJob round_msm = single_job(key, 0, d_u, n, 1, (int)(log_key - 1 - j));
+  {
     bool sp = false;
-    TRY((msm_plan<Fq>(ctx, &ctx->slot[0], key, 0, n, (int)(log_key - 1 - j), &sp)));
+    TRY((msm_plan<Fq>(ctx, &ctx->slot[0], round_msm, &sp)));
   }
   u32 blocks = 0;
   TRY((ipa_round_vectors<Fr>(ctx, xi_mont, j, log_key, d_coeffs, d_z, half, d_u, fold_x_mont, &blocks)));
@@ -102,7 +102,7 @@ int ipa_round_impl(amsm_ctx* ctx, const amsm_bases* key, const uint64_t* xi_mont
   stage_begin(ctx);
   TRY(prep_fork(ctx));
   {
-    int rc_e = msm_enqueue<Fq, Fr>(ctx, &ctx->slot[0], key, 0, d_u, n, 1, (int)(log_key - 1 - j));
+    int rc_e = msm_enqueue<Fq, Fr>(ctx, &ctx->slot[0], round_msm, Place::LONE);
     if (rc_e != AMSM_OK) {
       stage_end(ctx);
       return rc_e;
@@ -187,7 +187,7 @@ int msm_partial_impl(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, co
   Slot* sl = &ctx->slot[0];
   stage_begin(ctx);
   TRY(prep_fork(ctx));
-  TRY((msm_enqueue<Fq, Fr>(ctx, sl, bases, base_off, d_scalars, n, mont)));
+  TRY((msm_enqueue<Fq, Fr>(ctx, sl, single_job(bases, base_off, d_scalars, n, mont), Place::LONE)));
   if (sl->geom.n_sets == 1) {
     // single folded record: it stays on the device (copied record-to-record); the host only waits for
     // the range flag

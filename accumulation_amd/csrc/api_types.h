@@ -35,16 +35,27 @@ struct Share {
   bool first = false, last = false;
 };
 
-// One MSM, or one range of one, as the batch drivers of api_pipeline.inc list them for the slot ring
+// One MSM, or one range of one: THE description of an MSM, from the entry point that lists it to the slot that carries it
 struct MsmJob {
   size_t owner = 0;                // index of the caller's MSM; this job's result is added to out[owner]
   const amsm_bases* key = nullptr;  // the key this job runs over (a 20-bit key's twin for a skewed vector)
   size_t off = 0;                  // first generator
-  size_t n = 0;                    // number of pairs (0: the identity, no slot)
+  size_t n = 0;                    // number of pairs (0: the identity, no slot), clamped to the key
   const void* scalars = nullptr;   // device pointer; a host pointer on the upload path
-  bool force_chunked = false;      // skew probe verdict: skip the bucket-per-lane attempt
+  int mont = 0;                    // the scalars are in Montgomery form
+  int group_shift = -1;            // >= 0: two sums by that bit of the index (the IPA rounds)
+  bool force_chunked = false;      // skew probe verdict, or a prep that overflowed: no bucket-per-lane / bucket-split attempt
+  bool skip_ones = false;          // the vector's unit scalars are summed apart (msm_multi_split_xyzz): MsmGeom::skip_ones
   Share share;                     // buf >= 0: one range of a shared bucket set
 };
+
+// Where an MSM stands in its call (msm_enqueue): whether anybody waits for its tail, and whether anything can overlap with it
+enum class Place {
+  LONE,         // the only MSM of a blocking call: exposed tail, the whole chain on the caller's stream
+  BATCH_LAST,   // the last MSM of a batch (or a re-run inside one): exposed tail, on the per-stage streams
+  BATCH_INNER,  // another MSM is queued behind it: its tail is hidden behind that one's accumulation
+};
+inline Place place_of(size_t i, size_t count) { return count == 1 ? Place::LONE : (i + 1 == count ? Place::BATCH_LAST : Place::BATCH_INNER); }
 
 // One pipeline slot = one stream + one private workspace, so two MSMs of a batch can be in flight:
 // the latency-bound tail of MSM i (fold partials, bucket reduce) overlaps the throughput-bound head of
@@ -62,18 +73,10 @@ struct Slot {  // buffers and events of one MSM in flight (the streams belong to
   DevBuf red_ticket;  // one arrival counter per bucket set (k_bucket_reduce_fold_quad; zeroed at allocation, left clear by the kernel)
   DevBuf ds_flags;  // the direct sum's two flag words (zeroed at allocation, left clear by k_fold_quad)
   DevBuf bpl_grp, bpl_order;  // bucket-per-lane pipeline: group headers, bucket order (entries live in vals_a / vals_b)
-  // the MSM this slot carries, kept until it is collected: a bucket-per-lane MSM whose prep reports a skewed input is
-  // re-run from here through the chunked pipeline (msm_collect)
-  struct Job {
-    Share share;  // this MSM is one range of a longer one whose ranges share a bucket set (buf >= 0)
-    const amsm_bases* bases = nullptr;
-    size_t base_off = 0, n = 0;
-    const void* d_scalars = nullptr;
-    int mont = 0;
-    int group_shift = -1;
-    bool force_chunked = false;  // a bucket-split MSM whose prep overflowed: the re-run must not choose that pipeline again
-    int (*rerun)(amsm_ctx*, Slot*) = nullptr;
-  } job;
+  // the MSM this slot carries (with the caller's key, not the twin msm_plan resolves), kept until it is collected: a bucket-per-lane
+  // or bucket-split MSM whose prep reports a skewed input is re-run from here through the chunked pipeline (msm_collect)
+  MsmJob job;
+  int (*rerun)(amsm_ctx*, Slot*) = nullptr;
   void* h_pinned = nullptr;
   size_t h_pinned_bytes = 0;
   MsmGeom geom = {};
@@ -245,7 +248,7 @@ struct amsm_ctx {
   DevBuf check_ws;      // amsm_points_check[_device]: counters, status bytes and the uploaded piece (api_keys.inc)
   int subgroup_ladder = 1;  // AMSM_SUBGROUP_LADDER: the shape of the BLS12-381 subgroup ladder (points_check_kernels.h; 2: the A/B's other side)
   DevBuf xyzz_scratch;  // unconverted sums of large key folds / precompute levels (launch.h: batch_affine_pays)
-  // two-valued device vectors (api_pipeline.inc: msm_two_valued_pass): every scalar is 0 or one value v -> v * (sum of the
+  // two-valued device vectors (api_pipeline.inc: msm_multi_split_xyzz): every scalar is 0 or one value v -> v * (sum of the
   // generators with a non-zero scalar), on its own stream beside the batch's other MSMs.  AMSM_TWO_VALUED=0 turns it off.
   int two_valued = 1;
   DevBuf tv_flags, tv_parts, tv_out;
@@ -264,10 +267,7 @@ struct amsm_ctx {
   void** rccl_comms = nullptr;   // ncclComm_t per shard
   DevBuf rec_send, rec_recv, stage;  // per device: this shard's partial records / the gathered ones / scalar slices
   hipEvent_t multi_fork = nullptr;
-  // vectors whose unit scalars are summed apart during the current msm_multi_split_xyzz call: [first byte, one past the last) of
-  // their scalars -- msm_enqueue sets MsmGeom::skip_ones for every (range of a) vector that lies inside one
-  std::vector<std::pair<const char*, const char*>> skip_ones_ranges;
-  unsigned long long n_ones_split = 0;  // MSMs that took that form (amsm_ctx_unit_scalar_msms)
+  unsigned long long n_ones_split = 0;  // MSMs whose unit scalars were summed apart (amsm_ctx_unit_scalar_msms)
   size_t replicate_below = 0;             // amsm_ctx_set_replicate_below: keys up to this many generators are replicated, not sharded
   unsigned long long n_replicated = 0;    // MSMs of batch calls over replicated keys that ran off the primary device
   unsigned long long n_collectives = 0;  // exchanges of partial records so far (amsm_ctx_collectives: one per sharded call)

@@ -13,6 +13,7 @@
 //                    distribution (k_accum_l0 + k_accum_l1)
 // Longer MSMs are cut into ranges first (`range`), each range is chosen again; the ranges of one vector over a bucket-per-lane key
 // share one bucket set (api_types.h: struct Share).
+// Beside the two tables: `classify`, what a call makes of its vectors' two-valued probes (two-valued, all zero, unit scalars summed apart).
 #pragma once
 #include <stddef.h>
 
@@ -160,6 +161,66 @@ inline bool wants_skew_probe(const KeyDesc& k, size_t n, const Switches& sw) {
   const size_t r = range_of(k, n, sw);
   const Choice ch = choose(k, r ? r : n, false, false, false, sw);
   return ch.pipeline == BUCKET_PER_LANE || ch.pipeline == BUCKET_SPLIT;
+}
+
+// ---- the vectors of one call: which skip the windowed pipelines, which run them without their unit scalars -------------------------
+// What the host reads of a device vector's two-valued probe (vec_kernels.h k_tv_probe: exact test plus 1024 samples) and what it
+// makes of it.  words: the vector's probe block as read back (null: not probed -- too short, or the shortcut is off).
+constexpr unsigned TVW_MIXED = 0, TVW_TWO_VALUED = 1, TVW_ALL_ZERO = 2, TVW_N_EXC = 3, TVW_ONES = 4, TVW_VALUE = 8;  // word indices
+// unit scalars among the probe's 1024 samples from which a vector's ones are summed apart (0.8 %: below the skew probe's 24 of
+// 1024 in one bin, so what that probe no longer sees is always taken out)
+constexpr unsigned TV_ONES_MIN_SAMPLES = 8;
+enum Verdict {
+  V_REGULAR = 0,     // the windowed pipelines, as it is
+  V_TWO_VALUED = 1,  // every scalar 0 or one value v: v * (sum of the generators under v), no pipeline
+  V_ALL_ZERO = 2,    // the identity, nothing to launch
+  V_ONES_APART = 3   // the pipelines without its unit scalars (MsmJob::skip_ones), their generators summed apart
+};
+struct VecProbe {
+  const unsigned* words;
+  size_t n;             // pairs
+  const char* scalars;  // first byte of its n * 32 bytes of scalars
+};
+inline void classify(const VecProbe* vec, size_t k, bool mont, const KeyDesc& key, const Switches& sw, unsigned char* verdict) {
+  for (size_t v = 0; v < k; v++) {
+    verdict[v] = V_REGULAR;
+    const unsigned* f = vec[v].words;
+    if (!f) continue;
+    // canonical-form vectors (mont == 0) whose value is 2^255 or more keep to the windowed pipelines, which report such
+    // scalars (include/amsm.h: AMSM_E_SCALAR_RANGE) -- the shortcut must not turn that error into a result; values in
+    // [r, 2^255) give the same point either way.  The vector's exceptions, a handful of scalars read back after the sum, are
+    // checked when they arrive (msm_multi_split_xyzz: tv_bad)
+    if (f[TVW_MIXED] == 0u && f[TVW_TWO_VALUED] == 1u && (mont || (f[TVW_VALUE + 7] >> 31) == 0u)) {
+      verdict[v] = V_TWO_VALUED;
+      continue;
+    }
+    if (f[TVW_MIXED] == 0u && f[TVW_TWO_VALUED] != 1u && f[TVW_ALL_ZERO] == 1u) {
+      verdict[v] = V_ALL_ZERO;
+      continue;
+    }
+    // Round 5: vectors with a SHARE of unit scalars (the boolean wires of an R1CS witness; ark-ec's multi_scalar_mul adds their bases
+    // directly) are not two-valued, but all their ones would land in bucket 1 of the lowest window (measured, M pairs/s in batches:
+    // 2^18 pairs with 10 % booleans 2.2x slower than uniform, a plain 2^20 key 2.3x).
+    // (not where the MSM would be a direct sum: that form has no buckets to skew)
+    // (nor over a 20-bit table: the skew probe sends such a vector to the chunked pipeline over the key's 17-bit twin, where the
+    // ones cost little -- 2^20 pairs in batches, 10 / 50 / 90 % booleans: 1.21 / 0.85 / 0.52 ms against 1.13 / 0.91 / 0.75 with the
+    // separate sum, a uniform vector 1.10)
+    if (f[TVW_ONES] >= TV_ONES_MIN_SAMPLES && !key.bpl && choose(key, vec[v].n, false, false, false, sw).pipeline != DIRECT_SUM)
+      verdict[v] = V_ONES_APART;
+  }
+  // a vector sharing memory with one of the call that keeps its ones gives the form up (protects nothing now that MsmJob carries skip_ones)
+  for (bool changed = true; changed;) {
+    changed = false;
+    for (size_t v = 0; v < k; v++) {
+      if (verdict[v] != V_ONES_APART) continue;
+      const char *a0 = vec[v].scalars, *a1 = a0 + vec[v].n * 32;
+      for (size_t u = 0; u < k && verdict[v] == V_ONES_APART; u++) {
+        if (u == v || verdict[u] != V_REGULAR || vec[u].n == 0) continue;
+        const char *b0 = vec[u].scalars, *b1 = b0 + vec[u].n * 32;
+        if (a0 < b1 && b0 < a1) verdict[v] = V_REGULAR, changed = true;
+      }
+    }
+  }
 }
 
 }  // namespace msel

@@ -1,6 +1,7 @@
 // Prints what accumulation_amd/csrc/msm_select.h decides at every threshold edge (plain C++: no HIP, no library) --
 // tests/test_pipeline_select_cpu.py holds the expected table.  One line per (key, pairs, form):
 //   <key> <pairs> <plain|grouped|grouped_irregular|skewed> <pipeline> twin=<0|1> plain_window=<c> range=<pairs>
+// and one per case of msel::classify:  classify <case> <verdict of each vector>
 #include <cstdio>
 #include <vector>
 
@@ -75,5 +76,69 @@ int main() {
   for (int lg : {1, 8, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 22})
     printf("key_window 2p%d precomputed=%d precomputed_bpl_off=%d plain=%d\n", lg, key_window(P2(lg), true, true), key_window(P2(lg), true, false),
            key_window(P2(lg), false, true));
+  // what a call makes of its vectors' two-valued probes (classify): one line per case, one verdict per vector
+  {
+    static char mem[(size_t)3 << 22];  // the scalars' addresses (never read): three vectors of 2^17 scalars
+    struct V {
+      unsigned words[32];
+      bool probed;
+      VecProbe p;
+    };
+    // mixed / two_valued / all_zero: the probe's flag words; ones: unit scalars among its 1024 samples; top: the value's highest word
+    auto vec = [&](bool probed, unsigned mixed, unsigned two_valued, unsigned all_zero, unsigned ones, unsigned top, size_t n, size_t at) {
+      V v{};
+      v.words[TVW_MIXED] = mixed;
+      v.words[TVW_TWO_VALUED] = two_valued;
+      v.words[TVW_ALL_ZERO] = all_zero;
+      v.words[TVW_ONES] = ones;
+      v.words[TVW_VALUE + 7] = top;
+      v.probed = probed;
+      v.p = VecProbe{nullptr, n, mem + at * 32};
+      return v;
+    };
+    auto run = [&](const char* name, std::vector<V> vs, bool mont, const KeyDesc& key, const Switches& s) {
+      std::vector<VecProbe> ps;
+      for (V& v : vs) {
+        if (v.probed) v.p.words = v.words;
+        ps.push_back(v.p);
+      }
+      std::vector<unsigned char> verdict(ps.size());
+      classify(ps.data(), ps.size(), mont, key, s, verdict.data());
+      printf("classify %s", name);
+      const char* names[] = {"regular", "two_valued", "all_zero", "ones_apart"};
+      for (unsigned char x : verdict) printf(" %s", names[x]);
+      printf("\n");
+    };
+    const KeyDesc table17{P2(17), true, false, false, 17};
+    const size_t n = P2(17);
+    const unsigned heavy = 400, few = 0;  // sampled ones of a 40 % boolean vector / of 40 ones in 2^17
+    run("two_valued", {vec(true, 0, 1, 0, 0, 0x3fffffffu, n, 0)}, false, table17, sw);
+    run("mixed_flag_wins", {vec(true, 1, 1, 0, 0, 0, n, 0)}, false, table17, sw);
+    run("value_2p255_canonical", {vec(true, 0, 1, 0, 0, 0x80000000u, n, 0)}, false, table17, sw);
+    run("value_2p255_montgomery", {vec(true, 0, 1, 0, 0, 0x80000000u, n, 0)}, true, table17, sw);
+    run("all_zero", {vec(true, 0, 0, 1, 0, 0, n, 0)}, false, table17, sw);
+    run("ones_7_samples", {vec(true, 1, 0, 0, TV_ONES_MIN_SAMPLES - 1, 0, n, 0)}, false, table17, sw);
+    run("ones_8_samples", {vec(true, 1, 0, 0, TV_ONES_MIN_SAMPLES, 0, n, 0)}, false, table17, sw);
+    run("not_probed", {vec(false, 0, 0, 0, heavy, 0, n, 0)}, false, table17, sw);
+    run("ones_over_20_bit_table", {vec(true, 1, 0, 0, heavy, 0, P2(20), 0)}, false, keys[3].d, sw);
+    run("ones_plain_key", {vec(true, 1, 0, 0, heavy, 0, P2(20), 0)}, false, keys[5].d, sw);
+    run("ones_direct_sum", {vec(true, 1, 0, 0, heavy, 0, P2(14), 0)}, false, keys[0].d, sw);
+    off = sw;
+    off.direct = false;
+    run("ones_direct_sum_off", {vec(true, 1, 0, 0, heavy, 0, P2(14), 0)}, false, keys[0].d, off);
+    // tests/test_unit_scalars_gpu.py: a boolean-heavy vector, a view that starts 100 scalars before its end and keeps its few ones,
+    // an unrelated witness
+    run("shared_memory_view", {vec(true, 1, 0, 0, heavy, 0, n, 0), vec(true, 1, 0, 0, few, 0, n, n - 100), vec(true, 1, 0, 0, heavy, 0, n, 2 * n)},
+        false, table17, sw);
+    run("shared_memory_no_view", {vec(true, 1, 0, 0, heavy, 0, n, 0), vec(true, 1, 0, 0, heavy, 0, n, 2 * n)}, false, table17, sw);
+    run("shared_memory_adjacent", {vec(true, 1, 0, 0, heavy, 0, n, 0), vec(true, 1, 0, 0, few, 0, n, n)}, false, table17, sw);
+    run("shared_memory_unprobed_view", {vec(true, 1, 0, 0, heavy, 0, n, 0), vec(false, 0, 0, 0, 0, 0, 100, n - 100)}, false, table17, sw);
+    run("shared_memory_empty_view", {vec(true, 1, 0, 0, heavy, 0, n, 0), vec(false, 0, 0, 0, 0, 0, 0, n - 100)}, false, table17, sw);
+    run("shared_memory_two_valued_view", {vec(true, 1, 0, 0, heavy, 0, n, 0), vec(true, 0, 1, 0, 0, 0, P2(14), 0)}, false, table17, sw);
+    run("shared_memory_both_ones", {vec(true, 1, 0, 0, heavy, 0, n, 0), vec(true, 1, 0, 0, heavy, 0, P2(16), 0)}, false, table17, sw);
+    // the give-up spreads: the middle vector overlaps one that keeps its ones, the first overlaps the middle one
+    run("shared_memory_chain", {vec(true, 1, 0, 0, heavy, 0, n, 0), vec(true, 1, 0, 0, heavy, 0, n, n - 100), vec(true, 1, 0, 0, few, 0, n, 2 * n - 200)},
+        false, table17, sw);
+  }
   return 0;
 }

@@ -99,3 +99,34 @@ def test_switches_and_key_windows(table):
     assert win == {"2p1": [8, 8, 4], "2p8": [8, 8, 4], "2p9": [8, 8, 8], "2p12": [8, 8, 8], "2p13": [10, 10, 8], "2p14": [10, 10, 8],
                    "2p15": [13, 13, 8], "2p16": [16, 16, 8], "2p17": [17, 17, 8], "2p18": [16, 16, 8], "2p19": [16, 16, 8],
                    "2p20": [20, 17, 13], "2p22": [20, 17, 16]}
+
+
+def test_classification_of_probed_vectors(table):
+    """msel::classify -- what a call makes of its vectors' two-valued probe words -- one case per rule"""
+    got = {ln.split()[1]: ln.split()[2:] for ln in table[1] if ln.startswith("classify ")}
+    want = {
+        "two_valued": ["two_valued"],
+        "mixed_flag_wins": ["regular"],
+        # a canonical value of 2^255 or more stays with the windowed pipelines (they report it); in Montgomery form the stored
+        # words say nothing about the value's size
+        "value_2p255_canonical": ["regular"],
+        "value_2p255_montgomery": ["two_valued"],
+        "all_zero": ["all_zero"],
+        "ones_7_samples": ["regular"],  # TV_ONES_MIN_SAMPLES = 8 of the 1024 samples
+        "ones_8_samples": ["ones_apart"],
+        "not_probed": ["regular"],
+        "ones_over_20_bit_table": ["regular"],  # runs chunked over the 17-bit twin, where the ones cost little
+        "ones_plain_key": ["ones_apart"],
+        "ones_direct_sum": ["regular"],  # no buckets to skew
+        "ones_direct_sum_off": ["ones_apart"],
+        # tests/test_unit_scalars_gpu.py::test_views_that_share_memory_with_a_vector_that_keeps_its_ones
+        "shared_memory_view": ["regular", "regular", "ones_apart"],
+        "shared_memory_no_view": ["ones_apart", "ones_apart"],
+        "shared_memory_adjacent": ["ones_apart", "regular"],  # touching is not sharing
+        "shared_memory_unprobed_view": ["regular", "regular"],  # a vector too short to probe keeps its ones too
+        "shared_memory_empty_view": ["ones_apart", "regular"],
+        "shared_memory_two_valued_view": ["ones_apart", "two_valued"],  # a view that skips the pipelines keeps nothing in them
+        "shared_memory_both_ones": ["ones_apart", "ones_apart"],
+        "shared_memory_chain": ["regular", "regular", "regular"],
+    }
+    assert got == want

@@ -138,6 +138,35 @@ def test_views_that_share_memory_with_a_vector_that_keeps_its_ones():
         ctx.close()
 
 
+@pytest.mark.parametrize("mont", [False, True], ids=["canonical", "montgomery"])
+def test_unit_scalars_stay_apart_when_the_prep_overflows_and_the_msm_is_rerun(mont):
+    """a plain key just above 2^17 pairs (the smallest size msm_select.h gives a plain key the bucket-per-lane pipeline; plain keys
+    are not skew-probed): a witness with 30 % ones whose ones are summed apart, and a quarter of its scalars the value 2 -- those
+    overflow the prep of the lowest window, msm_collect re-runs the MSM chunked, and the re-run must still leave the ones out
+    (counted twice otherwise): the form is taken once, a fallback is counted, the point is the oracle's"""
+    from accumulation_amd import CommitterKey, Context, VariableBaseMSM
+    curve = ffi.AMSM_PALLAS
+    ctx = Context(curve)
+    try:
+        n = (1 << 17) + 11
+        key = CommitterKey.generate(ctx, 0x0E5B, n, ffi.AMSM_BASES_NO_PRECOMPUTE)
+        xy, _ = key.read()
+        w = _witness(n, 0.3, 61, ones_only=True)
+        w[np.random.default_rng(62).random(n) < 0.25] = [2, 0, 0, 0]
+        if "rerun" not in _ORACLE_CACHE:
+            _ORACLE_CACHE["rerun"] = cref.msm(curve, xy, w)
+        ref, ref_inf = _ORACLE_CACHE["rerun"]
+        up = ctx.upload(cref.fr_to_mont(curve, w) if mont else w)
+        before = ctx.pipeline_stats()
+        out, oinf = VariableBaseMSM.multi_scalar_mul_batch(key, [up], mont=mont)
+        after = ctx.pipeline_stats()
+        assert after["unit_scalar_sums"] - before["unit_scalar_sums"] == 1, (before, after)
+        assert after["fallbacks"] > before["fallbacks"], (before, after)
+        assert bool(oinf[0]) == bool(ref_inf) and np.array_equal(out[0], ref)
+    finally:
+        ctx.close()
+
+
 def test_witness_like_vectors_over_a_sharded_key():
     """a multi-device context (three shards on GPU 0): every shard probes and sums the unit scalars of ITS slice; same results as
     the single-device context and the oracle"""
