@@ -98,7 +98,6 @@ int amsm_ctx_create(amsm_ctx** out, int curve, int device_id, void* stream) {
   if (const char* e = getenv("AMSM_DIRECT_SUM_MAX_LOG2")) c->direct_max_log2 = std::max(0, std::min(16, atoi(e)));
   if (const char* e = getenv("AMSM_TWO_VALUED")) c->two_valued = atoi(e) != 0;
   if (const char* e = getenv("AMSM_SHARE_BUCKETS")) c->share_buckets = atoi(e) != 0;
-  if (const char* e = getenv("AMSM_FUSED_FOLD")) c->fused_fold = atoi(e) != 0;
   if (const char* e = getenv("AMSM_HOST_HALVES")) c->host_halves = atoi(e) != 0;
   if (const char* e = getenv("AMSM_SUBGROUP_LADDER")) c->subgroup_ladder = atoi(e) == 2 ? 2 : 1;
   *out = c;

@@ -54,7 +54,7 @@ int ensure_pinned(Slot* sl, size_t bytes) {
   return AMSM_OK;
 }
 
-// The slot's arrival counters of k_bucket_reduce_fold_quad, one per bucket set: zeroed when the buffer grows (a memset, then the
+// The slot's arrival counters of the fused tail (k_bucket_reduce<QUAD, FUSED>), one per bucket set: zeroed when the buffer grows (a memset, then the
 // caller's stream is synchronised), left clear by every launch
 int ensure_red_ticket(amsm_ctx* ctx, Slot* sl, size_t n_sets) {
   if (sl->red_ticket.bytes < n_sets * 4) {
@@ -70,6 +70,24 @@ int ensure_red_ticket(amsm_ctx* ctx, Slot* sl, size_t n_sets) {
 
 inline u32 cdiv(u32 a, u32 b) { return (a + b - 1) / b; }
 using msel::ilog2_ceil;
+
+template <class Fq>
+constexpr size_t xyzz_bytes() {
+  return 4 * Fq::L * 4;
+}
+// Everything a tail of n_sets sets needs on slot `sl` (msm_select.h: tail_plan says how much; launch_tail / launch_fold write no more):
+// the partial records, the folded ones with their two flag words on the device and in page-locked memory, the row / column scratch and
+// the arrival counters
+template <class Fq>
+int reserve_tail(amsm_ctx* ctx, Slot* sl, size_t n_sets, const msel::TailPlan& t) {
+  const size_t rec = xyzz_bytes<Fq>();
+  if (t.rc_records) TRY(ensure(sl->red2_rc, t.rc_records * rec));
+  TRY(ensure(sl->red_out, n_sets * t.partials * rec));
+  TRY(ensure(sl->fold_out, n_sets * rec + 64));
+  TRY(ensure_pinned(sl, n_sets * rec + 64));
+  return t.ticket ? ensure_red_ticket(ctx, sl, n_sets) : AMSM_OK;
+}
+inline msel::TailPlan tail_plan_of(const MsmGeom& g, Place place) { return msel::tail_plan(g.nb, g.n_sets, g.B, g.E, g.bpl == 1u, place); }
 
 // Every size threshold -- which window a key's table is built for, which pipeline an MSM takes, where a long MSM is cut -- lives in
 // msm_select.h (two tables, plain C++, unit-tested without a GPU: tests/test_pipeline_select_cpu.py).  Here: how the context's
@@ -106,10 +124,6 @@ inline int slots_for(int c) { return windows_for(c); }   // entry slots per scal
 template <class Fq>
 constexpr size_t affine_bytes() {
   return 2 * Fq::L * 4;
-}
-template <class Fq>
-constexpr size_t xyzz_bytes() {
-  return 4 * Fq::L * 4;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -202,14 +216,7 @@ int make_geom(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, size_t n,
     }
   }
   g.K1 = tune::K1;
-  // buckets per lane of the bucket reduction: 4; 8 for the 2^16-bucket sets of 17-bit windows (half the 16-bit small
-  // multiples, the reduction's largest ALU item; batches 821 -> 826 M pairs/s at 2^20, 845 -> 853 at 2^22; 2 and 16 do not pay)
-  // round 6: 2 for the 128-bucket sets of 8-bit windows (plain keys up to 2^17 pairs: the rounds of a large IPA opening over its
-  // folded key, 64 sets of 128 buckets) -- a set is one workgroup either way, and its chain is the leaf's additions + a 7-bit multiple
-  // + the tree: 3 additions instead of 7 at the leaf
-  g.red_s = std::min<u32>(g.nb >= 65536u ? 8u : (g.nb <= 256u ? 2u : 4u), g.nb);
-  g.red_threads = g.nb / g.red_s;
-  *out = g;
+  *out = g;  // (red_s / red_threads: the tail's plan, msm_select.h -- launch_tail fills them in)
   return AMSM_OK;
 }
 
@@ -287,11 +294,6 @@ inline bool bpl_geom(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, si
     g.part_max = (u32)std::min<unsigned long long>(0xffffffffull, g.precomp ? (wins - 1ull) * per_win + per_top : std::max(per_win, per_top));
     if (g.groups > 1u) g.part_max = (g.part_max + 1u) / 2u;  // (a group sees half the scalars)
   }
-  // the bucket reduction is hidden behind the next MSM's accumulation or exposed on few waves either way: long per-lane runs keep
-  // its small multiples (one per lane) rare -- 2^19 buckets / 32 = 16 384 lanes (measured: 16 / 32 / 64 -> 911 / 955 / 895 M pairs/s
-  // in batches, 0.45 / 0.37 / 0.52 ms exposed)
-  g.red_s = std::min<u32>(32u, g.nb);
-  g.red_threads = g.nb / g.red_s;
   if (!prep_bpl_supported(g)) return false;
   *out = g;
   return true;
@@ -323,9 +325,6 @@ inline bool bps_geom(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, si
   return true;
 }
 
-// bucket sets of 2^18 buckets and more reduce as row / column sums (msm_kernels.h: k_red2_*); smaller sets LOSE with that form
-// (measured: 2^15 buckets, 2^16 pairs 280 -> 212 M pairs/s) and keep the running-sum kernels
-inline bool red2_applies(const amsm_ctx*, const MsmGeom& g) { return g.nb >= (1u << 18) && (g.nb & 1023u) == 0u; }
 // one MSM over generators [off, off + n) of `key` (n already clamped to the key), as the single-MSM entry points describe it
 inline MsmJob single_job(const amsm_bases* key, size_t off, const void* scalars, size_t n, int mont, int group_shift = -1) {
   MsmJob j;
@@ -346,7 +345,7 @@ inline bool direct_sum_applies(const amsm_ctx* ctx, const amsm_bases* bases, siz
 }
 inline bool direct_sum_applies(const amsm_ctx* ctx, const MsmJob& j) { return direct_sum_applies(ctx, j.key, j.n, j.group_shift, j.force_chunked); }
 // Geometry and every allocation of nv direct sums over one key in one launch on slot `sl` (msm_enqueue_direct_batch; nv = 1 may be
-// grouped); nothing is launched
+// grouped); nothing of the MSM is launched
 struct DirectPlan {
   u32 m;       // windows per lane
   u32 blocks;  // workgroups per MSM / per class
@@ -374,12 +373,11 @@ int direct_plan(amsm_ctx* ctx, Slot* sl, const MsmJob* jobs, size_t nv, DirectPl
   const size_t lane_cap = nv > 1 ? (size_t)3 << 16 : (size_t)1 << 16;
   u32 m = 4;
   while (m < DS_W && (nv * n_max * (size_t)(DS_W / m)) > lane_cap) m <<= 1;
-  const size_t rec = xyzz_bytes<Fq>();
   const u32 blocks = cdiv((u32)((group_shift >= 0 ? n_max / 2 : n_max) * (DS_W / m)), 256);  // per MSM / per class
-  TRY(ensure(sl->red_out, (size_t)g.n_sets * blocks * rec));
-  TRY(ensure(sl->fold_out, g.n_sets * rec + 64));
-  TRY(ensure_pinned(sl, g.n_sets * rec + 64));
-  if (!sl->ds_flags.p) {  // zeroed once: k_fold_quad leaves the words clear behind every MSM
+  msel::TailPlan fold{};  // no bucket reduction: the sum kernel leaves the partial records, the bare fold follows
+  fold.partials = blocks;
+  TRY(reserve_tail<Fq>(ctx, sl, g.n_sets, fold));
+  if (!sl->ds_flags.p) {  // zeroed once: k_fold leaves the words clear behind every MSM
     TRY(ensure(sl->ds_flags, 64));
     HIP_TRY(hipMemsetAsync(sl->ds_flags.p, 0, 64, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -390,15 +388,15 @@ int direct_plan(amsm_ctx* ctx, Slot* sl, const MsmJob* jobs, size_t nv, DirectPl
 }
 
 // Geometry and EVERY allocation of one MSM on slot `sl`: what can fail for lack of memory fails here, so a caller with side effects
-// to apply first (amsm_ipa_round_fused folds its vectors in place) can reserve before it commits.  Nothing of the MSM is launched;
-// when the slot's arrival counters grow, their zeroing is (a memset, and the caller's stream is synchronised: ensure_red_ticket).
+// to apply first (amsm_ipa_round_fused folds its vectors in place) can reserve before it commits.  Nothing of the MSM is launched --
+// but flag words and arrival counters are zeroed when they are first allocated or grow: a memset on the caller's stream, which is
+// then synchronised (direct_plan, ensure_red_ticket).
 // *eff = the key the MSM runs over: job.key, or its 17-bit twin when msm_select.h sends a range of a 20-bit key there.
 template <class Fq>
 int msm_plan(amsm_ctx* ctx, Slot* sl, const MsmJob& job, bool* short_prep_out, const amsm_bases** eff = nullptr) {
   const amsm_bases* bases = job.key;
   const size_t base_off = job.off, n = job.n;
   const int group_shift = job.group_shift;
-  const bool quad = true;  // (the reduce partials are sized for the quad kernels: msm_enqueue picks per geometry)
   MsmGeom g;
   const size_t rec = xyzz_bytes<Fq>();
   if (direct_sum_applies(ctx, job)) {  // no prep, no buckets
@@ -408,17 +406,9 @@ int msm_plan(amsm_ctx* ctx, Slot* sl, const MsmJob& job, bool* short_prep_out, c
     return direct_plan<Fq>(ctx, sl, &job, 1, &dp);
   }
   const msel::Choice ch = choose_pipeline(ctx, bases, n, group_shift, job.force_chunked);
-  auto common = [&]() -> int {  // what every sorted pipeline needs behind its accumulation
-    u32 red_blocks = cdiv(g.red_threads * (quad ? 4u : 1u), 256);
-    if (red2_applies(ctx, g)) {  // the row / column reduction's scratch: here, not in msm_enqueue (plan_only callers allocate FIRST)
-      TRY(ensure(sl->red2_rc, (size_t)g.n_sets * (g.nb / 1024u + 1024u) * rec));
-      red_blocks = std::max(red_blocks, cdiv((g.nb / 1024u + 1024u) * 4u, 256) + 1u);
-    }
-    TRY(ensure(sl->buckets, (size_t)g.B * rec));
-    TRY(ensure(sl->red_out, (size_t)g.n_sets * red_blocks * rec));
-    TRY(ensure(sl->fold_out, (size_t)g.n_sets * rec + 64));
-    TRY(ensure_pinned(sl, g.n_sets * rec + 64));
-    return ensure_red_ticket(ctx, sl, g.n_sets);
+  auto common = [&]() -> int {  // what every sorted pipeline needs behind its accumulation: the buckets, and the tail wherever the
+    TRY(ensure(sl->buckets, (size_t)g.B * rec));  // MSM will stand in its call (msm_enqueue knows, callers that reserve first do not)
+    return reserve_tail<Fq>(ctx, sl, g.n_sets, msel::tail_plan_any_place(g.nb, g.n_sets, g.B, g.E, g.bpl == 1u));
   };
   if (ch.pipeline == msel::BUCKET_PER_LANE && bpl_geom(ctx, bases, base_off, n, group_shift, ch.plain_window, &g)) {
     sl->geom = g;
@@ -525,7 +515,7 @@ int msm_enqueue_direct_batch(amsm_ctx* ctx, Slot* sl, const MsmJob* jobs, size_t
     (void)hipEventRecord(sl->ev[ST_ACCUM_L12], st);
     (void)hipEventRecord(sl->ev[ST_REDUCE], st);
   }
-  launch_fold_quad<Fq>(st, g.n_sets, (const u32*)sl->red_out.p, dp.blocks, (u32*)sl->fold_out.p, d_err, (u32*)sl->h_pinned, true);
+  launch_fold<Fq>(st, true, g.n_sets, (const u32*)sl->red_out.p, dp.blocks, (u32*)sl->fold_out.p, d_err, (u32*)sl->h_pinned, true);
   if (ctx->profiling) (void)hipEventRecord(sl->ev[ST_COUNT], st);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(sl->done, st));
@@ -539,11 +529,7 @@ int msm_enqueue_direct_batch(amsm_ctx* ctx, Slot* sl, const MsmJob* jobs, size_t
 // in sl->fold_out and queues their D2H into sl->h_pinned.
 template <class Fq, class Fr>
 int msm_enqueue(amsm_ctx* ctx, Slot* sl, const MsmJob& job, Place place) {
-  // exposed_tail: nothing is queued behind this MSM, so the caller waits for its tail (bucket reduce + fold, a chain of
-  // dependent point operations on a few waves): run it on the quad-cooperative kernels (-0.08 ms).  Inside a batch the
-  // tail is hidden behind the next MSM's accumulation and the one-lane kernels cost less ALU time (measured: 1 % of the
-  // batch throughput).
-  const bool exposed_tail = place != Place::BATCH_INNER;
+  const bool exposed_tail = place != Place::BATCH_INNER;  // nothing is queued behind this MSM: the caller waits for its tail
   if (direct_sum_applies(ctx, job)) return msm_enqueue_direct_batch<Fq, Fr>(ctx, sl, &job, 1, place);
   bool short_prep = false;
   const amsm_bases* bases = nullptr;  // the key the MSM runs over: job.key or its 17-bit twin
@@ -552,17 +538,7 @@ int msm_enqueue(amsm_ctx* ctx, Slot* sl, const MsmJob& job, Place place) {
   const MsmGeom g = sl->geom;
   const void* d_scalars = job.scalars;
   const int scalars_mont = job.mont;
-  // Round 4: a HIDDEN tail (inside a batch) also takes the quad kernels when the bucket table is small.  The tails of
-  // consecutive MSMs queue on one stream, and the one-lane kernels are latency chains whatever the bucket count -- accumulate
-  // L1 80 + reduce 240 + fold 120 us for the 2^15 buckets of a 2^18-pair MSM whose accumulation takes 300 us (rocprofv3, round
-  // 4): the batch ran at one MSM per tail (0.46 ms at 2^18, 0.71 at 2^19).  The quad kernels cost four times the lanes of
-  // almost nothing there and halve the chain; from 2^18 buckets up the one-lane kernels' lower ALU cost wins (2^20 pairs).
-  // (... and only while the accumulation is shorter than the tail chain: up to 2^18 pairs of 16 entries -- at 2^19 the batch
-  // is bound by the accumulation's work and the quad kernels' extra lanes cost 2-6 %; measured, same box, M pairs/s in batches:
-  // 2^16 234 -> 283, 2^17 395 -> 451, 2^18 582 -> 617, 2^19 754 -> 741; BLS12-381 2^18 207 -> 297, 2^19 352 -> 332)
-  const bool small_table = g.B <= (1u << tune::TAIL_QUAD_HIDDEN_LOG2) && g.E <= (5u << 20);
-  const bool quad = exposed_tail || small_table;
-  const bool tail_hidden = !exposed_tail && !small_table;
+  const msel::TailPlan tp = tail_plan_of(g, place);  // the form of the tail, its grids and what msm_plan reserved for it (msm_select.h)
   // one range of a longer MSM over ONE bucket set (struct Share): the caller made the decision with bpl_geom, as msm_plan did
   const Share share = job.share;
   const bool shared = share.buf >= 0;
@@ -577,7 +553,6 @@ int msm_enqueue(amsm_ctx* ctx, Slot* sl, const MsmJob& job, Place place) {
   const bool one = place == Place::LONE;
   hipStream_t st = one ? ctx->stream : ctx->s_prep;  // digits / sort / bounds
   hipStream_t sm = ctx->stream;                      // accumulate L0
-  const u32 red_blocks = cdiv(g.red_threads * (quad ? 4u : 1u), 256);
   const size_t rec = xyzz_bytes<Fq>();
   u32* d_err = short_prep ? (u32*)sl->prep_small.p : (u32*)sl->misc.p;
   u32* d_heavy_count = d_err + 1;
@@ -687,7 +662,9 @@ int msm_enqueue(amsm_ctx* ctx, Slot* sl, const MsmJob& job, Place place) {
     return AMSM_OK;
   };
 
-  // ---- tail: partial records into buckets (chunked pipeline only), the bucket reduction, the fold; the records mirrored to the host ----
+  // ---- tail: partial records into buckets (chunked pipeline only), then the bucket reduction, the fold and the export as tail_plan chose
+  // them; the records and the flag words go straight to the slot's page-locked block (msm_kernels.h: emit_record's mirror): no copy
+  // command between the fold and the slot's `done` event ----
   auto tail = [&]() -> int {
     // The tail the caller waits for -- a blocking call's, or the LAST MSM's of a batch -- stays on the caller's stream, behind its own
     // accumulation: on the tail stream it would queue behind the previous MSM's tail, which runs beside this accumulation and takes
@@ -701,7 +678,7 @@ int msm_enqueue(amsm_ctx* ctx, Slot* sl, const MsmJob& job, Place place) {
     }
     if (ctx->profiling) (void)hipEventRecord(sl->ev[ST_ACCUM_L12], tl);
     if (!g.bpl) {  // the bucket-per-lane accumulation leaves finished buckets: no partial records to fold
-      launch_accum_l1<Fq>(tl, l1_lanes(g, tail_hidden), (const u32*)sl->partials.p, (const u32*)sl->items.p, (const u32*)sl->item_off.p, g,
+      launch_accum_l1<Fq>(tl, l1_lanes(g, !tp.quad), (const u32*)sl->partials.p, (const u32*)sl->items.p, (const u32*)sl->item_off.p, g,
                           (u32*)sl->buckets.p, d_heavy_count, (u32*)sl->heavy.p);
       AMSM_DBG("l1");
       launch_accum_l2<Fq>(tl, (const u32*)sl->partials.p, (const u32*)sl->items.p, (const u32*)sl->item_off.p, (const u32*)d_heavy_count,
@@ -709,35 +686,13 @@ int msm_enqueue(amsm_ctx* ctx, Slot* sl, const MsmJob& job, Place place) {
       AMSM_DBG("l2");
     }
     if (ctx->profiling) (void)hipEventRecord(sl->ev[ST_REDUCE], tl);
-    // round 4: bucket sets of 2^18 buckets and more reduce as row / column sums (msm_kernels.h: k_red2_*; AMSM_RED2=0: the
-    // running-sum kernels; AMSM_RED2=2: every set of 1024 buckets and more).  Measured, same box, batches / blocking call: 2^20
-    // pairs over the 20-bit key 908 -> 928 M pairs/s, 1.409 -> 1.381 ms; smaller sets LOSE (2^15 buckets: 2^16 pairs 280 -> 212,
-    // 2^19 pairs 717 -> 598; a plain key's 16 sets of 2^15: 794 -> 731): with few rows the column sums are all butterfly, and
-    // 1024 + A small multiples cost more than the per-lane ones of a short running-sum kernel
-    u32 fold_n = red_blocks;
-    if (red2_applies(ctx, g)) {  // (scratch sized by msm_plan)
-      fold_n = launch_bucket_reduce2<Fq>(tl, (const u32*)d_buckets, g, quad, quad || !tail_hidden, (u32*)sl->red2_rc.p, (u32*)sl->red_out.p);
-    } else if (quad && ctx->fused_fold) {
-      // round 6: the quad reduction and its fold as ONE launch (the last workgroup of a set to arrive folds the set)
-      launch_bucket_reduce_fold_quad<Fq>(tl, red_blocks, (const u32*)d_buckets, g, (u32*)sl->red_out.p, (u32*)sl->red_ticket.p,
-                                         (u32*)sl->fold_out.p, d_err, (u32*)sl->h_pinned);
-      fold_n = 0;
-    } else if (quad) {
-      launch_bucket_reduce_quad<Fq>(tl, red_blocks, (const u32*)d_buckets, g, (u32*)sl->red_out.p);
-    } else {
-      launch_bucket_reduce<Fq>(tl, red_blocks, (const u32*)d_buckets, g, (u32*)sl->red_out.p);
+    launch_tail<Fq>(tl, tp, (const u32*)d_buckets, g, (u32*)sl->red2_rc.p, (u32*)sl->red_out.p, (u32*)sl->red_ticket.p, (u32*)sl->fold_out.p,
+                    d_err, (u32*)sl->h_pinned);
+    if (amsm_debug()) {
+      char stage[32];
+      snprintf(stage, sizeof(stage), "tail %s", msel::tail_form_name(tp.form));
+      AMSM_DBG(stage);
     }
-    AMSM_DBG("reduce");
-    u32* h = (u32*)sl->h_pinned;
-    // the records and the flag words go straight to the slot's page-locked block (msm_kernels.h: k_fold's mirror): no copy
-    // command between the fold and the slot's `done` event
-    if (fold_n == 0) {
-    } else if (quad) {
-      launch_fold_quad<Fq>(tl, g.n_sets, (const u32*)sl->red_out.p, fold_n, (u32*)sl->fold_out.p, d_err, h);
-    } else {
-      launch_fold<Fq>(tl, g.n_sets, (const u32*)sl->red_out.p, fold_n, (u32*)sl->fold_out.p, d_err, h);
-    }
-    AMSM_DBG("fold");
     if (ctx->profiling) (void)hipEventRecord(sl->ev[ST_COUNT], tl);
     HIP_TRY(hipGetLastError());
     if (shared) {  // the table may be rewritten once this tail has read it
@@ -1263,7 +1218,7 @@ int tv_launch_sums(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, const TvProbe
     u32* parts = (u32*)((char*)ctx->tv_parts.p + t0 * (size_t)blocks * rec);
     launch_tv_sum<Fq>(ctx->s_tv, (const u32*)vecs[0].key->d_table, nv, ptrs, probes, nn, oo, blocks, parts, (u32*)((char*)d_exc + t0 * EXC_B));
     // (the caller waits for these sums: the quad-cooperative fold, as for an exposed MSM tail)
-    launch_fold_quad<Fq>(ctx->s_tv, nv, parts, blocks, (u32*)((char*)ctx->tv_out.p + t0 * rec), nullptr);
+    launch_fold<Fq>(ctx->s_tv, true, nv, parts, blocks, (u32*)((char*)ctx->tv_out.p + t0 * rec), nullptr);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(ctx->tv_pinned, ctx->tv_out.p, tv.size() * (rec + EXC_B), hipMemcpyDeviceToHost, ctx->s_tv));

@@ -541,16 +541,11 @@ int ipa_jump_fold_impl(amsm_ctx* ctx, const amsm_bases* key, size_t log_key, con
   memset(&g, 0, sizeof(g));
   g.nb = JUMP_NB;
   g.n_sets = (u32)(2 * n_rep * m0);
-  g.red_s = 2;
-  g.red_threads = JUMP_NB / 2;
-  const u32 red_blocks = cdiv(g.red_threads * 4u, 256);
+  const msel::TailPlan tp = tail_plan_of(g, Place::LONE);  // (the caller waits: the fused quad tail, two buckets per logical lane)
   Slot* sl = &ctx->slot[0];
   if (sl->busy) return AMSM_E_INVALID_ARG;
   TRY(ensure(sl->buckets, (size_t)g.n_sets * JUMP_NB * rec));
-  TRY(ensure(sl->red_out, (size_t)g.n_sets * red_blocks * rec));
-  TRY(ensure(sl->fold_out, (size_t)g.n_sets * rec + 64));
-  TRY(ensure_pinned(sl, (size_t)g.n_sets * rec + 64));
-  TRY(ensure_red_ticket(ctx, sl, g.n_sets));
+  TRY(reserve_tail<Fq>(ctx, sl, g.n_sets, tp));
   const size_t words = sorted.size() + list_off.size() + list_slot.size();
   TRY(ensure(sl->vals_a, words * 4 + 64));
   u32* d_ent = (u32*)sl->vals_a.p;
@@ -565,8 +560,8 @@ int ipa_jump_fold_impl(amsm_ctx* ctx, const amsm_bases* key, size_t log_key, con
     if (key->ready) HIP_TRY(hipStreamWaitEvent(st, key->ready, 0));
     launch_ipa_jump_accum<Fq>(st, key->d_table, d_ent, d_off, d_slot, n_lists, (u32)m0, JUMP_NB, (u32*)sl->buckets.p);
   }
-  launch_bucket_reduce_fold_quad<Fq>(st, red_blocks, (const u32*)sl->buckets.p, g, (u32*)sl->red_out.p, (u32*)sl->red_ticket.p,
-                                     (u32*)sl->fold_out.p, nullptr, (u32*)sl->h_pinned);
+  launch_tail<Fq>(st, tp, (const u32*)sl->buckets.p, g, (u32*)sl->red2_rc.p, (u32*)sl->red_out.p, (u32*)sl->red_ticket.p, (u32*)sl->fold_out.p,
+                  nullptr, (u32*)sl->h_pinned);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));  // (the host vectors above were pageable: their copies are done as well)
   const u32* h = (const u32*)sl->h_pinned;

@@ -22,7 +22,6 @@ namespace tune {
 constexpr int K0_MAX = 32;                 // largest chunk of accumulate L0 (24 -> 805, 32 -> 811-816 M pairs/s in 2^20 batches)
 constexpr amsm::u32 K1 = 1024;             // buckets with more partials than this go to the workgroup-per-bucket path (extreme skew)
 constexpr size_t ONESHOT_RANGE = (size_t)1 << 19;  // amsm_msm_oneshot: pairs per range (upload of range j + 1 beside the MSM of range j)
-constexpr int TAIL_QUAD_HIDDEN_LOG2 = 17;  // bucket tables up to 2^this take the quad tail inside a batch too (2^16 234 -> 283 M pairs/s)
 }  // namespace tune
 
 // One range of an MSM that is longer than the 2^c-pair window of its bucket-per-lane key (round 5; 2^22 pairs over the 20-bit key:
@@ -49,13 +48,8 @@ struct MsmJob {
   Share share;                     // buf >= 0: one range of a shared bucket set
 };
 
-// Where an MSM stands in its call (msm_enqueue): whether anybody waits for its tail, and whether anything can overlap with it
-enum class Place {
-  LONE,         // the only MSM of a blocking call: exposed tail, the whole chain on the caller's stream
-  BATCH_LAST,   // the last MSM of a batch (or a re-run inside one): exposed tail, on the per-stage streams
-  BATCH_INNER,  // another MSM is queued behind it: its tail is hidden behind that one's accumulation
-};
-inline Place place_of(size_t i, size_t count) { return count == 1 ? Place::LONE : (i + 1 == count ? Place::BATCH_LAST : Place::BATCH_INNER); }
+using msel::Place;  // where an MSM stands in its call (msm_select.h: the tail depends on it)
+using msel::place_of;
 
 // One pipeline slot = one stream + one private workspace, so two MSMs of a batch can be in flight:
 // the latency-bound tail of MSM i (fold partials, bucket reduce) overlaps the throughput-bound head of
@@ -70,8 +64,8 @@ struct Slot {  // buffers and events of one MSM in flight (the streams belong to
   DevBuf keys_a, keys_b, vals_a, vals_b, start, items, item_off, partials, buckets, red_out, fold_out, heavy, misc,
       sort_tmp, scan_tmp, prep_small, heavy_scratch;
   DevBuf red2_rc;  // row / column sums of the bucket reduction (k_red2_sums)
-  DevBuf red_ticket;  // one arrival counter per bucket set (k_bucket_reduce_fold_quad; zeroed at allocation, left clear by the kernel)
-  DevBuf ds_flags;  // the direct sum's two flag words (zeroed at allocation, left clear by k_fold_quad)
+  DevBuf red_ticket;  // one arrival counter per bucket set (k_bucket_reduce<QUAD, FUSED>; zeroed at allocation, left clear by the kernel)
+  DevBuf ds_flags;  // the direct sum's two flag words (zeroed at allocation, left clear by k_fold)
   DevBuf bpl_grp, bpl_order;  // bucket-per-lane pipeline: group headers, bucket order (entries live in vals_a / vals_b)
   // the MSM this slot carries (with the caller's key, not the twin msm_plan resolves), kept until it is collected: a bucket-per-lane
   // or bucket-split MSM whose prep reports a skewed input is re-run from here through the chunked pipeline (msm_collect)
@@ -211,7 +205,6 @@ struct amsm_ctx {
   int direct_max_log2 = 15;         // keys of up to 2^this generators carry that table (AMSM_DIRECT_SUM_MAX_LOG2; 0: none)
   unsigned direct_rr = 0;           // which stream the next direct sum of a batch takes
   bool host_halves = true;  // AMSM_HOST_HALVES=0: a lone host slice over a 20-bit key as ONE range (upload, then the MSM: rounds 1-5; A/B)
-  bool fused_fold = true;  // AMSM_FUSED_FOLD=0: the quad bucket reduction and its fold as two launches (round 5's tail; A/B)
   bool bpl_probe = true;  // sample every candidate vector's digits first and send skewed ones straight to the chunked pipeline
                           // (AMSM_BPL_PROBE=0: find out from the prep's overflow flag only -- the safety net either way)
   unsigned long long n_bpl = 0, n_bpl_fallbacks = 0;  // MSMs that took it / that were re-run chunked (skewed digits)

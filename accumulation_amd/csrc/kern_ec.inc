@@ -92,58 +92,45 @@ template <>
 u32 accum_l2_slices<AMSM_FQ>() {
   return L2_SLICES;
 }
+// the bare fold over ready partial records (the tail's last launch; the direct sum's and the two-valued sums' only one)
 template <>
-void launch_bucket_reduce<AMSM_FQ>(hipStream_t st, u32 red_blocks, const u32* buckets, MsmGeom g, u32* out) {
-  hipLaunchKernelGGL((k_bucket_reduce<FQD>), dim3(red_blocks, g.n_sets), dim3(256), 0, st, buckets, g, out);
+void launch_fold<AMSM_FQ>(hipStream_t st, bool quad, u32 n_sets, const u32* in, u32 n_per_set, u32* out, const u32* flags, u32* mirror,
+                          bool clear_flags) {
+  // quad: four waves when there are enough records to share out (msm_kernels.h), one otherwise
+  if (quad)
+    hipLaunchKernelGGL((k_fold<FQD, true>), dim3(n_sets), dim3(n_per_set > 32u ? 256 : 64), 0, st, in, n_per_set, out, flags, mirror,
+                       clear_flags ? 1u : 0u);
+  else hipLaunchKernelGGL((k_fold<FQD, false>), dim3(n_sets), dim3(64), 0, st, in, n_per_set, out, flags, mirror, 0u);
 }
-// rows / columns form of the bucket reduction (msm_kernels.h: k_red2_sums + k_red2_weighted); returns the partial records per
-// set it leaves in `out` (for launch_fold[_quad]).  rc: n_sets * (nb / 1024 + 1024) records of scratch.  nb a multiple of 1024.
+// The tail of an MSM as msm_select.h planned it (tail_plan: the form, the grids and what the buffers hold): the buckets of g.n_sets sets
+// of g.nb to one exported record per set in `out`, mirrored.  rc: t.rc_records records (RED2), partial: g.n_sets * t.partials records,
+// ticket: g.n_sets zeroed words (where t.ticket).
 template <>
-u32 launch_bucket_reduce2<AMSM_FQ>(hipStream_t st, const u32* buckets, MsmGeom g, bool quad, bool latency, u32* rc, u32* out) {
-  Red2Geom r;
-  r.A = g.nb / 1024u;
-  // latency (an exposed tail, or a small table whose chain would bound a batch): short strips, wide butterflies; otherwise long
-  // strips -- fewer butterfly additions (a butterfly level costs every lane of the wave one addition)
-  r.gw = latency ? 64u : 16u;
-  r.gc = std::min<u32>(r.A, latency ? 64u : 16u);
-  u32 p2 = 1;
-  while (p2 * 2u <= r.gc) p2 *= 2u;
-  r.gc = p2;
-  while (r.A % r.gc) r.gc >>= 1;  // (A is a power of two for every geometry that gets here; defensive)
-  r.row_waves = cdiv_(r.A, 64u / r.gw);
-  r.col_waves = cdiv_(1024u, 64u / r.gc);
-  hipLaunchKernelGGL((k_red2_sums<FQD>), dim3(cdiv_(r.row_waves + r.col_waves, 4), g.n_sets), dim3(256), 0, st, buckets, g.nb, r, rc);
-  const u32 items = r.A + 1024u, blocks = cdiv_(items * (quad ? 4u : 1u), 256);
-  if (quad) hipLaunchKernelGGL((k_red2_weighted<FQD, true>), dim3(blocks, g.n_sets), dim3(256), 0, st, rc, r.A, out);
-  else hipLaunchKernelGGL((k_red2_weighted<FQD, false>), dim3(blocks, g.n_sets), dim3(256), 0, st, rc, r.A, out);
-  return blocks;
-}
-template <>
-void launch_fold<AMSM_FQ>(hipStream_t st, u32 n_sets, const u32* in, u32 n_per_set, u32* out, const u32* flags, u32* mirror) {
-  hipLaunchKernelGGL((k_fold<FQD>), dim3(n_sets), dim3(64), 0, st, in, n_per_set, out, flags, mirror);
-}
-template <>
-void launch_bucket_reduce_quad<AMSM_FQ>(hipStream_t st, u32 red_blocks, const u32* buckets, MsmGeom g, u32* out) {
-  hipLaunchKernelGGL((k_bucket_reduce_quad<FQD>), dim3(red_blocks, g.n_sets), dim3(256), 0, st, buckets, g, out);
-}
-template <>
-void launch_bucket_reduce_fold_quad<AMSM_FQ>(hipStream_t st, u32 red_blocks, const u32* buckets, MsmGeom g, u32* partial, u32* ticket,
-                                             u32* out, const u32* flags, u32* mirror) {
-  hipLaunchKernelGGL((k_bucket_reduce_fold_quad<FQD>), dim3(red_blocks, g.n_sets), dim3(256), 0, st, buckets, g, partial, ticket, out, flags,
-                     mirror);
+void launch_tail<AMSM_FQ>(hipStream_t st, const msel::TailPlan& t, const u32* buckets, MsmGeom g, u32* rc, u32* partial, u32* ticket,
+                          u32* out, const u32* flags, u32* mirror) {
+  g.red_s = t.red_s;
+  g.red_threads = t.red_threads;
+  const dim3 grid(t.partials, g.n_sets);
+  if (t.form == msel::FUSED_QUAD) {
+    hipLaunchKernelGGL((k_bucket_reduce<FQD, true, true>), grid, dim3(256), 0, st, buckets, g, partial, ticket, out, flags, mirror);
+    return;
+  }
+  if (t.form == msel::RED2) {  // row / column sums, then their small multiples
+    const Red2Geom r = msel::red2_geom(g.nb, t.latency);
+    hipLaunchKernelGGL((k_red2_sums<FQD>), dim3(cdiv_(r.row_waves + r.col_waves, 4), g.n_sets), dim3(256), 0, st, buckets, g.nb, r, rc);
+    if (t.quad) hipLaunchKernelGGL((k_red2_weighted<FQD, true>), grid, dim3(256), 0, st, rc, r.A, partial);
+    else hipLaunchKernelGGL((k_red2_weighted<FQD, false>), grid, dim3(256), 0, st, rc, r.A, partial);
+  } else {
+    hipLaunchKernelGGL((k_bucket_reduce<FQD, false, false>), grid, dim3(256), 0, st, buckets, g, partial, (u32*)nullptr, (u32*)nullptr,
+                       (const u32*)nullptr, (u32*)nullptr);
+  }
+  launch_fold<AMSM_FQ>(st, t.quad, g.n_sets, partial, t.partials, out, flags, mirror, false);
 }
 template <>
 void launch_ipa_jump_accum<AMSM_FQ>(hipStream_t st, const u32* table, const u32* entries, const u32* list_off, const u32* list_slot,
                                     u32 n_lists, u32 m0, u32 nb, u32* buckets) {
   hipLaunchKernelGGL((k_ipa_jump_accum<FQD>), dim3(n_lists, m0 / 64u), dim3(64 * JUMP_WAVES), 0, st, table, entries, list_off, list_slot, m0,
                      nb, buckets);
-}
-template <>
-void launch_fold_quad<AMSM_FQ>(hipStream_t st, u32 n_sets, const u32* in, u32 n_per_set, u32* out, const u32* flags, u32* mirror,
-                               bool clear_flags) {
-  // four waves when there are enough records to share out (msm_kernels.h), one otherwise
-  hipLaunchKernelGGL((k_fold_quad<FQD>), dim3(n_sets), dim3(n_per_set > 32u ? 256 : 64), 0, st, in, n_per_set, out, flags, mirror,
-                     clear_flags ? 1u : 0u);
 }
 // Points per lane of the batched XYZZ -> affine conversion: 4 (one inversion per 4 points; 8 would starve the GPU of
 // lanes at the sizes that matter).  Below BATCH_AFFINE_MIN points the kernels convert in place, one inversion each.

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "msm_select.h"
 #include "msm_types.h"
 
 namespace amsm {
@@ -27,29 +28,22 @@ void launch_accum_l2(hipStream_t st, const u32* partials, const u32* items, cons
                      const u32* heavy_count, const u32* heavy_list, u32* scratch, u32* buckets);
 template <class Fq>
 u32 accum_l2_slices();  // scratch records per heavy bucket
+// The tail of an MSM (msm_kernels.h: k_bucket_reduce / k_red2_* / k_fold) as msel::tail_plan planned it: form, grids and buffer sizes
+// all come from the plan.  rc: t.rc_records records of scratch (RED2), partial: g.n_sets * t.partials records, ticket: g.n_sets zeroed
+// words (t.ticket), out: g.n_sets records + the two flag words (flags may be null), mirror: the same in page-locked host memory.
 template <class Fq>
-void launch_bucket_reduce(hipStream_t st, u32 red_blocks, const u32* buckets, MsmGeom g, u32* out);
-// round 4: rows / columns form (msm_kernels.h: k_red2_sums, k_red2_weighted): nb a multiple of 1024; rc = n_sets * (nb / 1024 +
-// 1024) scratch records; returns the partial records per set left in `out` (at most 4 * (nb / 1024 + 1024) / 256 + 1)
+void launch_tail(hipStream_t st, const msel::TailPlan& t, const u32* buckets, MsmGeom g, u32* rc, u32* partial, u32* ticket, u32* out,
+                 const u32* flags, u32* host_mirror);
+// the bare fold of n_per_set ready partial records per set; quad: a quad of lanes per logical lane (ec.h: xyzz_add_quad).
+// flags (may be null): two words copied behind the n_sets records (out needs 8 bytes more); clear_flags (quad only): the two words are
+// zeroed once they have been copied out
 template <class Fq>
-u32 launch_bucket_reduce2(hipStream_t st, const u32* buckets, MsmGeom g, bool quad, bool latency, u32* rc, u32* out);
-template <class Fq>
-// flags (may be null): two words copied behind the n_sets records (out needs 8 bytes more)
-void launch_fold(hipStream_t st, u32 n_sets, const u32* in, u32 n_per_set, u32* out, const u32* flags, u32* host_mirror = nullptr);
-// the same two kernels with a quad of lanes per logical lane (ec.h: xyzz_add_quad): red_blocks = 4x
-template <class Fq>
-void launch_bucket_reduce_quad(hipStream_t st, u32 red_blocks, const u32* buckets, MsmGeom g, u32* out);
-// round 6: both in one launch (msm_kernels.h: k_bucket_reduce_fold_quad); partial: n_sets * red_blocks records, ticket: n_sets zeroed words
-template <class Fq>
-void launch_bucket_reduce_fold_quad(hipStream_t st, u32 red_blocks, const u32* buckets, MsmGeom g, u32* partial, u32* ticket, u32* out,
-                                    const u32* flags, u32* host_mirror);
+void launch_fold(hipStream_t st, bool quad, u32 n_sets, const u32* in, u32 n_per_set, u32* out, const u32* flags, u32* host_mirror = nullptr,
+                 bool clear_flags = false);
 // round 6: the jump fold of an IPA opening (msm_kernels.h: k_ipa_jump_accum): n_lists lists, m0 (a multiple of 64) outputs
 template <class Fq>
 void launch_ipa_jump_accum(hipStream_t st, const u32* table, const u32* entries, const u32* list_off, const u32* list_slot, u32 n_lists,
                            u32 m0, u32 nb, u32* buckets);
-template <class Fq>
-void launch_fold_quad(hipStream_t st, u32 n_sets, const u32* in, u32 n_per_set, u32* out, const u32* flags, u32* host_mirror = nullptr,
-                      bool clear_flags = false);  // clear_flags: the two words are zeroed once they have been copied out
 template <class Fq>
 // level = 2^c * mul_m * (level - 1); mul_m = 0 / 1: no small multiple (power-of-two windows)
 void launch_precompute_level(hipStream_t st, u32* table, u32 stride, u32 level, u32 c, u32* xyzz_scratch);
@@ -58,7 +52,7 @@ template <class Fq>
 void launch_precompute_all_levels(hipStream_t st, u32* table, u32 n, u32 c, u32 W, u32* xyzz_scratch);
 // Direct sum (msm_kernels.h k_direct_sum): the 512-points-per-generator table of a small key from its window table (W levels of
 // plain c-bit windows, device radix), built in slabs of `slab_windows` of its 64 four-bit windows (xyzz_scratch: 8 * slab_windows * n
-// records), and one MSM as cdiv(n * 64 / m, 256) partial records (returned) for launch_fold_quad
+// records), and one MSM as cdiv(n * 64 / m, 256) partial records (returned) for launch_fold
 template <class Fq>
 void launch_ds_table(hipStream_t st, const u32* win_table, u32 n, u32 c, u32 W, u32* xyzz_scratch, u32 slab_windows, u32* table);
 // nv <= DS_BATCH MSMs over the key in one launch: MSM v's `blocks` records (the return value, sized by the longest vector) at

@@ -23,6 +23,7 @@
 // and the reduce stage shrinks W-fold.
 #pragma once
 #include "ec.h"
+#include "msm_select.h"
 #include "msm_types.h"
 #include "rng.h"
 
@@ -381,21 +382,79 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// Workgroup (256 lanes = 4 waves) reduction: wave shuffles, then 4 records through LDS.
-// lds must hold 4 XYZZ records (4 * 4*W u32).  Result valid in lane 0 of the workgroup.
+// ---- quad-cooperative tail (ec.h: xyzz_add_quad / xyzz_dbl_quad): logical lane = an aligned quad of lanes ----
+// butterfly over the 16 quads of a wave; every quad ends with the wave's sum
 template <class Fq>
-AMSM_DEV void block_reduce_xyzz(XYZZ<Fq>& acc, u32* lds) {
-  wave_reduce_xyzz<Fq>(acc);
-  u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) xyzz_store<Fq>(lds, wave, acc);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (u32 w = 1; w < (blockDim.x >> 6); w++) {
-      XYZZ<Fq> o = xyzz_load<Fq>(lds, w);
-      xyzz_add<Fq>(acc, o);
+AMSM_DEV void wave_reduce_xyzz_quad(XYZZ<Fq>& acc) {
+#pragma unroll 1
+  for (int m = 32; m >= 4; m >>= 1) {
+    XYZZ<Fq> o;
+#pragma unroll
+    for (int i = 0; i < Fq::L; i++) {
+      o.x.v[i] = __shfl_xor(acc.x.v[i], m, 64);
+      o.y.v[i] = __shfl_xor(acc.y.v[i], m, 64);
+      o.zz.v[i] = __shfl_xor(acc.zz.v[i], m, 64);
+      o.zzz.v[i] = __shfl_xor(acc.zzz.v[i], m, 64);
     }
+    bool low = (threadIdx.x & m) == 0;  // both quads add in the same order
+    XYZZ<Fq> a = low ? acc : o;
+    XYZZ<Fq> b2 = low ? o : acc;
+    xyzz_add_quad<Fq>(a, b2);
+    acc = a;
   }
 }
+
+// Lane policy of the tail kernels: a logical lane is ONE lane, or (QUAD) an aligned quad of lanes that shares every point operation
+// (the tail of a blocking MSM call is a chain of ~45 dependent point operations on a few waves: 0.24 ms; the quad schedule cuts the
+// depth of each).  Quad grids are 4x the one-lane ones.
+template <bool QUAD>
+struct Lanes {
+  static constexpr u32 SHIFT = QUAD ? 2u : 0u;  // logical lane = hardware lane >> SHIFT
+  template <class Fq>
+  static AMSM_DEV void add(XYZZ<Fq>& acc, const XYZZ<Fq>& q) {
+    if constexpr (QUAD) xyzz_add_quad<Fq>(acc, q);
+    else xyzz_add<Fq>(acc, q);
+  }
+  template <class Fq>
+  static AMSM_DEV XYZZ<Fq> dbl(const XYZZ<Fq>& p) {
+    if constexpr (QUAD) return xyzz_dbl_quad<Fq>(p);
+    else return xyzz_dbl<Fq>(p);
+  }
+  // k * p for a small non-negative integer k (double-and-add, MSB first)
+  template <class Fq>
+  static AMSM_DEV XYZZ<Fq> mul_small(const XYZZ<Fq>& p, u32 k) {
+    XYZZ<Fq> acc = xyzz_inf<Fq>();
+    if (k == 0) return acc;
+    int top = 31 - __clz(k);
+    for (int i = top; i >= 0; i--) {
+      acc = dbl(acc);
+      if ((k >> i) & 1) add(acc, p);
+    }
+    return acc;
+  }
+  // every logical lane of a wave ends with the wave's sum
+  template <class Fq>
+  static AMSM_DEV void wave_reduce(XYZZ<Fq>& acc) {
+    if constexpr (QUAD) wave_reduce_xyzz_quad<Fq>(acc);
+    else wave_reduce_xyzz<Fq>(acc);
+  }
+  // Workgroup (256 lanes = 4 waves) reduction: wave shuffles, then 4 records through LDS.
+  // lds must hold 4 XYZZ records (4 * 4*W u32).  Result valid in the first logical lane of the workgroup.
+  template <class Fq>
+  static AMSM_DEV void block_reduce(XYZZ<Fq>& acc, u32* lds) {
+    wave_reduce(acc);
+    u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) xyzz_store<Fq>(lds, wave, acc);
+    __syncthreads();
+    if (QUAD ? threadIdx.x < 4u : threadIdx.x == 0) {
+      for (u32 w = 1; w < (blockDim.x >> 6); w++) {
+        XYZZ<Fq> o = xyzz_load<Fq>(lds, w);
+        add(acc, o);
+      }
+    }
+  }
+};
+
 
 // accumulate L2: heavy buckets (more than K1 partials: skewed digit distributions) in two steps so that
 // the sequential chain per lane stays short whatever the skew: (a) L2_SLICES workgroups per heavy bucket each sum a
@@ -420,7 +479,7 @@ __global__ void __launch_bounds__(256)
       XYZZ<Fq> p = xyzz_load<Fq>(partials, off + k);
       xyzz_add<Fq>(acc, p);
     }
-    block_reduce_xyzz<Fq>(acc, lds);
+    Lanes<false>::block_reduce(acc, lds);
     if (threadIdx.x == 0) xyzz_store<Fq>(scratch, (size_t)h * L2_SLICES + sidx, acc);
     __syncthreads();
   }
@@ -438,90 +497,154 @@ __global__ void __launch_bounds__(64)
   }
 }
 
-// ---- quad-cooperative tail (ec.h: xyzz_add_quad / xyzz_dbl_quad): logical lane = an aligned quad of lanes ----
-// butterfly over the 16 quads of a wave; every quad ends with the wave's sum
-template <class Fq>
-AMSM_DEV void wave_reduce_xyzz_quad(XYZZ<Fq>& acc) {
-#pragma unroll 1
-  for (int m = 32; m >= 4; m >>= 1) {
-    XYZZ<Fq> o;
-#pragma unroll
-    for (int i = 0; i < Fq::L; i++) {
-      o.x.v[i] = __shfl_xor(acc.x.v[i], m, 64);
-      o.y.v[i] = __shfl_xor(acc.y.v[i], m, 64);
-      o.zz.v[i] = __shfl_xor(acc.zz.v[i], m, 64);
-      o.zzz.v[i] = __shfl_xor(acc.zzz.v[i], m, 64);
-    }
-    bool low = (threadIdx.x & m) == 0;  // both quads add in the same order
-    XYZZ<Fq> a = low ? acc : o;
-    XYZZ<Fq> b2 = low ? o : acc;
-    xyzz_add_quad<Fq>(a, b2);
-    acc = a;
-  }
-}
-// lds: one XYZZ record per wave of the workgroup.  Result valid in the first quad of the workgroup.
-template <class Fq>
-AMSM_DEV void block_reduce_xyzz_quad(XYZZ<Fq>& acc, u32* lds) {
-  wave_reduce_xyzz_quad<Fq>(acc);
-  u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) xyzz_store<Fq>(lds, wave, acc);
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    for (u32 w = 1; w < (blockDim.x >> 6); w++) {
-      XYZZ<Fq> o = xyzz_load<Fq>(lds, w);
-      xyzz_add_quad<Fq>(acc, o);
-    }
-  }
-}
-template <class Fq>
-AMSM_DEV XYZZ<Fq> xyzz_mul_small_quad(const XYZZ<Fq>& p, u32 k) {
-  XYZZ<Fq> acc = xyzz_inf<Fq>();
-  if (k == 0) return acc;
-  int top = 31 - __clz(k);
-  for (int i = top; i >= 0; i--) {
-    acc = xyzz_dbl_quad<Fq>(acc);
-    if ((k >> i) & 1) xyzz_add_quad<Fq>(acc, p);
-  }
-  return acc;
-}
-
-// k * p for a small non-negative integer k (double-and-add, MSB first)
-template <class Fq>
-AMSM_DEV XYZZ<Fq> xyzz_mul_small(const XYZZ<Fq>& p, u32 k) {
-  XYZZ<Fq> acc = xyzz_inf<Fq>();
-  if (k == 0) return acc;
-  int top = 31 - __clz(k);
-  for (int i = top; i >= 0; i--) {
-    acc = xyzz_dbl<Fq>(acc);
-    if ((k >> i) & 1) xyzz_add<Fq>(acc, p);
-  }
-  return acc;
-}
-
 // ---------------------------------------------------------------------------------------------
-// reduce: per set, sum_{j=1..nb} j * bucket[j-1].  Lane t owns buckets [t*s, (t+1)*s).
-// grid = (red_threads/256 or 1, n_sets).  One partial per workgroup: out[set*gridDim.x + blockIdx.x].
+// The tail: per set, sum_{j=1..nb} j * bucket[j-1], folded to one record that leaves the device.  Three routines shared by its kernels,
+// each instantiation's schedule an explicit parameter (they differ as they were measured; msm_select.h: tail_plan picks the form).
 // ---------------------------------------------------------------------------------------------
-template <class Fq>
-__global__ void __launch_bounds__(256)
-    k_bucket_reduce(const u32* __restrict__ buckets, MsmGeom g, u32* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) u32 lds[4 * 4 * Fq::W];
-  u32 set = blockIdx.y;
-  u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+// Running sums: logical lane t owns buckets [t*s, (t+1)*s) of its set and returns their weighted sum (lane past the set: the
+// identity).  PREFETCH: the next bucket is requested before this one's two additions.
+template <class Fq, bool QUAD, bool PREFETCH>
+AMSM_DEV XYZZ<Fq> reduce_leaf(const u32* __restrict__ buckets, const MsmGeom& g, u32 set, u32 t) {
+  using L = Lanes<QUAD>;
   XYZZ<Fq> total = xyzz_inf<Fq>();
   if (t < g.red_threads) {
-    u32 lo = t * g.red_s;
+    const u32 lo = t * g.red_s;
     XYZZ<Fq> run = xyzz_inf<Fq>(), sum = xyzz_inf<Fq>();
+    XYZZ<Fq> bk, nx;
+    if constexpr (PREFETCH) bk = xyzz_load<Fq>(buckets, (size_t)set * g.nb + lo + g.red_s - 1);
     for (int k = (int)g.red_s - 1; k >= 0; k--) {
-      XYZZ<Fq> bk = xyzz_load<Fq>(buckets, (size_t)set * g.nb + lo + k);
-      xyzz_add<Fq>(run, bk);
-      xyzz_add<Fq>(sum, run);
+      if constexpr (PREFETCH) {
+        nx = bk;
+        if (k > 0) nx = xyzz_load<Fq>(buckets, (size_t)set * g.nb + lo + k - 1);
+      } else {
+        bk = xyzz_load<Fq>(buckets, (size_t)set * g.nb + lo + k);
+      }
+      L::add(run, bk);
+      L::add(sum, run);
+      if constexpr (PREFETCH) bk = nx;
     }
-    total = xyzz_mul_small<Fq>(run, lo);
-    xyzz_add<Fq>(total, sum);
+    total = L::mul_small(run, lo);
+    L::add(total, sum);
   }
-  block_reduce_xyzz<Fq>(total, lds);
-  if (threadIdx.x == 0) xyzz_store<Fq>(out, (size_t)set * gridDim.x + blockIdx.x, total);
+  return total;
+}
+// Fold of records: the sum of in[base + k], k = k0, k0 + nl, .. < n (logical lane k0 of nl).  PREFETCH: the next record is requested
+// before this one's addition.
+template <class Fq, bool QUAD, bool PREFETCH>
+AMSM_DEV XYZZ<Fq> fold_records(const u32* in, size_t base, u32 n, u32 k0, u32 nl) {
+  XYZZ<Fq> acc = xyzz_inf<Fq>();
+  if constexpr (PREFETCH) {
+    XYZZ<Fq> p = k0 < n ? xyzz_load<Fq>(in, base + k0) : acc;
+    for (u32 k = k0; k < n; k += nl) {
+      XYZZ<Fq> nx = p;
+      if (k + nl < n) nx = xyzz_load<Fq>(in, base + k + nl);
+      Lanes<QUAD>::add(acc, p);
+      p = nx;
+    }
+  } else {
+    for (u32 k = k0; k < n; k += nl) {
+      const XYZZ<Fq> p = xyzz_load<Fq>(in, base + k);
+      Lanes<QUAD>::add(acc, p);
+    }
+  }
+  return acc;
+}
+// Emit (one lane): the folded record idx of `count` leaves the device -- C-ABI Montgomery radix from here on (identity on saturated
+// fields) -- into out[idx].  mirror (may be null): page-locked HOST memory that receives the same record and flag words (round 4: the
+// result used to leave by a 128-byte copy command, which queues behind whatever the copy engines are doing -- a 0.6 ms scalar upload of
+// a host-slice batch -- and held the slot's `done` event back).  flags (may be null): the MSM's two flag words ride behind the records:
+// one copy takes both to the host; clear_flags: they are left zeroed for the slot's next MSM (the direct sum's: no fill command per MSM).
+template <class Fq>
+AMSM_DEV void emit_record(const XYZZ<Fq>& acc, u32 idx, u32 count, u32* __restrict__ out, const u32* __restrict__ flags,
+                          u32* __restrict__ mirror, bool clear_flags) {
+  XYZZ<Fq> e;
+  e.x = fe_export<Fq>(acc.x);
+  e.y = fe_export<Fq>(acc.y);
+  e.zz = fe_export<Fq>(acc.zz);
+  e.zzz = fe_export<Fq>(acc.zzz);
+  xyzz_store<Fq>(out, idx, e);
+  if (mirror) xyzz_store<Fq>(mirror, idx, e);
+  if (flags && idx == 0) {
+    const u32 f0 = flags[0], f1 = flags[1];
+    out[(size_t)count * (4 * Fq::W)] = f0;
+    out[(size_t)count * (4 * Fq::W) + 1] = f1;
+    if (mirror) {
+      mirror[(size_t)count * (4 * Fq::W)] = f0;
+      mirror[(size_t)count * (4 * Fq::W) + 1] = f1;
+    }
+    if (clear_flags) {
+      const_cast<u32*>(flags)[0] = 0;
+      const_cast<u32*>(flags)[1] = 0;
+    }
+  }
+  if (mirror) __threadfence_system();
+}
+
+// reduce: grid = (logical lanes * lanes per logical lane / 256, n_sets).  One partial per workgroup: partial[set*gridDim.x + blockIdx.x].
+// FUSED (round 6): the reduction and its fold as ONE launch.  The blocks of a set leave their partial records as before and
+// take a ticket; the LAST block of the set to arrive folds the set's gridDim.x records, exports the
+// sum to the C-ABI radix, mirrors it (and, for set 0, the MSM's flag words) into page-locked memory and clears the ticket for
+// the slot's next MSM.  What it saves is the dependent launch between two latency chains -- the second kernel's dispatch, its
+// drain and the ~5 us hand-over -- in every blocking MSM of up to 2^17 buckets and in every round of an IPA opening.
+// partial: n_sets * gridDim.x records of scratch; ticket: n_sets words, zero on entry.  Not FUSED: ticket, out, flags, mirror unused.
+// Schedules: the one-lane leaf does not prefetch, the quad leaf does; the fused fold does not.
+template <class Fq, bool QUAD, bool FUSED>
+__global__ void __launch_bounds__(256)
+    k_bucket_reduce(const u32* __restrict__ buckets, MsmGeom g, u32* partial, u32* __restrict__ ticket, u32* __restrict__ out,
+                    const u32* __restrict__ flags, u32* __restrict__ mirror) {
+  using L = Lanes<QUAD>;
+  __shared__ __attribute__((aligned(16))) u32 lds[4 * 4 * Fq::W];
+  const u32 set = blockIdx.y;
+  XYZZ<Fq> total = reduce_leaf<Fq, QUAD, /*PREFETCH=*/QUAD>(buckets, g, set, (blockIdx.x * blockDim.x + threadIdx.x) >> L::SHIFT);
+  L::block_reduce(total, lds);
+  if constexpr (!FUSED) {
+    if (threadIdx.x == 0) xyzz_store<Fq>(partial, (size_t)set * gridDim.x + blockIdx.x, total);
+  } else {
+    __shared__ u32 s_last;
+    if (threadIdx.x == 0) {
+      xyzz_store<Fq>(partial, (size_t)set * gridDim.x + blockIdx.x, total);
+      __threadfence();  // the record is visible device-wide before the ticket is
+      s_last = atomicAdd(ticket + set, 1u) == gridDim.x - 1u ? 1u : 0u;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();  // acquire: the other blocks' records (other XCDs' L2s) are read from memory
+    const u32 n = gridDim.x;
+    const u32* in = partial + (size_t)set * n * (4 * Fq::W);  // (written by other workgroups of THIS launch: read behind the fence above)
+    XYZZ<Fq> acc = xyzz_inf<Fq>();
+    if (n <= 4u) {
+      // a handful of records (the small sets of 8-bit windows: ONE): the first logical lane adds them one after the other -- the
+      // workgroup tree would be 7 more dependent additions on identities
+      if (threadIdx.x < (1u << L::SHIFT)) acc = fold_records<Fq, QUAD, /*PREFETCH=*/false>(in, 0, n, 0u, 1u);
+    } else {
+      acc = fold_records<Fq, QUAD, /*PREFETCH=*/false>(in, 0, n, threadIdx.x >> L::SHIFT, blockDim.x >> L::SHIFT);
+      __syncthreads();  // (lds is reused)
+      L::block_reduce(acc, lds);
+    }
+    if (threadIdx.x == 0) {
+      ticket[set] = 0;  // every record of the set has been read
+      emit_record<Fq>(acc, set, gridDim.y, out, flags, mirror, false);
+    }
+  }
+}
+
+// fold: workgroup b sums records [b*n, (b+1)*n) and emits out[b].  One lane per logical lane: ONE wave, lane-strided, no prefetch,
+// the shuffle butterfly.  QUAD (round 3): one or four waves (the launcher: four when there are enough records to share out) -- the
+// serial part of the fold drops from n / 16 to n / 64 additions per quad (n = 256 partial records after the reduction of a 2^19-bucket
+// set), prefetched, then the quad butterfly and one LDS step.  clear_flags: QUAD only (emit_record).
+template <class Fq, bool QUAD>
+__global__ void __launch_bounds__(QUAD ? 256 : 64) k_fold(const u32* __restrict__ in, u32 n, u32* __restrict__ out,
+                                                          const u32* __restrict__ flags, u32* __restrict__ mirror, u32 clear_flags) {
+  XYZZ<Fq> acc;
+  if constexpr (QUAD) {
+    __shared__ __attribute__((aligned(16))) u32 lds[4 * 4 * Fq::W];
+    acc = fold_records<Fq, true, /*PREFETCH=*/true>(in, (size_t)blockIdx.x * n, n, threadIdx.x >> 2, blockDim.x >> 2);
+    Lanes<true>::block_reduce(acc, lds);
+  } else {
+    acc = fold_records<Fq, false, /*PREFETCH=*/false>(in, (size_t)blockIdx.x * n, n, threadIdx.x, 64u);
+    wave_reduce_xyzz<Fq>(acc);
+  }
+  if (threadIdx.x == 0) emit_record<Fq>(acc, blockIdx.x, gridDim.x, out, flags, mirror, QUAD && clear_flags);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -535,14 +658,9 @@ __global__ void __launch_bounds__(256)
 //                    columns) or one column (strips of `srow` = A / gc consecutive rows, gc lanes), strip sequentially, then a
 //                    butterfly over the group -> rc[set][0 .. A) = R_a, rc[set][A .. A + 1024) = C_b
 //   k_red2_weighted  logical lane (a lane, or a quad) = one of the A + 1024 sums: its small multiple (1024 a: a 19-bit
-//                    double-and-add; b + 1), a workgroup reduction -> one partial record per workgroup, folded by k_fold[_quad]
+//                    double-and-add; b + 1), a workgroup reduction -> one partial record per workgroup, folded by k_fold
 // ---------------------------------------------------------------------------------------------
-struct Red2Geom {
-  u32 A;      // rows = nb / 1024
-  u32 gw;     // lanes per row group (power of two <= 64): row strips of 1024 / gw columns
-  u32 gc;     // lanes per column group (power of two <= 64, <= A): column strips of A / gc rows
-  u32 row_waves, col_waves;  // waves per set in each mode
-};
+using msel::Red2Geom;  // (msm_select.h: red2_geom -- its grid, checked without a GPU)
 // butterfly over aligned groups of `width` lanes (a power of two, runtime); every lane of a group ends with the group's sum
 template <class Fq>
 AMSM_DEV void group_reduce_xyzz_rt(XYZZ<Fq>& acc, u32 width) {
@@ -604,10 +722,9 @@ __global__ void __launch_bounds__(256) k_red2_weighted(const u32* __restrict__ r
   if (t < items) {
     const XYZZ<Fq> v = xyzz_load<Fq>(rc, (size_t)set * items + t);
     const u32 w = t < A ? t * 1024u : (t - A) + 1u;
-    total = QUAD ? xyzz_mul_small_quad<Fq>(v, w) : xyzz_mul_small<Fq>(v, w);
+    total = Lanes<QUAD>::mul_small(v, w);
   }
-  if (QUAD) block_reduce_xyzz_quad<Fq>(total, lds);
-  else block_reduce_xyzz<Fq>(total, lds);
+  Lanes<QUAD>::block_reduce(total, lds);
   if (threadIdx.x == 0) xyzz_store<Fq>(out, (size_t)set * gridDim.x + blockIdx.x, total);
 }
 
@@ -645,7 +762,7 @@ __global__ void __launch_bounds__(256) k_tv_sum(const u32* __restrict__ table, T
     const Affine<Fq> g = affine_export<Fq>(affine_load<Fq>(table, (size_t)base_off + j));
     affine_store<Fq>(o + 8, 0, g);
   }
-  block_reduce_xyzz<Fq>(acc, lds);
+  Lanes<false>::block_reduce(acc, lds);
   if (threadIdx.x == 0) xyzz_store<Fq>(out, (size_t)v * gridDim.x + blockIdx.x, acc);
 }
 
@@ -657,7 +774,7 @@ __global__ void __launch_bounds__(256) k_tv_sum(const u32* __restrict__ table, T
 // plain SUM of n * 64 * 15/16 table points: no buckets, hence no sort, no bucket reduction with its 2^(c-1)-fold weights, and no
 // dependence on the digit distribution (a constant vector costs what a uniform one does).  One launch sums them -- lane (g, i)
 // adds the points of scalar i's windows [g m, (g + 1) m) by mixed additions, two butterfly levels leave every quad of lanes
-// with its sum, the quad-cooperative tree (ec.h) takes the workgroup's 64 quads to one record -- and k_fold_quad adds the
+// with its sum, the quad-cooperative tree (ec.h) takes the workgroup's 64 quads to one record -- and k_fold<QUAD> adds the
 // workgroups' records.  Digits without a carry chain: s' = s + 0x0888...8 (an 8 under each of the 63 low windows), then digit
 // w = nibble w of s' - 8 in [-8, 7], the top window's nibble taken as it is (0 .. 8 for every s < 8.47 * 2^252, which covers
 // the canonical scalars of both fields; anything above is reported like a scalar that does not fit the other pipelines' windows).
@@ -746,195 +863,10 @@ __global__ void __launch_bounds__(256)
     }
   }
   group_reduce_xyzz<Fq, 4>(acc);  // one-lane additions: afterwards the four lanes of a quad hold the same sum
-  block_reduce_xyzz_quad<Fq>(acc, lds);
+  Lanes<true>::block_reduce(acc, lds);
   if (threadIdx.x == 0) xyzz_store<Fq>(partials, (size_t)blockIdx.y * gridDim.x + blockIdx.x, acc);
 }
 
-// fold: wave b sums records [b*n, (b+1)*n) (lane-strided + shuffle butterfly) and writes out[b] (C-ABI radix).
-// mirror (may be null): page-locked HOST memory that receives the same record and flag words (round 4: the result used to leave
-// by a 128-byte copy command, which queues behind whatever the copy engines are doing -- a 0.6 ms scalar upload of a host-slice
-// batch -- and held the slot's `done` event back)
-template <class Fq>
-__global__ void __launch_bounds__(64) k_fold(const u32* __restrict__ in, u32 n, u32* __restrict__ out,
-                                             const u32* __restrict__ flags, u32* __restrict__ mirror) {
-  XYZZ<Fq> acc = xyzz_inf<Fq>();
-  for (u32 k = threadIdx.x; k < n; k += 64) {
-    XYZZ<Fq> p = xyzz_load<Fq>(in, (size_t)blockIdx.x * n + k);
-    xyzz_add<Fq>(acc, p);
-  }
-  wave_reduce_xyzz<Fq>(acc);
-  if (threadIdx.x == 0) {
-    // the folded record leaves the device: C-ABI Montgomery radix from here on (identity on saturated fields)
-    XYZZ<Fq> e;
-    e.x = fe_export<Fq>(acc.x);
-    e.y = fe_export<Fq>(acc.y);
-    e.zz = fe_export<Fq>(acc.zz);
-    e.zzz = fe_export<Fq>(acc.zzz);
-    xyzz_store<Fq>(out, blockIdx.x, e);
-    if (mirror) xyzz_store<Fq>(mirror, blockIdx.x, e);
-    // the MSM's flag words ride behind the records: one copy takes both to the host
-    if (flags && blockIdx.x == 0) {
-      out[(size_t)gridDim.x * (4 * Fq::W)] = flags[0];
-      out[(size_t)gridDim.x * (4 * Fq::W) + 1] = flags[1];
-      if (mirror) {
-        mirror[(size_t)gridDim.x * (4 * Fq::W)] = flags[0];
-        mirror[(size_t)gridDim.x * (4 * Fq::W) + 1] = flags[1];
-      }
-    }
-    if (mirror) __threadfence_system();
-  }
-}
-
-// The same two kernels with a quad of lanes per logical lane (the tail of a blocking MSM call is a chain of ~45 dependent
-// point operations on a few waves: 0.24 ms; the quad schedule cuts the depth of each).  grid.x = 4x k_bucket_reduce's.
-template <class Fq>
-__global__ void __launch_bounds__(256)
-    k_bucket_reduce_quad(const u32* __restrict__ buckets, MsmGeom g, u32* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) u32 lds[4 * 4 * Fq::W];
-  u32 set = blockIdx.y;
-  u32 t = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;  // logical lane: owns buckets [t*s, (t+1)*s)
-  XYZZ<Fq> total = xyzz_inf<Fq>();
-  if (t < g.red_threads) {
-    u32 lo = t * g.red_s;
-    XYZZ<Fq> run = xyzz_inf<Fq>(), sum = xyzz_inf<Fq>();
-    XYZZ<Fq> bk = xyzz_load<Fq>(buckets, (size_t)set * g.nb + lo + g.red_s - 1);
-    for (int k = (int)g.red_s - 1; k >= 0; k--) {
-      XYZZ<Fq> nx = bk;  // the next bucket is requested before this one's two additions
-      if (k > 0) nx = xyzz_load<Fq>(buckets, (size_t)set * g.nb + lo + k - 1);
-      xyzz_add_quad<Fq>(run, bk);
-      xyzz_add_quad<Fq>(sum, run);
-      bk = nx;
-    }
-    total = xyzz_mul_small_quad<Fq>(run, lo);
-    xyzz_add_quad<Fq>(total, sum);
-  }
-  block_reduce_xyzz_quad<Fq>(total, lds);
-  if (threadIdx.x == 0) xyzz_store<Fq>(out, (size_t)set * gridDim.x + blockIdx.x, total);
-}
-// Round 6: k_bucket_reduce_quad and k_fold_quad as ONE launch.  The blocks of a set leave their partial records as before and
-// take a ticket; the LAST block of the set to arrive folds the set's gridDim.x records (the quad fold's schedule), exports the
-// sum to the C-ABI radix, mirrors it (and, for set 0, the MSM's flag words) into page-locked memory and clears the ticket for
-// the slot's next MSM.  What it saves is the dependent launch between two latency chains -- the second kernel's dispatch, its
-// drain and the ~5 us hand-over -- in every blocking MSM of up to 2^17 buckets and in every round of an IPA opening.
-// partial: n_sets * gridDim.x records of scratch; ticket: n_sets words, zero on entry.
-template <class Fq>
-__global__ void __launch_bounds__(256)
-    k_bucket_reduce_fold_quad(const u32* __restrict__ buckets, MsmGeom g, u32* partial, u32* __restrict__ ticket, u32* __restrict__ out,
-                              const u32* __restrict__ flags, u32* __restrict__ mirror) {
-  __shared__ __attribute__((aligned(16))) u32 lds[4 * 4 * Fq::W];
-  __shared__ u32 s_last;
-  const u32 set = blockIdx.y;
-  {
-    const u32 t = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;  // logical lane: owns buckets [t*s, (t+1)*s)
-    XYZZ<Fq> total = xyzz_inf<Fq>();
-    if (t < g.red_threads) {
-      const u32 lo = t * g.red_s;
-      XYZZ<Fq> run = xyzz_inf<Fq>(), sum = xyzz_inf<Fq>();
-      XYZZ<Fq> bk = xyzz_load<Fq>(buckets, (size_t)set * g.nb + lo + g.red_s - 1);
-      for (int k = (int)g.red_s - 1; k >= 0; k--) {
-        XYZZ<Fq> nx = bk;
-        if (k > 0) nx = xyzz_load<Fq>(buckets, (size_t)set * g.nb + lo + k - 1);
-        xyzz_add_quad<Fq>(run, bk);
-        xyzz_add_quad<Fq>(sum, run);
-        bk = nx;
-      }
-      total = xyzz_mul_small_quad<Fq>(run, lo);
-      xyzz_add_quad<Fq>(total, sum);
-    }
-    block_reduce_xyzz_quad<Fq>(total, lds);
-    if (threadIdx.x == 0) {
-      xyzz_store<Fq>(partial, (size_t)set * gridDim.x + blockIdx.x, total);
-      __threadfence();  // the record is visible device-wide before the ticket is
-      s_last = atomicAdd(ticket + set, 1u) == gridDim.x - 1u ? 1u : 0u;
-    }
-  }
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();  // acquire: the other blocks' records (other XCDs' L2s) are read from memory
-  const u32 n = gridDim.x;
-  XYZZ<Fq> acc = xyzz_inf<Fq>();
-  const u32* in = partial + (size_t)set * n * (4 * Fq::W);
-  if (n <= 4u) {
-    // a handful of records (the small sets of 8-bit windows: ONE): the first quad adds them one after the other -- the workgroup
-    // tree would be 7 more dependent additions on identities
-    if (threadIdx.x < 4u)
-      for (u32 k = 0; k < n; k++) {
-        const XYZZ<Fq> p = xyzz_load<Fq>(in, k);  // (written by other workgroups of THIS launch: read behind the fence above)
-        xyzz_add_quad<Fq>(acc, p);
-      }
-  } else {
-    const u32 k0 = threadIdx.x >> 2, nq = blockDim.x >> 2;
-    for (u32 k = k0; k < n; k += nq) {
-      const XYZZ<Fq> p = xyzz_load<Fq>(in, k);
-      xyzz_add_quad<Fq>(acc, p);
-    }
-    __syncthreads();  // (lds is reused)
-    block_reduce_xyzz_quad<Fq>(acc, lds);
-  }
-  if (threadIdx.x == 0) {
-    XYZZ<Fq> e;
-    e.x = fe_export<Fq>(acc.x);
-    e.y = fe_export<Fq>(acc.y);
-    e.zz = fe_export<Fq>(acc.zz);
-    e.zzz = fe_export<Fq>(acc.zzz);
-    xyzz_store<Fq>(out, set, e);
-    if (mirror) xyzz_store<Fq>(mirror, set, e);
-    if (flags && set == 0) {
-      const u32 f0 = flags[0], f1 = flags[1];
-      out[(size_t)gridDim.y * (4 * Fq::W)] = f0;
-      out[(size_t)gridDim.y * (4 * Fq::W) + 1] = f1;
-      if (mirror) {
-        mirror[(size_t)gridDim.y * (4 * Fq::W)] = f0;
-        mirror[(size_t)gridDim.y * (4 * Fq::W) + 1] = f1;
-      }
-    }
-    ticket[set] = 0;
-    if (mirror) __threadfence_system();
-  }
-}
-template <class Fq>
-__global__ void __launch_bounds__(256) k_fold_quad(const u32* __restrict__ in, u32 n, u32* __restrict__ out,
-                                                   const u32* __restrict__ flags, u32* __restrict__ mirror, u32 clear_flags) {
-  // round 3: four waves (64 quads) instead of one -- the serial part of the fold drops from n / 16 to n / 64 additions per
-  // quad (n = 256 partial records after the reduction of a 2^19-bucket set), then the quad butterfly and one LDS step
-  __shared__ __attribute__((aligned(16))) u32 lds[4 * 4 * Fq::W];
-  XYZZ<Fq> acc = xyzz_inf<Fq>();
-  {
-    const u32 k0 = threadIdx.x >> 2, nq = blockDim.x >> 2;
-    XYZZ<Fq> p = k0 < n ? xyzz_load<Fq>(in, (size_t)blockIdx.x * n + k0) : acc;
-    for (u32 k = k0; k < n; k += nq) {
-      XYZZ<Fq> nx = p;
-      if (k + nq < n) nx = xyzz_load<Fq>(in, (size_t)blockIdx.x * n + k + nq);
-      xyzz_add_quad<Fq>(acc, p);
-      p = nx;
-    }
-  }
-  block_reduce_xyzz_quad<Fq>(acc, lds);
-  if (threadIdx.x == 0) {
-    XYZZ<Fq> e;
-    e.x = fe_export<Fq>(acc.x);
-    e.y = fe_export<Fq>(acc.y);
-    e.zz = fe_export<Fq>(acc.zz);
-    e.zzz = fe_export<Fq>(acc.zzz);
-    xyzz_store<Fq>(out, blockIdx.x, e);
-    if (mirror) xyzz_store<Fq>(mirror, blockIdx.x, e);
-    // the MSM's flag words ride behind the records: one copy takes both to the host
-    if (flags && blockIdx.x == 0) {
-      const u32 f0 = flags[0], f1 = flags[1];
-      out[(size_t)gridDim.x * (4 * Fq::W)] = f0;
-      out[(size_t)gridDim.x * (4 * Fq::W) + 1] = f1;
-      if (mirror) {
-        mirror[(size_t)gridDim.x * (4 * Fq::W)] = f0;
-        mirror[(size_t)gridDim.x * (4 * Fq::W) + 1] = f1;
-      }
-      if (clear_flags) {  // the direct sum's flag words: left zeroed for the slot's next MSM (no fill command per MSM)
-        const_cast<u32*>(flags)[0] = 0;
-        const_cast<u32*>(flags)[1] = 0;
-      }
-    }
-    if (mirror) __threadfence_system();
-  }
-}
 
 // ---------------------------------------------------------------------------------------------
 // Round 6: the JUMP FOLD of an IPA opening (ark_poly_commit::ipa_pc::open ext, under src/ipa_pc_as/mod.rs:454).  After j rounds the
@@ -948,7 +880,7 @@ __global__ void __launch_bounds__(256) k_fold_quad(const u32* __restrict__ in, u
 // one piece: wave q adds entries q, q + JUMP_WAVES, .. for 64 outputs k at once (lane = k: the 64 points T_w[t m0 + k ..] of an entry are
 // ONE contiguous row of the table: coalesced), an LDS tree adds the waves' sums, and the piece's sum lands in bucket (value - 1) of set
 // ((piece number within its list, half), k) -- pieces of one list are buckets of the SAME weight in different sets.  The sets then go
-// through the ordinary weighted bucket reduction (k_bucket_reduce_fold_quad: sum_v v bucket_v) and the host adds the sets of an
+// through the ordinary weighted bucket reduction (k_bucket_reduce<QUAD, FUSED>: sum_v v bucket_v) and the host adds the sets of an
 // output: lo + 2^8 hi.
 // entries[e] = (w * stride + t * m0) | neg << 31;  list_off[l] .. list_off[l + 1]: piece l's entries;  list_slot[l] = (2 piece + half) nb +
 // value - 1.  buckets: 2 n_pieces_max m0 sets of nb records, ZEROED by the launcher (a value without entries stays the identity).

@@ -1,7 +1,8 @@
-// Which pipeline an MSM takes, and which table a key is built with: ONE place, two tables, no HIP -- plain C++ that the host
-// launcher (api_pipeline.inc, api_keys.inc) includes and that tests/cpp_host/select_check.cpp compiles on its own to check every
-// threshold edge without a GPU (tests/test_pipeline_select_cpu.py).  Every size threshold of the library lives here; the numbers
-// are measured on MI355X (same-process A/B, DESIGN.md section 4.2 and profiles/), not derived.
+// Which pipeline an MSM takes, which table a key is built with, and which form its tail takes: ONE place, three tables, no HIP -- plain
+// C++ that the host launcher (api_pipeline.inc, api_keys.inc) and the kernels' launchers (kern_ec.inc) include and that
+// tests/cpp_host/select_check.cpp compiles on its own to check every threshold edge without a GPU (tests/test_pipeline_select_cpu.py).
+// Every size threshold of the library lives here; the numbers are measured on MI355X (same-process A/B, DESIGN.md section 4.2 and
+// profiles/), not derived.
 //
 // The four accumulation forms:
 //   DIRECT_SUM       keys of up to 2^15 generators that carry every multiple a 4-bit signed digit can ask for: one launch that sums
@@ -13,7 +14,8 @@
 //                    distribution (k_accum_l0 + k_accum_l1)
 // Longer MSMs are cut into ranges first (`range`), each range is chosen again; the ranges of one vector over a bucket-per-lane key
 // share one bucket set (api_types.h: struct Share).
-// Beside the two tables: `classify`, what a call makes of its vectors' two-valued probes (two-valued, all zero, unit scalars summed apart).
+// Table 3, `tail_plan`: the bucket reduction, fold and export behind any of them -- form, grids and what the slot must hold.
+// Beside the tables: `classify`, what a call makes of its vectors' two-valued probes (two-valued, all zero, unit scalars summed apart).
 #pragma once
 #include <stddef.h>
 
@@ -221,6 +223,114 @@ inline void classify(const VecProbe* vec, size_t k, bool mont, const KeyDesc& ke
       }
     }
   }
+}
+
+// ---- table 3: the tail of an MSM -- the bucket reduction (per set sum_j (j + 1) bucket_j), the fold of its partial records, the export ----
+// Where an MSM stands in its call (msm_enqueue): whether anybody waits for its tail, and whether anything can overlap with it
+enum class Place {
+  LONE,         // the only MSM of a blocking call: exposed tail, the whole chain on the caller's stream
+  BATCH_LAST,   // the last MSM of a batch (or a re-run inside one): exposed tail, on the per-stage streams
+  BATCH_INNER,  // another MSM is queued behind it: its tail is hidden behind that one's accumulation
+};
+inline Place place_of(size_t i, size_t count) { return count == 1 ? Place::LONE : (i + 1 == count ? Place::BATCH_LAST : Place::BATCH_INNER); }
+enum TailForm {
+  RED2 = 0,        // row / column sums, their small multiples, the fold: three launches (k_red2_sums, k_red2_weighted, k_fold)
+  FUSED_QUAD = 1,  // running sums on quads of lanes; the last workgroup of a set to arrive folds it: one launch (k_bucket_reduce)
+  ONE_LANE = 2     // running sums on single lanes, then the one-wave fold: two launches (k_bucket_reduce, k_fold)
+};
+inline const char* tail_form_name(int f) { return f == RED2 ? "red2" : (f == FUSED_QUAD ? "fused_quad" : "one_lane"); }
+constexpr int TAIL_QUAD_HIDDEN_LOG2 = 17;  // bucket tables up to 2^this take the quad tail inside a batch too (2^16 234 -> 283 M pairs/s)
+constexpr unsigned RED2_COLS = 1024, RED2_MIN_NB = 1u << 18;
+inline unsigned cdiv_u(unsigned a, unsigned b) { return (a + b - 1) / b; }
+// the row / column form's grid (msm_kernels.h: k_red2_sums): nb a multiple of RED2_COLS
+struct Red2Geom {
+  unsigned A;      // rows = nb / 1024
+  unsigned gw;     // lanes per row group (power of two <= 64): row strips of 1024 / gw columns
+  unsigned gc;     // lanes per column group (power of two <= 64, <= A): column strips of A / gc rows
+  unsigned row_waves, col_waves;  // waves per set in each mode
+};
+inline Red2Geom red2_geom(unsigned nb, bool latency) {
+  Red2Geom r;
+  r.A = nb / RED2_COLS;
+  // latency (an exposed tail, or a small table whose chain would bound a batch): short strips, wide butterflies; otherwise long
+  // strips -- fewer butterfly additions (a butterfly level costs every lane of the wave one addition)
+  r.gw = latency ? 64u : 16u;
+  r.gc = r.A < r.gw ? r.A : r.gw;
+  unsigned p2 = 1;
+  while (p2 * 2u <= r.gc) p2 *= 2u;
+  r.gc = p2;
+  while (r.A % r.gc) r.gc >>= 1;  // (A is a power of two for every geometry that gets here; defensive)
+  r.row_waves = cdiv_u(r.A, 64u / r.gw);
+  r.col_waves = cdiv_u(RED2_COLS, 64u / r.gc);
+  return r;
+}
+struct TailPlan {
+  TailForm form;
+  bool quad;        // a quad of lanes per logical lane (ec.h: xyzz_add_quad) in every kernel of the tail
+  bool latency;     // RED2: the strip shape (red2_geom)
+  unsigned red_s, red_threads;  // running sums: buckets per logical lane, logical lanes per set
+  unsigned partials;  // partial records per set that the reduction leaves in the slot's red_out
+  size_t rc_records;  // RED2: records of row / column scratch (all sets), else 0
+  bool ticket;        // FUSED_QUAD: one zeroed arrival counter per set
+};
+// nb buckets in each of n_sets sets (B in all), E sorted entries; bpl: the bucket-per-lane accumulation filled the buckets
+inline TailPlan tail_plan(unsigned nb, unsigned n_sets, unsigned B, unsigned E, bool bpl, Place place) {
+  TailPlan t{};
+  // exposed: nothing is queued behind this MSM, so the caller waits for its tail (bucket reduce + fold, a chain of dependent point
+  // operations on a few waves): run it on the quad-cooperative kernels (-0.08 ms).  Inside a batch the tail is hidden behind the
+  // next MSM's accumulation and the one-lane kernels cost less ALU time (measured: 1 % of the batch throughput).
+  const bool exposed = place != Place::BATCH_INNER;
+  // Round 4: a HIDDEN tail (inside a batch) also takes the quad kernels when the bucket table is small.  The tails of
+  // consecutive MSMs queue on one stream, and the one-lane kernels are latency chains whatever the bucket count -- accumulate
+  // L1 80 + reduce 240 + fold 120 us for the 2^15 buckets of a 2^18-pair MSM whose accumulation takes 300 us (rocprofv3, round
+  // 4): the batch ran at one MSM per tail (0.46 ms at 2^18, 0.71 at 2^19).  The quad kernels cost four times the lanes of
+  // almost nothing there and halve the chain; from 2^18 buckets up the one-lane kernels' lower ALU cost wins (2^20 pairs).
+  // (... and only while the accumulation is shorter than the tail chain: up to 2^18 pairs of 16 entries -- at 2^19 the batch
+  // is bound by the accumulation's work and the quad kernels' extra lanes cost 2-6 %; measured, same box, M pairs/s in batches:
+  // 2^16 234 -> 283, 2^17 395 -> 451, 2^18 582 -> 617, 2^19 754 -> 741; BLS12-381 2^18 207 -> 297, 2^19 352 -> 332)
+  const bool small_table = B <= (1u << TAIL_QUAD_HIDDEN_LOG2) && E <= (5u << 20);
+  t.quad = exposed || small_table;
+  t.latency = t.quad;
+  // buckets per lane of the running sums: 4; 8 for the 2^16-bucket sets of 17-bit windows (half the 16-bit small
+  // multiples, the reduction's largest ALU item; batches 821 -> 826 M pairs/s at 2^20, 845 -> 853 at 2^22; 2 and 16 do not pay)
+  // round 6: 2 for the 128-bucket sets of 8-bit windows (plain keys up to 2^17 pairs: the rounds of a large IPA opening over its
+  // folded key, 64 sets of 128 buckets) -- a set is one workgroup either way, and its chain is the leaf's additions + a 7-bit multiple
+  // + the tree: 3 additions instead of 7 at the leaf
+  // bucket-per-lane: the reduction is hidden behind the next MSM's accumulation or exposed on few waves either way: long per-lane runs
+  // keep its small multiples (one per lane) rare -- 2^19 buckets / 32 = 16 384 lanes (measured: 16 / 32 / 64 -> 911 / 955 / 895 M
+  // pairs/s in batches, 0.45 / 0.37 / 0.52 ms exposed)
+  t.red_s = bpl ? 32u : (nb >= 65536u ? 8u : (nb <= 256u ? 2u : 4u));
+  if (t.red_s > nb) t.red_s = nb;
+  t.red_threads = nb / t.red_s;
+  const unsigned lanes = t.quad ? 4u : 1u;  // hardware lanes per logical lane
+  // round 4: bucket sets of 2^18 buckets and more reduce as row / column sums.  Measured, same box, batches / blocking call: 2^20
+  // pairs over the 20-bit key 908 -> 928 M pairs/s, 1.409 -> 1.381 ms; smaller sets LOSE (2^15 buckets: 2^16 pairs 280 -> 212,
+  // 2^19 pairs 717 -> 598; a plain key's 16 sets of 2^15: 794 -> 731): with few rows the column sums are all butterfly, and
+  // 1024 + A small multiples cost more than the per-lane ones of a short running-sum kernel
+  if (nb >= RED2_MIN_NB && nb % RED2_COLS == 0u) {
+    const unsigned items = nb / RED2_COLS + RED2_COLS;  // one logical lane per row or column sum
+    t.form = RED2;
+    t.partials = cdiv_u(items * lanes, 256);
+    t.rc_records = (size_t)n_sets * items;
+    return t;
+  }
+  // round 6: the quad reduction and its fold as ONE launch (profiles/r06_fused_fold_ab.txt: equal or ahead of the two launches everywhere)
+  t.form = t.quad ? FUSED_QUAD : ONE_LANE;
+  t.partials = cdiv_u(t.red_threads * lanes, 256);
+  t.ticket = t.quad;
+  return t;
+}
+// What a slot must hold for the MSM wherever it stands in its call: msm_plan reserves before the Place is known (a caller with side
+// effects reserves first), msm_enqueue decides.  The form-independent fields are LONE's.
+inline TailPlan tail_plan_any_place(unsigned nb, unsigned n_sets, unsigned B, unsigned E, bool bpl) {
+  TailPlan w = tail_plan(nb, n_sets, B, E, bpl, Place::LONE);
+  for (Place p : {Place::BATCH_LAST, Place::BATCH_INNER}) {
+    const TailPlan t = tail_plan(nb, n_sets, B, E, bpl, p);
+    if (t.partials > w.partials) w.partials = t.partials;
+    if (t.rc_records > w.rc_records) w.rc_records = t.rc_records;
+    w.ticket = w.ticket || t.ticket;
+  }
+  return w;
 }
 
 }  // namespace msel

@@ -2,6 +2,10 @@
 // tests/test_pipeline_select_cpu.py holds the expected table.  One line per (key, pairs, form):
 //   <key> <pairs> <plain|grouped|grouped_irregular|skewed> <pipeline> twin=<0|1> plain_window=<c> range=<pairs>
 // and one per case of msel::classify:  classify <case> <verdict of each vector>
+// and three (one per Place) per geometry of msel::tail_plan:
+//   tail <case> <place> form=.. quad=.. latency=.. red_s=.. red_threads=.. partials=.. rc=.. ticket=.. whole=.. covered=..
+// covered: what tail_plan_any_place reserves (msm_plan, before the Place is known) holds everything the launches of this plan write, and
+// their grids reach every bucket and sum without reading past the sets; the program fails if any line is not covered
 #include <cstdio>
 #include <vector>
 
@@ -140,5 +144,72 @@ int main() {
     run("shared_memory_chain", {vec(true, 1, 0, 0, heavy, 0, n, 0), vec(true, 1, 0, 0, heavy, 0, n, n - 100), vec(true, 1, 0, 0, few, 0, n, 2 * n - 200)},
         false, table17, sw);
   }
-  return 0;
+  // the tail (table 3): every rule edge, the jump fold's geometry and the shapes of tests/test_tail_forms_gpu.py
+  int uncovered = 0;
+  {
+    struct T {
+      const char* name;
+      unsigned nb, n_sets, B, E;
+      bool bpl;
+    };
+    const unsigned E0 = 1u << 20;
+    const T cases[] = {
+        {"B_2p17", 1u << 15, 4, 1u << 17, E0, false},            // TAIL_QUAD_HIDDEN_LOG2: the last table whose hidden tail stays quad
+        {"B_2p17_plus_1", 1u << 15, 4, (1u << 17) + 1u, E0, false},
+        {"B_5_sets_of_2p15", 1u << 15, 5, 5u << 15, E0, false},
+        {"E_5_2p20", 1u << 15, 1, 1u << 15, 5u << 20, false},
+        {"E_5_2p20_plus_1", 1u << 15, 1, 1u << 15, (5u << 20) + 1u, false},
+        {"nb_2p18_minus_1024", (1u << 18) - 1024u, 1, (1u << 18) - 1024u, E0, false},
+        {"nb_2p18", 1u << 18, 1, 1u << 18, E0, false},
+        {"nb_2p18_plus_1", (1u << 18) + 1u, 1, (1u << 18) + 1u, E0, false},  // (no real geometry: nb is a power of two; the rule's edge)
+        {"nb_256", 256, 8, 2048, E0, false},
+        {"nb_257", 257, 8, 2056, E0, false},
+        {"nb_65535", 65535, 1, 65535, E0, false},
+        {"nb_65536", 65536, 1, 65536, E0, false},
+        {"bpl_20_bit_table", 1u << 19, 1, 1u << 19, 13u << 20, true},   // tests/test_bpl_gpu.py: the row / column form, both strip shapes
+        {"bpl_off_2p19", 1u << 19, 1, 1u << 19, 13u << 20, false},
+        {"bpl_plain_16_bit", 1u << 15, 17, 17u << 15, 16u << 20, true},
+        {"bpl_off_plain_16_bit", 1u << 15, 17, 17u << 15, 16u << 20, false},
+        {"two_sets_of_2p19", 1u << 19, 2, 1u << 20, 13u << 20, true},    // grouped over the 20-bit table
+        {"jump_fold", 256, 2 * 3 * 64, 2 * 3 * 64 * 256, 0, false},     // api_schemes.inc: JUMP_NB buckets, 2 n_rep m0 sets
+        {"gpu_a_plain_2p10", 128, 32, 32 * 128, 32u << 10, false},       // 8-bit windows: 32 sets of 128 buckets
+        {"gpu_b_table_2p15", 4096, 1, 4096, 20u << 12, false},           // 13-bit windows, 2^12 pairs
+        {"gpu_c_plain_2p17_plus_64", 1u << 14, 19, 19u << 14, ((1u << 17) + 64u) * 18u, true},  // 15-bit windows, 18 + 1 sets
+    };
+    const Place places[] = {Place::LONE, Place::BATCH_LAST, Place::BATCH_INNER};
+    const char* place_names[] = {"lone", "batch_last", "batch_inner"};
+    for (const T& c : cases) {
+      const TailPlan w = tail_plan_any_place(c.nb, c.n_sets, c.B, c.E, c.bpl);  // what msm_plan reserves
+      for (int p = 0; p < 3; p++) {
+        const TailPlan t = tail_plan(c.nb, c.n_sets, c.B, c.E, c.bpl, places[p]);
+        const unsigned shift = t.quad ? 2u : 0u;
+        const size_t lanes = ((size_t)t.partials * 256u) >> shift;  // logical lanes of a set's t.partials workgroups
+        bool ok = t.partials >= 1 && t.partials <= w.partials && t.rc_records <= w.rc_records && (!t.ticket || w.ticket);
+        bool whole = true;
+        if (t.form == RED2) {
+          const Red2Geom r = red2_geom(c.nb, t.latency);
+          const size_t items = (size_t)r.A + RED2_COLS;
+          auto pow2_le_64 = [](unsigned x) { return x >= 1 && x <= 64 && (x & (x - 1)) == 0; };
+          // k_red2_sums: every row and column has a group, strips tile them exactly, records [0, n_sets * items) are written
+          ok = ok && (size_t)r.A * RED2_COLS == c.nb && pow2_le_64(r.gw) && pow2_le_64(r.gc) && RED2_COLS % r.gw == 0 && r.A % r.gc == 0;
+          ok = ok && (size_t)r.row_waves * (64u / r.gw) >= r.A && (size_t)r.col_waves * (64u / r.gc) >= RED2_COLS;
+          ok = ok && (size_t)c.n_sets * items <= w.rc_records;
+          // k_red2_weighted: a logical lane per sum
+          ok = ok && lanes >= items && !t.ticket;
+        } else {
+          // k_bucket_reduce: a logical lane per run of red_s buckets, no bucket read past its set
+          ok = ok && t.red_s >= 1 && (size_t)t.red_threads * t.red_s <= c.nb && lanes >= t.red_threads && t.rc_records == 0;
+          ok = ok && t.ticket == (t.form == FUSED_QUAD) && t.quad == (t.form == FUSED_QUAD);
+          whole = (size_t)t.red_threads * t.red_s == c.nb;
+        }
+        // the partial records: n_sets * t.partials written (and folded), n_sets * w.partials reserved
+        ok = ok && (size_t)c.n_sets * t.partials <= (size_t)c.n_sets * w.partials;
+        if (!ok) uncovered++;
+        printf("tail %s %s form=%s quad=%d latency=%d red_s=%u red_threads=%u partials=%u rc=%zu ticket=%d whole=%d covered=%d\n", c.name,
+               place_names[p], tail_form_name(t.form), t.quad ? 1 : 0, t.latency ? 1 : 0, t.red_s, t.red_threads, t.partials, t.rc_records,
+               t.ticket ? 1 : 0, whole ? 1 : 0, ok ? 1 : 0);
+      }
+    }
+  }
+  return uncovered ? 1 : 0;
 }

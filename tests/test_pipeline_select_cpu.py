@@ -1,7 +1,9 @@
 """Which pipeline an MSM takes -- accumulation_amd/csrc/msm_select.h, the ONE table-driven function behind every entry point --
 at every threshold edge, without a GPU: tests/cpp_host/select_check.cpp is plain C++ over the header alone.
 Edges: n = 2^k - 1, 2^k, 2^k + 1 for k = 15 .. 20, 2^21, 2^22; keys: a direct-sum key, 16-bit tables of 2^16 / 2^19 generators,
-the 20-bit table (2^20 and 2^22 generators), a plain key; forms: plain, grouped (regular / irregular index classes), skewed."""
+the 20-bit table (2^20 and 2^22 generators), a plain key; forms: plain, grouped (regular / irregular index classes), skewed.
+The same program prints msel::tail_plan -- the form, grids and buffer needs of an MSM's tail -- at its rule edges and checks that what
+msm_plan reserves before the Place is known covers every launch (it exits non-zero otherwise: the fixture's check=True)."""
 import os
 import subprocess
 
@@ -130,3 +132,73 @@ def test_classification_of_probed_vectors(table):
         "shared_memory_chain": ["regular", "regular", "regular"],
     }
     assert got == want
+
+
+def tail_rows(table):
+    rows = {}
+    for ln in table[1]:
+        w = ln.split()
+        if w[0] == "tail":
+            rows[(w[1], w[2])] = dict(kv.split("=") for kv in w[3:])
+    return rows
+
+
+def test_tail_plan_rule_edges(table):
+    """msel::tail_plan, one line per rule edge and Place: (form, red_s, partial records per set, records of row / column scratch)"""
+    rows = tail_rows(table)
+    FQ, OL, R2 = "fused_quad", "one_lane", "red2"
+
+    def expect_tail(case, lone, inner):
+        # the two exposed places (a blocking call, the last MSM of a batch) always agree
+        for place, want in (("lone", lone), ("batch_last", lone), ("batch_inner", inner)):
+            r = rows[(case, place)]
+            got = (r["form"], int(r["red_s"]), int(r["partials"]), int(r["rc"]))
+            assert got == want, (case, place, r)
+            quad = want[0] == FQ or (want[0] == R2 and place != "batch_inner")
+            assert (int(r["quad"]), int(r["latency"]), int(r["ticket"])) == (int(quad), int(quad), int(want[0] == FQ)), (case, place, r)
+            assert r["covered"] == "1"
+
+    # a hidden tail stays on the quad kernels up to 2^17 buckets in all and 5 * 2^20 entries
+    expect_tail("B_2p17", (FQ, 4, 128, 0), (FQ, 4, 128, 0))
+    expect_tail("B_2p17_plus_1", (FQ, 4, 128, 0), (OL, 4, 32, 0))
+    expect_tail("B_5_sets_of_2p15", (FQ, 4, 128, 0), (OL, 4, 32, 0))
+    expect_tail("E_5_2p20", (FQ, 4, 128, 0), (FQ, 4, 128, 0))
+    expect_tail("E_5_2p20_plus_1", (FQ, 4, 128, 0), (OL, 4, 32, 0))
+    # row / column sums from 2^18 buckets per set, multiples of 1024 only: 256 + 1024 sums, a lane or a quad each
+    expect_tail("nb_2p18_minus_1024", (FQ, 8, 510, 0), (OL, 8, 128, 0))
+    expect_tail("nb_2p18", (R2, 8, 20, 1280), (R2, 8, 5, 1280))
+    expect_tail("nb_2p18_plus_1", (FQ, 8, 512, 0), (OL, 8, 128, 0))
+    # buckets per logical lane: 2 up to 256 buckets, 8 from 2^16, else 4; 32 behind the bucket-per-lane accumulation
+    expect_tail("nb_256", (FQ, 2, 2, 0), (FQ, 2, 2, 0))
+    expect_tail("nb_257", (FQ, 4, 1, 0), (FQ, 4, 1, 0))
+    expect_tail("nb_65535", (FQ, 4, 256, 0), (FQ, 4, 256, 0))
+    expect_tail("nb_65536", (FQ, 8, 128, 0), (FQ, 8, 128, 0))
+    expect_tail("bpl_20_bit_table", (R2, 32, 24, 1536), (R2, 32, 6, 1536))
+    expect_tail("bpl_off_2p19", (R2, 8, 24, 1536), (R2, 8, 6, 1536))
+    expect_tail("bpl_plain_16_bit", (FQ, 32, 16, 0), (OL, 32, 4, 0))
+    expect_tail("bpl_off_plain_16_bit", (FQ, 4, 128, 0), (OL, 4, 32, 0))
+    expect_tail("two_sets_of_2p19", (R2, 32, 24, 3072), (R2, 32, 6, 3072))
+    # the jump fold of an IPA opening: JUMP_NB = 256 buckets per set, two per logical lane
+    expect_tail("jump_fold", (FQ, 2, 2, 0), (FQ, 2, 2, 0))
+    assert rows[("jump_fold", "lone")]["red_threads"] == "128"
+
+
+def test_tail_plan_of_the_gpu_shapes(table):
+    """the shapes of tests/test_tail_forms_gpu.py: (a) one partial record per set, the first quad folds serially; (b) more than four,
+    the workgroup tree; (c) a hidden tail over more than 2^17 buckets on the one-lane kernels, the batch's last on the fused one"""
+    rows = tail_rows(table)
+    a, b = rows[("gpu_a_plain_2p10", "lone")], rows[("gpu_b_table_2p15", "lone")]
+    assert (a["form"], int(a["partials"])) == ("fused_quad", 1)
+    assert b["form"] == "fused_quad" and int(b["partials"]) == 16 > 4
+    c_in, c_last = rows[("gpu_c_plain_2p17_plus_64", "batch_inner")], rows[("gpu_c_plain_2p17_plus_64", "batch_last")]
+    assert (c_in["form"], int(c_in["red_s"]), int(c_in["partials"])) == ("one_lane", 32, 2)
+    assert (c_last["form"], int(c_last["partials"])) == ("fused_quad", 8)
+
+
+def test_tail_plan_reservation_covers_every_launch(table):
+    """every line: what tail_plan_any_place reserves holds what the launches of each Place write, and their grids reach every sum"""
+    rows = tail_rows(table)
+    assert len(rows) == 21 * 3
+    assert all(r["covered"] == "1" for r in rows.values())
+    # whole: the lanes' runs tile the set exactly -- true for every real geometry (nb is a power of two); the synthetic edges are not
+    assert sorted({c for (c, _), r in rows.items() if r["whole"] == "0"}) == ["nb_257", "nb_2p18_plus_1", "nb_65535"]
