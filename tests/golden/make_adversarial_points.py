@@ -1,11 +1,13 @@
 """Generate tests/golden/adversarial_points.json: curve points whose coordinates, IN THE DEVICE'S INTERNAL MONTGOMERY RADIX
-(2^261 for Pallas, 2^392 for BLS12-381: csrc/fpu.h), sit at the edges the lazy arithmetic of csrc/ec.h cares about -- tiny
+(2^261 for Pallas and Vesta, 2^392 for BLS12-381: csrc/fpu.h), sit at the edges the lazy arithmetic of csrc/ec.h cares about -- tiny
 values and values just below p.  The bug fixed in round 2 (doubling a negated point whose internal y was below 2^(B (L - 1)))
 needed exactly such a point and random tests meet one in 2^17 (BLS12-381) / 2^22 (Pallas) points.
 
-Pallas has cofactor 1, so points are CONSTRUCTED: pick the internal coordinate, solve the curve equation (cube root /
-square root).  BLS12-381 G1 needs points of the prime-order subgroup, so a pool of multiples of the generator (the C oracle's
+Pallas and Vesta have cofactor 1, so points are CONSTRUCTED: pick the internal coordinate, solve the curve equation (cube
+root / square root).  BLS12-381 G1 needs points of the prime-order subgroup, so a pool of multiples of the generator (the C oracle's
 rng_points) is SEARCHED for the most extreme coordinates.  Data only; run from the repo root:  python tests/golden/make_adversarial_points.py
+The constructed curves are made again on every run (well under a second); the BLS12-381 search takes minutes and its section
+is carried over from the existing file unless --search is given.
 """
 import json
 import os
@@ -17,8 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from oracle import cref, pyref as o  # noqa: E402
 from oracle.pyref_ser import _sqrt  # noqa: E402
+from tests.helpers import VESTA  # noqa: E402
 
-INTERNAL_BITS = {"pallas": 261, "bls12_381_g1": 392}
+INTERNAL_BITS = {"pallas": 261, "bls12_381_g1": 392, "vesta": 261}
 
 
 def cube_root(a, p):
@@ -101,10 +104,15 @@ def searched(c, per_kind, n_pool, seeds):
 
 
 if __name__ == "__main__":
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "adversarial_points.json")
+    as_hex = lambda d: {k: [[hex(P[0]), hex(P[1])] for P in v] for k, v in d.items()}  # noqa: E731
     doc = {"comment": "affine points (canonical integers, hex) with extreme coordinates in the device's internal Montgomery radix; "
                       "made by tests/golden/make_adversarial_points.py", "internal_radix_bits": INTERNAL_BITS, "curves": {}}
-    doc["curves"]["pallas"] = {k: [[hex(P[0]), hex(P[1])] for P in v] for k, v in constructed(o.PALLAS, 6).items()}
-    doc["curves"]["bls12_381_g1"] = {k: [[hex(P[0]), hex(P[1])] for P in v]
-                                     for k, v in searched(o.BLS12_381_G1, 4, 1 << 18, [4101, 4102, 4103, 4104]).items()}
-    json.dump(doc, open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "adversarial_points.json"), "w"), indent=1)
+    doc["curves"]["pallas"] = as_hex(constructed(o.PALLAS, 6))
+    if "--search" in sys.argv[1:] or not os.path.exists(path):
+        doc["curves"]["bls12_381_g1"] = as_hex(searched(o.BLS12_381_G1, 4, 1 << 18, [4101, 4102, 4103, 4104]))
+    else:
+        doc["curves"]["bls12_381_g1"] = json.load(open(path))["curves"]["bls12_381_g1"]
+    doc["curves"]["vesta"] = as_hex(constructed(VESTA, 6))
+    json.dump(doc, open(path, "w"), indent=1)
     print("written")

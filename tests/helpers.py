@@ -8,6 +8,9 @@ from oracle import pyref as o
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "msm_golden.json")
 
+# Pallas's partner in the Pasta cycle (AMSM_VESTA = 2): the two fields swapped.  The oracle is curve-generic and keeps no Vesta object.
+VESTA = o.Curve("vesta", 2, p=o.PALLAS.r, r=o.PALLAS.p, b=5, gx=o.PALLAS.r - 1, gy=2, limbs=4)
+
 
 def load_golden():
     with open(GOLDEN) as f:

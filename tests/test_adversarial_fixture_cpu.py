@@ -5,8 +5,9 @@ import json
 import os
 
 from oracle import pyref as o
+from tests.helpers import VESTA
 
-CURVES = [o.PALLAS, o.BLS12_381_G1]
+CURVES = [o.PALLAS, o.BLS12_381_G1, VESTA]
 FIX = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "adversarial_points.json")))
 
 

@@ -3,7 +3,11 @@
 below p).  The lazy arithmetic of csrc/ec.h (values bounded, not reduced; `K p - y` formed limb-wise) is exact only inside
 documented bounds, and random points meet the edges of those bounds once in 2^17 .. 2^22 operations: here every such
 point goes through doubling (duplicate bases), doubling of the negated point, cancellation, plain accumulation and the
-key fold's ladder, for both key kinds, against the big-int oracle."""
+key fold's ladder, for both key kinds, against the big-int oracle (oracle/pyref.py: it is curve-generic, so Vesta runs too).
+
+The expected sums are built from one table of s P, one oracle multiplication per (scalar, fixture point): r - s gives -(s P),
+P and -P share an entry, and every pattern's sum is additions of table entries -- a few hundred multiplications per case instead
+of one per key entry, scalar and pattern."""
 import json
 import os
 
@@ -14,7 +18,7 @@ from oracle import pyref as o
 from tests import helpers as h
 
 pytestmark = pytest.mark.gpu
-CURVES = [o.PALLAS, o.BLS12_381_G1]
+CURVES = [o.PALLAS, o.BLS12_381_G1, h.VESTA]
 FIX = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "adversarial_points.json")))
 
 
@@ -29,10 +33,29 @@ def neg(c, P):
     return (P[0], (-P[1]) % c.p)
 
 
+_MUL = {}  # (curve name, s, P) -> s P, for s <= r / 2 and P the one of P, -P with the smaller y
+
+
+def smul(c, s, P):
+    """s P, exactly: the oracle's multiplication, once per scalar and point up to sign ((r - s) P = s (-P) = -(s P): every fixture
+    point has order r, tests/test_adversarial_fixture_cpu.py)"""
+    s %= c.r
+    if s == 0 or P is None:
+        return None
+    if 2 * s > c.r:
+        return o.neg(c, smul(c, c.r - s, P))
+    if 2 * P[1] > c.p:
+        return o.neg(c, smul(c, s, neg(c, P)))
+    key = (c.name, s, P)
+    if key not in _MUL:
+        _MUL[key] = o.mul(c, s, P)
+    return _MUL[key]
+
+
 def oracle_msm(c, pts, scalars):
     acc = None
     for P, s in zip(pts, scalars):
-        acc = o.add(c, acc, o.mul(c, s % c.r, P))
+        acc = o.add(c, acc, smul(c, s, P))
     return acc
 
 
@@ -115,7 +138,7 @@ def test_key_fold_over_adversarial_pairs(ctxs, c):
         f = ck.fold(half, fr.to_limbs(x), nbits)
         got, ginf = f.read()
         for i in range(half):
-            want = o.add(c, left[i], o.mul(c, x, right[i]))
+            want = o.add(c, left[i], smul(c, x, right[i]))
             assert h.np_to_point(c, got[i], bool(ginf[i])) == want, (c.name, hex(x), i)
         f.free()
         ck.free()

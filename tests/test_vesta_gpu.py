@@ -1,6 +1,11 @@
-"""Vesta (AMSM_VESTA = 2) on the GPU: the synthetic key stream, MSMs on explicit adversarial points, every MSM pipeline forced once,
-2^20 / 2^22 MSMs checked exactly, the scalar-field vector kernels, key folds (GLV ladder), the four schemes' C++ drivers and a
-2-shard key.
+"""Vesta (AMSM_VESTA = 2) on the GPU: the synthetic key stream, MSMs over explicit keys with duplicates, negations and identities,
+every MSM pipeline forced once, edge scalars through every accumulation form, 2^20 / 2^22 MSMs checked exactly, the scalar-field
+vector kernels, key folds (GLV ladder), the four schemes' C++ drivers and a 2-shard key.
+
+The explicit keys here are "adversarial" in their STRUCTURE only: duplicates, negations and identities of random generated points,
+whose coordinates are never tiny or just below p in the device's internal radix.  Points with such extreme coordinates
+(tests/golden/adversarial_points.json) go through the group law in tests/test_adversarial_points_gpu.py, Vesta included, and the
+scalar-field kernels meet their edge values in tests/test_vec_gpu.py::test_scalar_field_kernels_on_edge_values.
 
 Large MSMs need no big oracle: a generated key has G_i = k_i G with k_i = rng_scalar(seed, i) (pyref.rng_scalar, restated below
 with numpy), so sum s_i G_i = (sum s_i k_i mod r) G, one scalar multiplication in Python.  Explicit keys are built the same way
@@ -16,7 +21,7 @@ from tests import helpers as h
 pytestmark = pytest.mark.gpu
 
 PALLAS = o.PALLAS
-VESTA = o.Curve("vesta", 2, p=PALLAS.r, r=PALLAS.p, b=5, gx=PALLAS.r - 1, gy=2, limbs=4)
+VESTA = h.VESTA
 SEED = 0x5EED2002
 RINV = pow(1 << 256, -1, VESTA.r)
 
@@ -170,6 +175,87 @@ def test_pipelines_forced_once(ctx):
         plain.free()
     finally:
         c2.close()
+
+
+def edge_scalars():
+    """the scalars a digit recoding can get wrong, all below r: the ends of the field, its middle, single bits and runs of ones at
+    window boundaries, and for every window width c the library uses (msm_select.h: 8, 13, 15, 16, 17, 20) the window patterns
+    around the signed digits' carry.  r is just above 2^254, so a scalar below r has 254 free bits: the patterns fill those."""
+    r = VESTA.r
+    vals = [0, 1, 2, r - 1, r - 2, (r - 1) // 2, (r + 1) // 2, 1 << 254]
+    for k in (16, 17, 20, 40, 128, 200, 254):
+        vals += [(1 << k) - 1, 1 << k]
+    # 2^254 - 1 (above) has EVERY window of every width all ones: each signed digit is -1 or 0 with a carry into the next, up to the top
+    # window.  Beside it, per width: every window 2^c - 2 (with the carry all ones: every digit non-zero, negative and carrying),
+    # 2^(c-1) (the sign boundary itself) and 2^(c-1) - 1 (the largest digit that does not carry)
+    for c in (8, 13, 15, 16, 17, 20):
+        for w in ((1 << c) - 2, 1 << (c - 1), (1 << (c - 1)) - 1):
+            vals.append(sum(w << (c * j) for j in range(254 // c + 1)) & ((1 << 254) - 1))
+    assert all(0 <= v < r for v in vals) and (1 << 254) - 1 in vals
+    return vals
+
+
+# One case per accumulation form, at the smallest size the selection table (csrc/msm_select.h: kPipeline, key_window, tail_plan;
+# pinned without a GPU by tests/test_pipeline_select_cpu.py) gives that form -- (key flags, generators, pairs, the counter of
+# Context.pipeline_stats() that must move (None: the chunked pipeline, which has none), AMSM_BPL):
+#   direct sum          any precomputed key of up to 2^15 generators carries the table of 4-bit signed digits
+#   13-bit windows      a precomputed key of 2^15 generators without that table, chunked (key_window 2p15)
+#   bucket-split        precomputed, 2^16 pairs: the lower edge of (2^16 - 1, 2^17]; 16-bit windows
+#   one record per set  a plain key, 2^10 pairs, a blocking call: 8-bit windows, 32 sets of 128 buckets, the fused tail whose first quad
+#                       folds serially (test_tail_plan_of_the_gpu_shapes: gpu_a_plain_2p10)
+#   bucket-per-lane     plain keys from 2^17 + 1 pairs (15-bit windows) and from 2^18 + 1 (16-bit); over a precomputed key only with
+#                       the 20-bit table, 2^20 generators, from 2^18 + 1 pairs (a precomputed key of 2^17 generators is bucket-split)
+#   chunked             the same 2^17 + 1 pairs over a plain key in a context without bucket-per-lane: 8-bit windows at the size where
+#                       the switch decides
+# The chunked pipeline has no counter, so for its three cases (13-bit windows, one record per set, bucket-per-lane off) the device
+# says only that no OTHER form ran: that these sizes mean these window widths and this tail form is pinned by
+# tests/test_pipeline_select_cpu.py (key_window 2p15 / 2p9 .. 2p19, gpu_a_plain_2p10, "switch bpl=0") -- a change to the selection
+# table shows there, and these sizes move with it.
+FORMS = {
+    "direct_sum": (1, 1 << 12, 1 << 12, "direct_sum", None),
+    "chunked_13_bit_table": (1 | 4, 1 << 15, 1 << 12, None, None),
+    "bucket_split": (1, 1 << 16, 1 << 16, "bucket_split", None),
+    "fused_tail_one_record": (2, 1 << 10, 1 << 10, None, None),
+    "bucket_per_lane_plain_15_bit": (2, (1 << 17) + 1, (1 << 17) + 1, "bucket_per_lane", None),
+    "bucket_per_lane_plain_16_bit": (2, (1 << 18) + 1, (1 << 18) + 1, "bucket_per_lane", None),
+    "bucket_per_lane_20_bit_table": (1, 1 << 20, (1 << 18) + 1, "bucket_per_lane", None),
+    "chunked_bpl_off": (2, (1 << 17) + 1, (1 << 17) + 1, None, "0"),
+}
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_edge_scalars_through_every_accumulation_form(ctx, monkeypatch, form):
+    """sum s_i G_i for a vector that opens with three rounds of edge_scalars(), closes with a fourth (the last lanes of the last
+    block) and is uniform in between -- few enough edge values that no skew probe sends the vector elsewhere: the counters say which
+    form ran, and no fallback re-ran it"""
+    from accumulation_amd import CommitterKey, Context, VariableBaseMSM
+    flags, gens, n, counter, bpl = FORMS[form]
+    c = ctx
+    if bpl is not None:
+        with monkeypatch.context() as m:  # (the context reads its switches when it is made)
+            m.setenv("AMSM_BPL", bpl)
+            c = Context(VESTA.curve_id)
+    try:
+        ck = CommitterKey.generate(c, SEED, gens, flags)
+        assert ck.precomputed == bool(flags & 1)
+        edge = edge_scalars()
+        pad = c.random_vector(17, n, False)  # pyref.rng_fr's stream (test_vector_kernels)
+        sc = ints(pad.download())
+        pad.free()
+        assert n >= 4 * len(edge)
+        sc[:3 * len(edge)] = edge * 3
+        sc[n - len(edge):] = edge
+        v = c.upload(h.scalars_to_np(sc))
+        before = c.pipeline_stats()
+        res = VariableBaseMSM.multi_scalar_mul(ck, v, mont=False)
+        moved = {k: x - before[k] for k, x in c.pipeline_stats().items() if x != before[k]}
+        assert moved == ({counter: 1} if counter else {}), (form, moved)
+        assert got(*res) == expect(mults(SEED, n), sc), form
+        v.free()
+        ck.free()
+    finally:
+        if c is not ctx:
+            c.close()
 
 
 def test_unit_scalars_summed_apart(ctx):
