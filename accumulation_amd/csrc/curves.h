@@ -45,6 +45,17 @@ struct VestaCurve {  // ark-vesta 0.2: y^2 = x^3 + 5, cofactor 1; Fq = Pallas Fr
   static constexpr u64 cofactor[2] = {1, 0};
 };
 
+struct Bn254Curve {  // ark-bn254 G1 (alt_bn128): y^2 = x^3 + 3, cofactor 1, generator (1, 2)
+  using Fq = Bn254Fq;
+  using Fr = Bn254Fr;
+  static constexpr int id = AMSM_BN254_G1;
+  static constexpr int b = 3;
+  static constexpr bool subgroup_check = false;
+  static constexpr u64 gx[4] = {1, 0, 0, 0};
+  static constexpr u64 gy[4] = {2, 0, 0, 0};
+  static constexpr u64 cofactor[2] = {1, 0};
+};
+
 // base field pack -> its curve
 template <class Fq>
 struct CurveOf;
@@ -60,6 +71,10 @@ template <>
 struct CurveOf<VestaFq> {
   using type = VestaCurve;
 };
+template <>
+struct CurveOf<Bn254Fq> {
+  using type = Bn254Curve;
+};
 
 // f(Curve{}) for the curve with this id; `unknown` for any other id
 template <class R, class F>
@@ -68,6 +83,7 @@ R with_curve_or(int curve, R unknown, F&& f) {
     case AMSM_PALLAS: return f(PallasCurve{});
     case AMSM_BLS12_381_G1: return f(Bls12381Curve{});
     case AMSM_VESTA: return f(VestaCurve{});
+    case AMSM_BN254_G1: return f(Bn254Curve{});  // (id 3 is not a curve: include/amsm.h)
     default: return unknown;
   }
 }

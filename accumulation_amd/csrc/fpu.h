@@ -1,5 +1,5 @@
-// Unsaturated-limb Montgomery arithmetic for the base fields of the MSM hot loop (gfx950): Pallas Fq and Vesta Fq on
-// 9 x 29 bits, BLS12-381 Fq on 14 x 28 bits.
+// Unsaturated-limb Montgomery arithmetic for the base fields of the MSM hot loop (gfx950): Pallas Fq, Vesta Fq and
+// BN254 Fq on 9 x 29 bits, BLS12-381 Fq on 14 x 28 bits.
 //
 // gfx950 has no carry-in on v_mad_u64_u32 and a VALU carry write costs wait states, so the saturated 8 x 32-bit
 // schedule (fp_mul_gfx950.h) pays one v_addc per product.  Here an element is L limbs of B bits (Pallas Fq: 9 x 29,
@@ -12,7 +12,9 @@
 //   * "tight"  : limbs 0..L-2 < 2^B, value < 2^(B*L).  Everything held in registers between operations is tight.
 //   * "lazy"   : limbs < 2^(B+1), only allowed as ONE operand of a multiplication.
 //   * values are only bounded, not reduced: a multiplication gives  out < p + A*B / 2^(B*L)  and the group-law
-//     formulas in ec.h carry the bound of every intermediate in comments (cap = 2^261 ~ 128 p for Pallas and Vesta).
+//     formulas in ec.h carry the bound of every intermediate in comments (cap = 2^261 ~ 128 p for Pallas and Vesta,
+//     169 p for BN254: a value that is only known to be TIGHT may be as large as 169 p there -- nothing may canonicalise one with
+//     a KMAX chosen from "tight" alone; every u_canon / u_is_zero_mod call site has a bound from the formulas).
 //   * memory holds canonical values (< p), packed into W 32-bit words, in the INTERNAL Montgomery radix R'.  The
 //     C ABI's radix is R = 2^(32 W); fe_import / fe_export convert (one multiplication by a constant) at the
 //     edges (key load / read, the final fold of an MSM, amsm_points_fold), see DESIGN.md.
@@ -52,6 +54,29 @@ struct VestaFqU {  // Vesta Fq = Pallas Fr: the same shape as PallasFqU (p_0 = 1
   AMSM_TABLE(one, 9, 0x1fffff81u, 0x068ad507u, 0x100e85dau, 0x1435ee7eu, 0x1ffeefefu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x003fffffu)
   AMSM_TABLE(k_import, 9, 0x1ffff001u, 0x0ca6d907u, 0x01b40647u, 0x0db0c57eu, 0x1fddbb8bu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x003fffffu)
   AMSM_TABLE(k_export, 9, 0x1ffffffdu, 0x1959f4e7u, 0x108159d6u, 0x186a17c6u, 0x1ffff992u, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x003fffffu)
+};
+
+struct Bn254Fq;
+// BN254 Fq: 254 bits, R' / p = 169.28 (more head-room than Pallas's 127.99, so every `[< k p]` line of ec.h holds).  The first
+// 9 x 29 field on the GENERAL reduction path: all nine limbs of p are non-zero, p_0 != 1 (m_k costs a multiplication by NINV and
+// a product by p_0) and no limb is a power of two -- 9 x 9 reduction products per multiplication against Pallas's 5 x 9.
+// Column sums: 9 products with one lazy operand (< 2^59 each) + 9 reduction products (< 2^58) + the carry stay below 2^63; two
+// product sets with one lazy operand each (u_mul_add_mul) below 18 * 2^59 + 9 * 2^58 + 2^35 < 2^64.
+struct Bn254FqU {
+  using Sat = Bn254Fq;
+  static constexpr int L = 9;
+  static constexpr int W = 8;
+  static constexpr int B = 29;
+  static constexpr bool UNSAT = true;
+  static constexpr u32 NINV = 0x04866389u;  // -p^-1 mod 2^B
+  // measured both ways in one run of tools/fp_bench.hip (MI355X, cycles per SIMD at 2 waves per SIMD, chain / no chain): multiplication
+  // 985 / 998, squaring 826 / 820, mixed addition 10 330 / 10 357 -- the multiplication gains 1-2 % at every occupancy, the mixed
+  // addition is within 0.5 % either way, and k_accum_bpl keeps 3 waves without scratch with it
+  static constexpr bool CHAIN = true;
+  AMSM_TABLE(mod, 9, 0x187cfd47u, 0x010460b6u, 0x1c72a34fu, 0x02d522d0u, 0x1585d978u, 0x02db40c0u, 0x00a6e141u, 0x0e5c2634u, 0x0030644eu)
+  AMSM_TABLE(one, 9, 0x157ccc21u, 0x141c2758u, 0x185230d3u, 0x014c0419u, 0x0aa36fb9u, 0x1d4240ceu, 0x11d54c07u, 0x052ac7a8u, 0x000dc836u)
+  AMSM_TABLE(k_import, 9, 0x13349ca1u, 0x1a5d84a8u, 0x0a3e5cacu, 0x100249e0u, 0x12b951e8u, 0x0e92d304u, 0x14cb95b3u, 0x041b9d3du, 0x00058003u)
+  AMSM_TABLE(k_export, 9, 0x058f0d9du, 0x1aea1c6eu, 0x11c2cf74u, 0x11d651ebu, 0x1462c0a7u, 0x11b7bc3cu, 0x1cbd99bau, 0x183340fbu, 0x000e0a77u)
 };
 
 struct Bls12381Fq;
@@ -252,8 +277,10 @@ AMSM_DEV Fe<P> u_mul_add_mul(const Fe<P>& a, const Fe<P>& b, const Fe<P>& c, con
   return r;
 }
 
-// sum_{t < K} a[t] b[t] / 2^(B*L) mod p with ONE reduction (K <= 4 products of tight operands: 4 * 9 * 2^58 plus the reduction
-// terms stay below 2^64 per column).  Gives: tight, value < p + sum a[t] b[t] / 2^(B*L).
+// sum_{t < K} a[t] b[t] / 2^(B*L) mod p with ONE reduction (K <= 4 products of tight operands).  Per column: 4 * 9 products below
+// 2^58 plus one reduction product below 2^58 per non-zero limb of p -- six for Pallas and Vesta, (36 + 6) * 2^58; nine for BN254,
+// (36 + 9) * 2^58 = 45 * 2^58 -- plus a carry below 2^35: under 2^64 = 64 * 2^58 either way.
+// Gives: tight, value < p + sum a[t] b[t] / 2^(B*L).
 template <class P, int K>
 AMSM_DEV Fe<P> u_dot(const Fe<P>* a, const Fe<P>* b) {
   static_assert(K >= 1 && K <= 4, "column accumulators hold four products");

@@ -511,5 +511,6 @@ void launch_tv_probe(hipStream_t st, const u32* scalars, u32 n, u32* out16, cons
 AMSM_FR_LAUNCHERS(PallasFr)
 AMSM_FR_LAUNCHERS(Bls12381Fr)
 AMSM_FR_LAUNCHERS(VestaFr)
+AMSM_FR_LAUNCHERS(Bn254Fr)
 
 }  // namespace amsm

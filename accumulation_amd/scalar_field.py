@@ -10,6 +10,7 @@ MODULI = {
     ffi.AMSM_PALLAS: 0x40000000000000000000000000000000224698FC0994A8DD8C46EB2100000001,
     ffi.AMSM_BLS12_381_G1: 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
     ffi.AMSM_VESTA: 0x40000000000000000000000000000000224698FC094CF91B992D30ED00000001,  # = Pallas's base field
+    ffi.AMSM_BN254_G1: 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001,
 }
 _R = 1 << 256
 _M64 = (1 << 64) - 1

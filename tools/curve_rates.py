@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""MSM rates of Pallas and Vesta in ONE process, timed the way bench.py times its headline: a generated key (bench.py's point
+"""MSM rates of Pallas and the other 9 x 29-bit curves (Vesta, BN254 G1) in ONE process, timed the way bench.py times its headline: a generated key (bench.py's point
 seed), four resident scalar vectors (its scalar seed) cycled over the steps, PREHEAT untimed MSMs, W warm-up steps, then K steps
 issued as one batch call between two device synchronisations.  Sizes 2^16, 2^18, 2^20, each with a precomputed and a plain key;
-the two curves alternate per configuration so that clock drift hits both alike.
+the curves alternate per configuration so that clock drift hits all alike.
 
-    python tools/curve_rates.py [--steps K] [--warmup W] [--sizes 16,18,20] [--out FILE]
+    python tools/curve_rates.py [--curves pallas,vesta] [--steps K] [--warmup W] [--sizes 16,18,20] [--keys precomputed,plain]
+                                [--only 20:plain,...] [--out FILE]
 
-One JSON line per (curve, size, key) and a summary line with Vesta / Pallas per configuration and the source hash of the tree."""
+One JSON line per (curve, size, key) and a summary line with <curve> / Pallas per configuration and the source hash of the tree.
+Pallas is always measured: it is the reference point of every ratio."""
 from __future__ import annotations
 
 import argparse
@@ -35,6 +37,11 @@ def source_hash() -> str:
     return hs.hexdigest()[:16]
 
 
+def curve_ids() -> dict:
+    from accumulation_amd import ffi
+    return {"pallas": ffi.AMSM_PALLAS, "vesta": ffi.AMSM_VESTA, "bn254_g1": ffi.AMSM_BN254_G1}
+
+
 def rate(curve: int, log2n: int, precomp: bool, steps: int, warmup: int) -> dict:
     from accumulation_amd import CommitterKey, Context, VariableBaseMSM, ffi
     ctx = Context(curve)
@@ -57,7 +64,7 @@ def rate(curve: int, log2n: int, precomp: bool, steps: int, warmup: int) -> dict
         for v in vecs:
             v.free()
         ck.free()
-        return {"curve": {ffi.AMSM_PALLAS: "pallas", ffi.AMSM_VESTA: "vesta"}[curve], "log2n": log2n,
+        return {"curve": {v: k for k, v in curve_ids().items()}[curve], "log2n": log2n,
                 "key": "precomputed" if precomp else "plain", "pairs_per_s": n * steps / elapsed, "ms_per_msm": elapsed / steps * 1e3,
                 "steps": steps, "warmup": warmup}
     finally:
@@ -70,19 +77,27 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--sizes", default="16,18,20")
     ap.add_argument("--out", default=None, help="also write the lines to this file")
+    ap.add_argument("--curves", default="pallas,vesta", help="comma-separated: pallas, vesta, bn254_g1")
+    ap.add_argument("--keys", default="precomputed,plain")
+    ap.add_argument("--only", default=None, help="comma-separated size:key pairs to keep of sizes x keys, e.g. 16:precomputed,20:plain")
     args = ap.parse_args()
-    from accumulation_amd import ffi
-    lines, ratio = [], {}
+    ids = curve_ids()
+    names = ["pallas"] + [c for c in args.curves.split(",") if c != "pallas"]
+    only = None if args.only is None else {tuple(x.split(":")) for x in args.only.split(",")}
+    lines, ratio = [], {c: {} for c in names[1:]}
     for log2n in (int(s) for s in args.sizes.split(",")):
-        for precomp in (True, False):
+        for key in args.keys.split(","):
+            if only is not None and (str(log2n), key) not in only:
+                continue
             r = {}
-            for curve in (ffi.AMSM_PALLAS, ffi.AMSM_VESTA):
-                line = rate(curve, log2n, precomp, args.steps, args.warmup)
-                r[line["curve"]] = line["pairs_per_s"]
+            for name in names:
+                line = rate(ids[name], log2n, key == "precomputed", args.steps, args.warmup)
+                r[name] = line["pairs_per_s"]
                 lines.append(line)
                 print(json.dumps(line), flush=True)
-            ratio[f"2^{log2n} {'precomputed' if precomp else 'plain'}"] = round(r["vesta"] / r["pallas"], 4)
-    summary = {"summary": "vesta / pallas pairs per second", "ratio": ratio, "source": source_hash()}
+            for name in names[1:]:
+                ratio[name][f"2^{log2n} {key}"] = round(r[name] / r["pallas"], 4)
+    summary = {"summary": "pairs per second relative to pallas in the same run", "ratio": ratio, "source": source_hash()}
     print(json.dumps(summary), flush=True)
     if args.out:
         with open(args.out, "w") as f:

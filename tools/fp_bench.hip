@@ -6,6 +6,10 @@
 #include <vector>
 #include "ec.h"
 using namespace amsm;
+// Bn254FqU with the other CHAIN setting (fpu.h: u_opaque), so that ONE run decides it: same tables, same kernels
+struct Bn254FqUOther : Bn254FqU {
+  static constexpr bool CHAIN = !Bn254FqU::CHAIN;
+};
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 
 template <class P, int MODE, int MINW = 1>
@@ -67,6 +71,14 @@ int main() {
     run<PallasFqU, 4>("pallas 9x29 fe_sqr", w, 2000, 1, d_out);
     run<PallasFqU, 3>("pallas 9x29 xyzz_madd", w, 400, 1, d_out);
     run<PallasFqU, 3, 4>("pallas 9x29 xyzz_madd (<=128 VGPR)", w, 400, 1, d_out);
+    run<Bn254FqU, 0>(Bn254FqU::CHAIN ? "bn254 9x29 fe_mul (chain)" : "bn254 9x29 fe_mul (no chain)", w, 2000, 1, d_out);
+    run<Bn254FqU, 4>(Bn254FqU::CHAIN ? "bn254 9x29 fe_sqr (chain)" : "bn254 9x29 fe_sqr (no chain)", w, 2000, 1, d_out);
+    run<Bn254FqU, 3>(Bn254FqU::CHAIN ? "bn254 9x29 xyzz_madd (chain)" : "bn254 9x29 xyzz_madd (no chain)", w, 400, 1, d_out);
+    run<Bn254FqUOther, 0>(Bn254FqUOther::CHAIN ? "bn254 9x29 fe_mul (chain)" : "bn254 9x29 fe_mul (no chain)", w, 2000, 1, d_out);
+    run<Bn254FqUOther, 4>(Bn254FqUOther::CHAIN ? "bn254 9x29 fe_sqr (chain)" : "bn254 9x29 fe_sqr (no chain)", w, 2000, 1, d_out);
+    run<Bn254FqUOther, 3>(Bn254FqUOther::CHAIN ? "bn254 9x29 xyzz_madd (chain)" : "bn254 9x29 xyzz_madd (no chain)", w, 400, 1, d_out);
+    run<Bn254Fq, 0>("bn254 fe_mul (asm)", w, 2000, 1, d_out);
+    run<Bn254Fq, 3>("bn254 xyzz_madd", w, 400, 1, d_out);
     run<Bls12381Fq, 0>("bls12-381 fe_mul (asm)", w, 1000, 1, d_out);
     run<Bls12381Fq, 3>("bls12-381 xyzz_madd", w, 200, 1, d_out);
     run<Bls12381FqU, 0>("bls12-381 14x28 fe_mul", w, 1000, 1, d_out);

@@ -29,6 +29,8 @@ field("Bls12381Fq", 12, 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2
 field("Bls12381Fr", 8, 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001)
 field("VestaFq", 8, 0x40000000000000000000000000000000224698FC0994A8DD8C46EB2100000001)  # = Pallas Fr
 field("VestaFr", 8, 0x40000000000000000000000000000000224698FC094CF91B992D30ED00000001)  # = Pallas Fq
+field("Bn254Fq", 8, 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47)
+field("Bn254Fr", 8, 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001)
 
 MAX_TERMS = 11  # terms per asm statement (operand limit 30: 2*terms + acc + c2 + 3 sgpr temps)
 
@@ -181,7 +183,7 @@ def main():
     for name in FIELDS:
         hdr.append(gen_twin(name, twin_of(name)) if twin_of(name) else gen_field(name))
         hdr.append("")
-    for name in ("PallasFr", "Bls12381Fr"):  # the scalar-field vector kernels (vec_kernels.h)
+    for name in ("PallasFr", "Bls12381Fr", "Bn254Fr"):  # the scalar-field vector kernels (vec_kernels.h)
         for T in (2, 3):
             hdr.append(gen_field(name, T))
             hdr.append("")

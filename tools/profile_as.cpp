@@ -8,7 +8,7 @@
 // configs 4, 5) get the same treatment here.
 //
 //   profile_as <scheme: trivial_pc_as | ipa_pc_as | hp_as | r1cs_nark_as | all> <log_min> <log_max>
-//              [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] [--curve 0|1|2] [--constant] [--uniform] [--no-roundtrip]
+//              [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] [--curve 0|1|2|4] [--constant] [--uniform] [--no-roundtrip]
 //              [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--transparent DOMAIN]
 //   --transparent DOMAIN  every committer key is a transparent one over DOMAIN (amsm.h amsm_bases_sample, the setup_transparent of
 //                the headers) instead of the seeded synthetic key; the Python mirrors take the same key from setup(domain=...).
@@ -75,9 +75,19 @@ static void dump_records(const Opt& o, const std::vector<uint8_t>& acc, const st
 template <class F>
 static double timed_proves(const Opt& o, F&& prove_once);
 
-struct HarnessRng {  // ark_std::test_rng() stand-in: a fixed stream
+// ark_std::test_rng() stand-in: a fixed stream of 254-bit integers, reduced mod r -- the schemes' rng returns CANONICAL scalars
+// (amsm_hp_as.hpp: Rng).  Every 255-bit r exceeds the stream, so nothing is subtracted there; BN254's r lies between 2^253 and 2^254:
+// one conditional subtraction (the Python mirror takes the same integers mod r).
+struct HarnessRng {
   uint64_t seed, i = 0;
-  explicit HarnessRng(uint64_t s) : seed(s) {}
+  Fr r_minus_1{};
+  HarnessRng(uint64_t s, int curve) : seed(s) {
+    const Fr zero = {0, 0, 0, 0}, one = {1, 0, 0, 0};
+    Fr one_m, neg_m;
+    check(amsm_fr_to_mont(curve, one.data(), 1, one_m.data()), "amsm_fr_to_mont");
+    check(amsm_fr_sub(curve, zero.data(), one_m.data(), 1, neg_m.data()), "amsm_fr_sub");
+    check(amsm_fr_from_mont(curve, neg_m.data(), 1, r_minus_1.data()), "amsm_fr_from_mont");
+  }
   Fr field() {
     Fr x;
     for (uint64_t k = 0; k < 4; k++) {
@@ -89,6 +99,20 @@ struct HarnessRng {  // ark_std::test_rng() stand-in: a fixed stream
     }
     i++;
     x[3] &= (1ull << 62) - 1;
+    bool above = false;  // x > r - 1 ?
+    for (int k = 3; k >= 0; k--)
+      if (x[k] != r_minus_1[k]) {
+        above = x[k] > r_minus_1[k];
+        break;
+      }
+    if (above) {  // x -= r, as x - (r - 1) - 1
+      unsigned __int128 borrow = 1;
+      for (int k = 0; k < 4; k++) {
+        unsigned __int128 d = (unsigned __int128)x[k] - r_minus_1[k] - borrow;
+        x[k] = (uint64_t)d;
+        borrow = (uint64_t)(d >> 64) ? 1 : 0;
+      }
+    }
     return x;
   }
 };
@@ -142,7 +166,7 @@ static void profile_hp(const Opt& o, int lg, bool harness_shape) {
   Context ctx = make_context(o);
   hp_as::FrOps fr{o.curve};
   const size_t n = (size_t)1 << lg;
-  HarnessRng hr(0xA11CE ^ o.seed);
+  HarnessRng hr(0xA11CE ^ o.seed, o.curve);
   hp_as::Rng zk_rng = harness_shape ? hp_as::Rng([&hr]() { return hr.field(); }) : hp_as::Rng();
   Result r;
   auto t0 = Clock::now();
@@ -208,7 +232,7 @@ static void profile_nark_as(const Opt& o, int lg, bool harness_shape) {
   hp_as::FrOps fr{o.curve};
   const size_t n_con = (size_t)1 << lg, n_inputs = 5, n_inst = n_inputs + 1;
   const Fr one = {1, 0, 0, 0};
-  HarnessRng hr(0xB0B ^ o.seed);
+  HarnessRng hr(0xB0B ^ o.seed, o.curve);
   hp_as::Rng zk_rng = harness_shape ? hp_as::Rng([&hr]() { return hr.field(); }) : hp_as::Rng();
   Result r;
   auto t0 = Clock::now();
@@ -299,7 +323,7 @@ static void profile_nark(const Opt& o, int lg, bool make_zk) {
   const size_t n_con = (size_t)1 << lg, n_inputs = 5, n_inst = n_inputs + 1;
   const size_t n_wit = (n_con > 5 ? n_con - 5 : 1) + 1;  // a, b, then num_witness_variables - 1 copies of a
   const Fr one = {1, 0, 0, 0};
-  HarnessRng hr(0xB0B ^ o.seed);
+  HarnessRng hr(0xB0B ^ o.seed, o.curve);
   hp_as::Rng zk_rng = make_zk ? hp_as::Rng([&hr]() { return hr.field(); }) : hp_as::Rng();
   Result r;
   Fr a = hr.field(), b = hr.field();
@@ -350,7 +374,7 @@ static void profile_ipa(const Opt& o, int lg, bool harness_shape) {
   Context ctx = make_context(o);
   ipa_pc::FrX fr(o.curve);
   const size_t degree = ((size_t)1 << lg) - 1;
-  HarnessRng hr(0xD1 ^ o.seed);
+  HarnessRng hr(0xD1 ^ o.seed, o.curve);
   hp_as::Rng prng([&hr]() { return hr.field(); });
   hp_as::Rng zk_rng = harness_shape ? prng : hp_as::Rng();
   Result r;
@@ -403,7 +427,7 @@ static void profile_trivial(const Opt& o, int lg, bool harness_shape) {
   Context ctx = make_context(o);
   hp_as::FrOps fr{o.curve};
   const size_t degree = ((size_t)1 << lg) - 1;
-  HarnessRng hr(0x7121A1 ^ o.seed);
+  HarnessRng hr(0x7121A1 ^ o.seed, o.curve);
   Result r;
   CommitterKey pp = o.transparent ? TrivialPC::setup_transparent(ctx, degree, o.domain) : TrivialPC::setup(ctx, degree, 0x7121A1);
   CommitterKey ck = TrivialPC::trim(pp, degree);
@@ -469,7 +493,7 @@ int main(int argc, char** argv) {
   Opt o;
   if (argc < 4) {
     fprintf(stderr, "usage: %s <scheme|all> <log_min> <log_max> [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] "
-                    "[--curve 0|1|2] [--constant] [--uniform] [--no-roundtrip] [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--replicate-below L] [--transparent DOMAIN]\n", argv[0]);
+                    "[--curve 0|1|2|4] [--constant] [--uniform] [--no-roundtrip] [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--replicate-below L] [--transparent DOMAIN]\n", argv[0]);
     return 2;
   }
   o.scheme = argv[1];
