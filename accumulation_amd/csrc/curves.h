@@ -56,6 +56,17 @@ struct Bn254Curve {  // ark-bn254 G1 (alt_bn128): y^2 = x^3 + 3, cofactor 1, gen
   static constexpr u64 cofactor[2] = {1, 0};
 };
 
+struct GrumpkinCurve {  // ark-grumpkin: y^2 = x^3 - 17, cofactor 1; Fq = BN254 Fr, Fr = BN254 Fq (the other half of that cycle)
+  using Fq = GrumpkinFq;
+  using Fr = GrumpkinFr;
+  static constexpr int id = AMSM_GRUMPKIN;
+  static constexpr int b = -17;  // host_serialize.h: curve_b_mont gives q - 17
+  static constexpr bool subgroup_check = false;
+  static constexpr u64 gx[4] = {1, 0, 0, 0};
+  static constexpr u64 gy[4] = {0x833fc48d823f272cull, 0x2d270d45f1181294ull, 0xcf135e7506a45d63ull, 0x0000000000000002ull};  // y^2 = -16
+  static constexpr u64 cofactor[2] = {1, 0};
+};
+
 // base field pack -> its curve
 template <class Fq>
 struct CurveOf;
@@ -75,6 +86,10 @@ template <>
 struct CurveOf<Bn254Fq> {
   using type = Bn254Curve;
 };
+template <>
+struct CurveOf<GrumpkinFq> {
+  using type = GrumpkinCurve;
+};
 
 // f(Curve{}) for the curve with this id; `unknown` for any other id
 template <class R, class F>
@@ -83,7 +98,8 @@ R with_curve_or(int curve, R unknown, F&& f) {
     case AMSM_PALLAS: return f(PallasCurve{});
     case AMSM_BLS12_381_G1: return f(Bls12381Curve{});
     case AMSM_VESTA: return f(VestaCurve{});
-    case AMSM_BN254_G1: return f(Bn254Curve{});  // (id 3 is not a curve: include/amsm.h)
+    case AMSM_BN254_G1: return f(Bn254Curve{});  // (ids 3 and 5 are not curves: include/amsm.h)
+    case AMSM_GRUMPKIN: return f(GrumpkinCurve{});
     default: return unknown;
   }
 }

@@ -124,6 +124,28 @@ struct Bn254Fr {  // scalar field of BN254; 254 bits, 2-adicity 28
   AMSM_TABLE(r2, 8, 0xae216da7u, 0x1bb8e645u, 0xe35c59e3u, 0x53fe3ab1u, 0x53bb8085u, 0x8c49833du, 0x7f4e44a5u, 0x0216d0b1u)
 };
 
+// Grumpkin (the other half of the BN254 cycle): its base field is BN254's scalar field and its scalar field BN254's base field.
+// Types of their own with the same tables, as Vesta's are: dispatch (DevField, CurveOf, is_same) is on the type.
+struct GrumpkinFq {  // base field of Grumpkin (= BN254 Fr); 254 bits, 2-adicity 28
+  static constexpr int L = 8;  // register limbs
+  static constexpr int W = 8;  // 32-bit words in memory
+  static constexpr bool UNSAT = false;
+  static constexpr u32 INV = 0xefffffffu;
+  AMSM_TABLE(mod, 8, 0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u)
+  AMSM_TABLE(one, 8, 0x4ffffffbu, 0xac96341cu, 0x9f60cd29u, 0x36fc7695u, 0x7879462eu, 0x666ea36fu, 0x9a07df2fu, 0x0e0a77c1u)
+  AMSM_TABLE(r2, 8, 0xae216da7u, 0x1bb8e645u, 0xe35c59e3u, 0x53fe3ab1u, 0x53bb8085u, 0x8c49833du, 0x7f4e44a5u, 0x0216d0b1u)
+};
+
+struct GrumpkinFr {  // scalar field of Grumpkin (= BN254 Fq); 254 bits
+  static constexpr int L = 8;  // register limbs
+  static constexpr int W = 8;  // 32-bit words in memory
+  static constexpr bool UNSAT = false;
+  static constexpr u32 INV = 0xe4866389u;
+  AMSM_TABLE(mod, 8, 0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u)
+  AMSM_TABLE(one, 8, 0xc58f0d9du, 0xd35d438du, 0xf5c70b3du, 0x0a78eb28u, 0x7879462cu, 0x666ea36fu, 0x9a07df2fu, 0x0e0a77c1u)
+  AMSM_TABLE(r2, 8, 0x538afa89u, 0xf32cfc5bu, 0xd44501fbu, 0xb5e71911u, 0x0a417ff6u, 0x47ab1effu, 0xcab8351fu, 0x06d89f71u)
+};
+
 // ------------------------------------------------------------------------------------------------
 // Element type and helpers
 // ------------------------------------------------------------------------------------------------
@@ -133,10 +155,10 @@ struct Fe {
 };
 
 }  // namespace amsm
-#include "fpu.h"  // unsaturated-limb packs (PallasFqU, VestaFqU, Bls12381FqU, Bn254FqU) and their u_* primitives
+#include "fpu.h"  // unsaturated-limb packs (PallasFqU, VestaFqU, Bls12381FqU, Bn254FqU, GrumpkinFqU) and their u_* primitives
 namespace amsm {
 
-// Field the DEVICE kernels compute in for a given ABI field: Pallas, Vesta and BN254 Fq run on 9 x 29-bit unsaturated limbs
+// Field the DEVICE kernels compute in for a given ABI field: Pallas, Vesta, BN254 and Grumpkin Fq run on 9 x 29-bit unsaturated limbs
 // (internal Montgomery radix 2^261, fpu.h), BLS12-381 Fq on 14 x 28-bit limbs (radix 2^392).  (The saturated 32-bit-limb
 // schedules serve both scalar fields; for the base fields they measured 21 % / 23 % slower: DESIGN.md 4.1.)
 template <class Fq>
@@ -158,6 +180,10 @@ struct DevField<VestaFq> {  // the limb shape of Pallas Fq (fpu.h: VestaFqU)
 template <>
 struct DevField<Bn254Fq> {  // 9 x 29 bits through the general reduction (fpu.h: Bn254FqU)
   using type = Bn254FqU;
+};
+template <>
+struct DevField<GrumpkinFq> {  // the same general reduction over the other modulus of the cycle (fpu.h: GrumpkinFqU)
+  using type = GrumpkinFqU;
 };
 
 template <class P>

@@ -1,5 +1,5 @@
-// Unsaturated-limb Montgomery arithmetic for the base fields of the MSM hot loop (gfx950): Pallas Fq, Vesta Fq and
-// BN254 Fq on 9 x 29 bits, BLS12-381 Fq on 14 x 28 bits.
+// Unsaturated-limb Montgomery arithmetic for the base fields of the MSM hot loop (gfx950): Pallas Fq, Vesta Fq,
+// BN254 Fq and Grumpkin Fq on 9 x 29 bits, BLS12-381 Fq on 14 x 28 bits.
 //
 // gfx950 has no carry-in on v_mad_u64_u32 and a VALU carry write costs wait states, so the saturated 8 x 32-bit
 // schedule (fp_mul_gfx950.h) pays one v_addc per product.  Here an element is L limbs of B bits (Pallas Fq: 9 x 29,
@@ -13,7 +13,7 @@
 //   * "lazy"   : limbs < 2^(B+1), only allowed as ONE operand of a multiplication.
 //   * values are only bounded, not reduced: a multiplication gives  out < p + A*B / 2^(B*L)  and the group-law
 //     formulas in ec.h carry the bound of every intermediate in comments (cap = 2^261 ~ 128 p for Pallas and Vesta,
-//     169 p for BN254: a value that is only known to be TIGHT may be as large as 169 p there -- nothing may canonicalise one with
+//     169 p for BN254 and Grumpkin: a value that is only known to be TIGHT may be as large as 169 p there -- nothing may canonicalise one with
 //     a KMAX chosen from "tight" alone; every u_canon / u_is_zero_mod call site has a bound from the formulas).
 //   * memory holds canonical values (< p), packed into W 32-bit words, in the INTERNAL Montgomery radix R'.  The
 //     C ABI's radix is R = 2^(32 W); fe_import / fe_export convert (one multiplication by a constant) at the
@@ -77,6 +77,29 @@ struct Bn254FqU {
   AMSM_TABLE(one, 9, 0x157ccc21u, 0x141c2758u, 0x185230d3u, 0x014c0419u, 0x0aa36fb9u, 0x1d4240ceu, 0x11d54c07u, 0x052ac7a8u, 0x000dc836u)
   AMSM_TABLE(k_import, 9, 0x13349ca1u, 0x1a5d84a8u, 0x0a3e5cacu, 0x100249e0u, 0x12b951e8u, 0x0e92d304u, 0x14cb95b3u, 0x041b9d3du, 0x00058003u)
   AMSM_TABLE(k_export, 9, 0x058f0d9du, 0x1aea1c6eu, 0x11c2cf74u, 0x11d651ebu, 0x1462c0a7u, 0x11b7bc3cu, 0x1cbd99bau, 0x183340fbu, 0x000e0a77u)
+};
+
+struct GrumpkinFq;
+// Grumpkin Fq = BN254 Fr: 254 bits, R' / q = 169.28, the head-room of BN254 Fq, so every `[< k p]` line of ec.h holds.  The second
+// field on the GENERAL reduction path: no limb of q is zero, none of limbs 1..8 is a power of two, q_0 = 2^28 + 1 and
+// NINV = 2^28 - 1 != 2^29 - 1, so u_red_low takes the general branch (m_k = lo * NINV, then one ordinary MAD by q_0: no shortcut
+// for this q_0 is taken) -- 9 x 9 reduction products per multiplication.  The column sums of Bn254FqU above hold unchanged:
+// the limb widths are the same.
+struct GrumpkinFqU {
+  using Sat = GrumpkinFq;
+  static constexpr int L = 9;
+  static constexpr int W = 8;
+  static constexpr int B = 29;
+  static constexpr bool UNSAT = true;
+  static constexpr u32 NINV = 0x0fffffffu;  // -q^-1 mod 2^B
+  // measured both ways in one run of tools/fp_bench.hip beside BN254's lines (MI355X, cycles per SIMD at 2 waves per SIMD, chain / no
+  // chain): multiplication 959 / 929, squaring 868 / 889, mixed addition 9 639 / 9 934 -- the mixed addition decides, and its 3 %
+  // are six times what BN254's two lines differ by in that run (10 413 / 10 363); profiles/grumpkin_fp_bench.txt, DESIGN.md 4.1
+  static constexpr bool CHAIN = true;
+  AMSM_TABLE(mod, 9, 0x10000001u, 0x1f0fac9fu, 0x0e5c2450u, 0x07d090f3u, 0x1585d283u, 0x02db40c0u, 0x00a6e141u, 0x0e5c2634u, 0x0030644eu)
+  AMSM_TABLE(one, 9, 0x0fffff57u, 0x1ea70ab4u, 0x052c068bu, 0x17504f49u, 0x0aa8075bu, 0x1d4240ceu, 0x11d54c07u, 0x052ac7a8u, 0x000dc836u)
+  AMSM_TABLE(k_import, 9, 0x0fffead7u, 0x1d5444f4u, 0x04438aa5u, 0x03b4d096u, 0x134c84dau, 0x0e92d304u, 0x14cb95b3u, 0x041b9d3du, 0x00058003u)
+  AMSM_TABLE(k_export, 9, 0x0ffffffbu, 0x04b1a0e2u, 0x18334a6bu, 0x18ed2b3eu, 0x1462e36fu, 0x11b7bc3cu, 0x1cbd99bau, 0x183340fbu, 0x000e0a77u)
 };
 
 struct Bls12381Fq;
@@ -278,7 +301,7 @@ AMSM_DEV Fe<P> u_mul_add_mul(const Fe<P>& a, const Fe<P>& b, const Fe<P>& c, con
 }
 
 // sum_{t < K} a[t] b[t] / 2^(B*L) mod p with ONE reduction (K <= 4 products of tight operands).  Per column: 4 * 9 products below
-// 2^58 plus one reduction product below 2^58 per non-zero limb of p -- six for Pallas and Vesta, (36 + 6) * 2^58; nine for BN254,
+// 2^58 plus one reduction product below 2^58 per non-zero limb of p -- six for Pallas and Vesta, (36 + 6) * 2^58; nine for BN254 and Grumpkin,
 // (36 + 9) * 2^58 = 45 * 2^58 -- plus a carry below 2^35: under 2^64 = 64 * 2^58 either way.
 // Gives: tight, value < p + sum a[t] b[t] / 2^(B*L).
 template <class P, int K>

@@ -512,5 +512,6 @@ AMSM_FR_LAUNCHERS(PallasFr)
 AMSM_FR_LAUNCHERS(Bls12381Fr)
 AMSM_FR_LAUNCHERS(VestaFr)
 AMSM_FR_LAUNCHERS(Bn254Fr)
+AMSM_FR_LAUNCHERS(GrumpkinFr)
 
 }  // namespace amsm

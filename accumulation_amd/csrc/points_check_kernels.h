@@ -3,7 +3,7 @@
 //     0 valid            flagged infinite (coordinates ignored, as k_apply_inf ignores them), or (0, 0), or none of the below
 //     1 non-canonical    the integer in the words of x or of y is >= p (tested on the words as they arrive)
 //     2 off the curve    y^2 != x^3 + b
-//     3 off the subgroup [r]P != O (curves.h: subgroup_check -- BLS12-381 G1 only; Pallas, Vesta and BN254 G1 have cofactor 1)
+//     3 off the subgroup [r]P != O (curves.h: subgroup_check -- BLS12-381 G1 only; Pallas, Vesta, BN254 G1 and Grumpkin have cofactor 1)
 // -- in two kernels, so that the cheap pass does not inherit the ladder's registers:
 //   k_points_check_curve     every curve: rules 1 and 2, three multiplications per point over 64 or 96 bytes (memory-shaped: 16-byte
 //                            loads as k_points_import makes them).  Writes every status byte.

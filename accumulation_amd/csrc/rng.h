@@ -1,6 +1,6 @@
 // Synthetic input streams shared by device kernels and the host backend (counter-based splitmix64).
 //   rng_scalar      the MULTIPLIER stream: 254-bit integers k_i, only used for G_i = k_i G (any fixed set of distinct
-//                   subgroup points serves as a committer key).  On BN254 (r < 2^254) a k_i may exceed
+//                   subgroup points serves as a committer key).  On BN254 and Grumpkin (r < 2^254) a k_i may exceed
 //                   r: harmless, k_i G is taken over the integers (the oracle does the same) and equals (k_i mod r) G
 //   rng_scalar_fr   the SCALAR stream of amsm_vec_random: uniform in [0, r) of the curve's scalar field (round 6: the
 //                   254-bit stream never produced the 45 % of BLS12-381 scalars that have bit 254 set)
@@ -31,8 +31,8 @@ AMSM_HD void rng_scalar(u64 seed, u64 i, u32 out[8]) {
 
 // Uniform in [0, r): candidate t of scalar i = words (t << 40) + 4 i .. + 3 masked to 255 bits (the scalar fields have 254- or
 // 255-bit moduli), the first candidate below r wins (rejection sampling: exactly uniform; acceptance 0.50 Pallas and Vesta, 0.906
-// BLS12-381, 0.378 BN254).  After 64 rejections candidate 63 with bit 254 cleared: below 2^254 < r on the 255-bit fields
-// (probability < 2^-64); on BN254 (r < 2^254) the fallback is reached with probability 0.622^64 < 10^-13 per scalar and is no
+// BLS12-381, 0.378 BN254 and Grumpkin).  After 64 rejections candidate 63 with bit 254 cleared: below 2^254 < r on the 255-bit fields
+// (probability < 2^-64); on BN254 and Grumpkin (r < 2^254) the fallback is reached with probability 0.622^64 < 10^-13 per scalar and is no
 // longer guaranteed below r -- the oracle's rule is kept literally (oracle/pyref.py: rng_fr), not repaired on one side only.
 // The checkers restate it (pyref.py: rng_fr; the C restatement: ark_rng_scalars_fr; tools/ark_vectors/src/main.rs: rng_frs).
 template <class Fr>

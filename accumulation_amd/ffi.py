@@ -17,7 +17,8 @@ LIB_PATH = os.environ.get("AMSM_LIB_PATH") or os.path.join(_HERE, "libamsm.so")
 AMSM_PALLAS = 0
 AMSM_BLS12_381_G1 = 1
 AMSM_VESTA = 2
-AMSM_BN254_G1 = 4  # (3 is refused on purpose; 5 is left for Grumpkin)
+AMSM_BN254_G1 = 4
+AMSM_GRUMPKIN = 6  # (3 and 5 are not curves and are refused on purpose; Grumpkin is 6)
 
 AMSM_OK = 0
 AMSM_E_INVALID_ARG = -1

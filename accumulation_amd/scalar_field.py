@@ -11,6 +11,7 @@ MODULI = {
     ffi.AMSM_BLS12_381_G1: 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
     ffi.AMSM_VESTA: 0x40000000000000000000000000000000224698FC094CF91B992D30ED00000001,  # = Pallas's base field
     ffi.AMSM_BN254_G1: 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001,
+    ffi.AMSM_GRUMPKIN: 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47,  # = BN254's base field
 }
 _R = 1 << 256
 _M64 = (1 << 64) - 1

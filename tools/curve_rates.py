@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""MSM rates of Pallas and the other 9 x 29-bit curves (Vesta, BN254 G1) in ONE process, timed the way bench.py times its headline: a generated key (bench.py's point
+"""MSM rates of Pallas and the other 9 x 29-bit curves (Vesta, BN254 G1, Grumpkin) in ONE process, timed the way bench.py times its headline: a generated key (bench.py's point
 seed), four resident scalar vectors (its scalar seed) cycled over the steps, PREHEAT untimed MSMs, W warm-up steps, then K steps
 issued as one batch call between two device synchronisations.  Sizes 2^16, 2^18, 2^20, each with a precomputed and a plain key;
 the curves alternate per configuration so that clock drift hits all alike.
@@ -39,7 +39,8 @@ def source_hash() -> str:
 
 def curve_ids() -> dict:
     from accumulation_amd import ffi
-    return {"pallas": ffi.AMSM_PALLAS, "vesta": ffi.AMSM_VESTA, "bn254_g1": ffi.AMSM_BN254_G1}
+    return {"pallas": ffi.AMSM_PALLAS, "vesta": ffi.AMSM_VESTA, "bn254_g1": ffi.AMSM_BN254_G1,
+            "grumpkin": ffi.AMSM_GRUMPKIN}
 
 
 def rate(curve: int, log2n: int, precomp: bool, steps: int, warmup: int) -> dict:
@@ -77,7 +78,7 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--sizes", default="16,18,20")
     ap.add_argument("--out", default=None, help="also write the lines to this file")
-    ap.add_argument("--curves", default="pallas,vesta", help="comma-separated: pallas, vesta, bn254_g1")
+    ap.add_argument("--curves", default="pallas,vesta", help="comma-separated: pallas, vesta, bn254_g1, grumpkin")
     ap.add_argument("--keys", default="precomputed,plain")
     ap.add_argument("--only", default=None, help="comma-separated size:key pairs to keep of sizes x keys, e.g. 16:precomputed,20:plain")
     args = ap.parse_args()

@@ -6,9 +6,12 @@
 #include <vector>
 #include "ec.h"
 using namespace amsm;
-// Bn254FqU with the other CHAIN setting (fpu.h: u_opaque), so that ONE run decides it: same tables, same kernels
+// Bn254FqU / GrumpkinFqU with the other CHAIN setting (fpu.h: u_opaque), so that ONE run decides it: same tables, same kernels
 struct Bn254FqUOther : Bn254FqU {
   static constexpr bool CHAIN = !Bn254FqU::CHAIN;
+};
+struct GrumpkinFqUOther : GrumpkinFqU {
+  static constexpr bool CHAIN = !GrumpkinFqU::CHAIN;
 };
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 
@@ -79,6 +82,12 @@ int main() {
     run<Bn254FqUOther, 3>(Bn254FqUOther::CHAIN ? "bn254 9x29 xyzz_madd (chain)" : "bn254 9x29 xyzz_madd (no chain)", w, 400, 1, d_out);
     run<Bn254Fq, 0>("bn254 fe_mul (asm)", w, 2000, 1, d_out);
     run<Bn254Fq, 3>("bn254 xyzz_madd", w, 400, 1, d_out);
+    run<GrumpkinFqU, 0>(GrumpkinFqU::CHAIN ? "grumpkin 9x29 fe_mul (chain)" : "grumpkin 9x29 fe_mul (no chain)", w, 2000, 1, d_out);
+    run<GrumpkinFqU, 4>(GrumpkinFqU::CHAIN ? "grumpkin 9x29 fe_sqr (chain)" : "grumpkin 9x29 fe_sqr (no chain)", w, 2000, 1, d_out);
+    run<GrumpkinFqU, 3>(GrumpkinFqU::CHAIN ? "grumpkin 9x29 xyzz_madd (chain)" : "grumpkin 9x29 xyzz_madd (no chain)", w, 400, 1, d_out);
+    run<GrumpkinFqUOther, 0>(GrumpkinFqUOther::CHAIN ? "grumpkin 9x29 fe_mul (chain)" : "grumpkin 9x29 fe_mul (no chain)", w, 2000, 1, d_out);
+    run<GrumpkinFqUOther, 4>(GrumpkinFqUOther::CHAIN ? "grumpkin 9x29 fe_sqr (chain)" : "grumpkin 9x29 fe_sqr (no chain)", w, 2000, 1, d_out);
+    run<GrumpkinFqUOther, 3>(GrumpkinFqUOther::CHAIN ? "grumpkin 9x29 xyzz_madd (chain)" : "grumpkin 9x29 xyzz_madd (no chain)", w, 400, 1, d_out);
     run<Bls12381Fq, 0>("bls12-381 fe_mul (asm)", w, 1000, 1, d_out);
     run<Bls12381Fq, 3>("bls12-381 xyzz_madd", w, 200, 1, d_out);
     run<Bls12381FqU, 0>("bls12-381 14x28 fe_mul", w, 1000, 1, d_out);

@@ -31,6 +31,8 @@ field("VestaFq", 8, 0x40000000000000000000000000000000224698FC0994A8DD8C46EB2100
 field("VestaFr", 8, 0x40000000000000000000000000000000224698FC094CF91B992D30ED00000001)  # = Pallas Fq
 field("Bn254Fq", 8, 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47)
 field("Bn254Fr", 8, 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001)
+field("GrumpkinFq", 8, 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001)  # = BN254 Fr
+field("GrumpkinFr", 8, 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47)  # = BN254 Fq
 
 MAX_TERMS = 11  # terms per asm statement (operand limit 30: 2*terms + acc + c2 + 3 sgpr temps)
 
@@ -83,7 +85,7 @@ def emit_column_stmt(terms, first):
 
 
 def twin_of(name):
-    """an earlier field with the same modulus and limb count (Vesta's fields are Pallas's two): its schedule serves this one"""
+    """an earlier field with the same modulus and limb count (Vesta's fields are Pallas's two, Grumpkin's are BN254's): its schedule serves this one"""
     for other in FIELDS:
         if other == name:
             return None
@@ -183,7 +185,9 @@ def main():
     for name in FIELDS:
         hdr.append(gen_twin(name, twin_of(name)) if twin_of(name) else gen_field(name))
         hdr.append("")
-    for name in ("PallasFr", "Bls12381Fr", "Bn254Fr"):  # the scalar-field vector kernels (vec_kernels.h)
+    # the scalar-field vector kernels (vec_kernels.h).  GrumpkinFr's are generated under its own name: its twin is a base field only,
+    # no curve's scalar field, and gets none
+    for name in ("PallasFr", "Bls12381Fr", "Bn254Fr", "GrumpkinFr"):
         for T in (2, 3):
             hdr.append(gen_field(name, T))
             hdr.append("")

@@ -8,7 +8,7 @@
 // configs 4, 5) get the same treatment here.
 //
 //   profile_as <scheme: trivial_pc_as | ipa_pc_as | hp_as | r1cs_nark_as | all> <log_min> <log_max>
-//              [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] [--curve 0|1|2|4] [--constant] [--uniform] [--no-roundtrip]
+//              [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] [--curve 0|1|2|4|6] [--constant] [--uniform] [--no-roundtrip]
 //              [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--transparent DOMAIN]
 //   --transparent DOMAIN  every committer key is a transparent one over DOMAIN (amsm.h amsm_bases_sample, the setup_transparent of
 //                the headers) instead of the seeded synthetic key; the Python mirrors take the same key from setup(domain=...).
@@ -76,7 +76,7 @@ template <class F>
 static double timed_proves(const Opt& o, F&& prove_once);
 
 // ark_std::test_rng() stand-in: a fixed stream of 254-bit integers, reduced mod r -- the schemes' rng returns CANONICAL scalars
-// (amsm_hp_as.hpp: Rng).  Every 255-bit r exceeds the stream, so nothing is subtracted there; BN254's r lies between 2^253 and 2^254:
+// (amsm_hp_as.hpp: Rng).  Every 255-bit r exceeds the stream, so nothing is subtracted there; BN254's and Grumpkin's r lie between 2^253 and 2^254:
 // one conditional subtraction (the Python mirror takes the same integers mod r).
 struct HarnessRng {
   uint64_t seed, i = 0;
@@ -493,7 +493,7 @@ int main(int argc, char** argv) {
   Opt o;
   if (argc < 4) {
     fprintf(stderr, "usage: %s <scheme|all> <log_min> <log_max> [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] "
-                    "[--curve 0|1|2|4] [--constant] [--uniform] [--no-roundtrip] [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--replicate-below L] [--transparent DOMAIN]\n", argv[0]);
+                    "[--curve 0|1|2|4|6] [--constant] [--uniform] [--no-roundtrip] [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--replicate-below L] [--transparent DOMAIN]\n", argv[0]);
     return 2;
   }
   o.scheme = argv[1];
