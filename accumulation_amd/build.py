@@ -80,5 +80,49 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
     return LIB
 
 
+# The field probe (tests/hip/field_probe.hip): a test-only device unit, NOT part of libamsm.so.  One source, one object per
+# pack (-DPROBE_PACK=<id>) plus the dispatcher, compiled in parallel with the library's flags and linked next to the source.
+PROBE_SRC = os.path.join(ROOT, "tests", "hip", "field_probe.hip")
+PROBE_LIB = os.path.join(ROOT, "tests", "hip", "libfield_probe.so")
+PROBE_OBJ = os.path.join(ROOT, "build", "obj", "probe")
+PROBE_PACKS = [0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19]  # field_probe.hip: PROBE_PACKS
+
+
+def probe_stale() -> bool:
+    return _stale(PROBE_LIB, [PROBE_SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC)])
+
+
+def _compile_probe(pack) -> str:
+    tag = "dispatch" if pack is None else f"pack{pack}"
+    obj = os.path.join(PROBE_OBJ, f"field_probe_{tag}.o")
+    log = obj + ".log"
+    flags = [f for f in FLAGS if not f.startswith("-Rpass")]
+    define = [] if pack is None else [f"-DPROBE_PACK={pack}"]
+    cmd = ["hipcc", *flags, *define, "-I", CSRC, "-c", PROBE_SRC, "-o", obj]
+    with open(log, "w") as lf:
+        rc = subprocess.call(cmd, stdout=lf, stderr=subprocess.STDOUT)
+    if rc != 0:
+        sys.stderr.write(open(log).read()[-6000:])
+        raise RuntimeError(f"hipcc failed on field_probe.hip ({tag}; log: {log})")
+    return obj
+
+
+def build_probe(force: bool = False, verbose: bool = True) -> str:
+    """tests/hip/libfield_probe.so, rebuilt when it is missing or older than its source or anything under csrc/."""
+    if not force and not probe_stale():
+        return PROBE_LIB
+    os.makedirs(PROBE_OBJ, exist_ok=True)
+    if verbose:
+        print(f"[accumulation_amd.build] hipcc --offload-arch={ARCH}: tests/hip/field_probe.hip ({len(PROBE_PACKS)} packs)", flush=True)
+    jobs = min(16, os.cpu_count() or 1)
+    with ThreadPoolExecutor(max_workers=jobs) as ex:
+        objs = list(ex.map(_compile_probe, [None] + PROBE_PACKS))
+    subprocess.check_call(["hipcc", "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", PROBE_LIB, *objs])
+    return PROBE_LIB
+
+
 if __name__ == "__main__":
-    print(build_lib(force="--force" in sys.argv))
+    if "--probe" in sys.argv:
+        print(build_probe(force="--force" in sys.argv))
+    else:
+        print(build_lib(force="--force" in sys.argv))

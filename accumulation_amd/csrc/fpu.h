@@ -237,7 +237,9 @@ AMSM_DEV void u_carry(Fe<P>& a) {
 }
 
 // Montgomery product a*b / 2^(B*L) mod p.  Needs: limbs of a < 2^(B+1), limbs of b < 2^B (or the reverse).
-// Gives: tight, value < p + a*b / 2^(B*L).
+// Gives: limbs 0..L-2 < 2^B, value < p + a*b / 2^(B*L) -- TIGHT only where that bound (with the addend, if any) is <= 2^(B*L): limb
+// widths alone do not give it (a lazy a near 2^(B*L+1) times a tight b near 2^(B*L) lands above 2^(B*L), in a top limb wider than
+// B bits).  Every call site in ec.h has the bound from its `[< k p]` line; u_mul_add_mul and u_sqr are the same.
 // With ADD: returns a*b / 2^(B*L) + add, the addend's limbs (any u32, e.g. the unnormalised K*p - x) going straight
 // into the upper columns of the product, so "product minus value" costs L 64-bit adds instead of a subtraction and
 // a carry pass, and the result is tight.
@@ -294,30 +296,6 @@ AMSM_DEV Fe<P> u_mul_add_mul(const Fe<P>& a, const Fe<P>& b, const Fe<P>& c, con
       if (j >= 0 && j < L) {
         ac += (u64)a.v[i] * b.v[j];
         ac += (u64)c.v[i] * d.v[j];
-      }
-    }
-  });
-  return r;
-}
-
-// sum_{t < K} a[t] b[t] / 2^(B*L) mod p with ONE reduction (K <= 4 products of tight operands).  Per column: 4 * 9 products below
-// 2^58 plus one reduction product below 2^58 per non-zero limb of p -- six for Pallas and Vesta, (36 + 6) * 2^58; nine for BN254 and Grumpkin,
-// (36 + 9) * 2^58 = 45 * 2^58 -- plus a carry below 2^35: under 2^64 = 64 * 2^58 either way.
-// Gives: tight, value < p + sum a[t] b[t] / 2^(B*L).
-template <class P, int K>
-AMSM_DEV Fe<P> u_dot(const Fe<P>* a, const Fe<P>* b) {
-  static_assert(K >= 1 && K <= 4, "column accumulators hold four products");
-  constexpr int L = P::L;
-  u64 acc = 0;
-  u32 m[L];
-  Fe<P> r;
-  u_columns<P, 0>(acc, m, r, nullptr, false, [&](u64& ac, int k) {
-#pragma unroll
-    for (int t = 0; t < K; t++) {
-#pragma unroll
-      for (int i = 0; i < L; i++) {
-        int j = k - i;
-        if (j >= 0 && j < L) ac += (u64)a[t].v[i] * b[t].v[j];
       }
     }
   });

@@ -11,6 +11,12 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "msm
 # Pallas's partner in the Pasta cycle (AMSM_VESTA = 2): the two fields swapped.  The oracle is curve-generic and keeps no Vesta object.
 VESTA = o.Curve("vesta", 2, p=o.PALLAS.r, r=o.PALLAS.p, b=5, gx=o.PALLAS.r - 1, gy=2, limbs=4)
 
+# The BN254 / Grumpkin cycle (AMSM_BN254 = 4, AMSM_GRUMPKIN = 6), for new test code: each curve's base field is the other's scalar field.
+_BN_P = 21888242871839275222246405745257275088696311157297823662689037894645226208583
+_BN_R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+BN254 = o.Curve("bn254_g1", 4, p=_BN_P, r=_BN_R, b=3, gx=1, gy=2, limbs=4)
+GRUMPKIN = o.Curve("grumpkin", 6, p=_BN_R, r=_BN_P, b=_BN_R - 17, gx=1, gy=17631683881184975370165255887551781615748388533673675138860, limbs=4)
+
 
 def load_golden():
     with open(GOLDEN) as f:

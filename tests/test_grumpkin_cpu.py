@@ -73,7 +73,7 @@ def test_modulus_shape_in_radix_2p29():
     carry = 1 << 35
     assert 9 * lazy * tight + 9 * tight * tight + carry < 1 << 63  # one product, one lazy operand
     assert 18 * lazy * tight + 9 * tight * tight + carry + (1 << 32) < 1 << 64  # u_mul_add_mul, an addend riding along
-    assert (4 * 9 + 9) * tight * tight + carry < 1 << 64  # u_dot<4>
+    assert (4 * 9 + 9) * tight * tight + carry < 1 << 64  # four tight products under one reduction (the removed u_dot<4>)
 
 
 def _tables(src, name, limbs, bits):
