@@ -94,6 +94,7 @@ int amsm_ctx_create(amsm_ctx** out, int curve, int device_id, void* stream) {
   if (const char* e = getenv("AMSM_BPL_PLAIN")) c->bpl_plain = atoi(e) != 0;
   if (const char* e = getenv("AMSM_BPL_PROBE")) c->bpl_probe = atoi(e) != 0;
   if (const char* e = getenv("AMSM_BPS")) c->bps = std::max(0, std::min(2, atoi(e)));
+  if (const char* e = getenv("AMSM_BPS_BATCH")) c->bps_batch = std::max(0, std::min((int)msel::BPS_BATCH, atoi(e)));
   if (const char* e = getenv("AMSM_SPLIT_LOG2")) c->split_log2 = std::max(0, std::min(28, atoi(e)));
   if (const char* e = getenv("AMSM_DIRECT_SUM_MAX_LOG2")) c->direct_max_log2 = std::max(0, std::min(16, atoi(e)));
   if (const char* e = getenv("AMSM_TWO_VALUED")) c->two_valued = atoi(e) != 0;
@@ -272,6 +273,13 @@ int amsm_ctx_pipeline_stats_small(const amsm_ctx* c, unsigned long long* n_bucke
   if (!c) return AMSM_E_INVALID_ARG;
   if (n_bucket_split) *n_bucket_split = c->n_bps;
   if (n_fallbacks) *n_fallbacks = c->n_bps_fallbacks;
+  return AMSM_OK;
+}
+int amsm_ctx_batched_split_stats(const amsm_ctx* c, unsigned long long* n_units, unsigned long long* n_msms, unsigned long long* n_unit_reruns) {
+  if (!c) return AMSM_E_INVALID_ARG;
+  if (n_units) *n_units = c->n_bps_units;  // (the host backend has no pipelines: zeros)
+  if (n_msms) *n_msms = c->n_bps_batched;
+  if (n_unit_reruns) *n_unit_reruns = c->n_bps_unit_reruns;
   return AMSM_OK;
 }
 

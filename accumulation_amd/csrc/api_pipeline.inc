@@ -109,6 +109,7 @@ inline msel::Switches switches_of(const amsm_ctx* c) {
   s.split_log2 = c->split_log2;
   s.direct = c->direct_max_log2 > 0;
   s.window_override = c->window_override != 0;
+  s.bps_batch = c->bps_batch;
   return s;
 }
 inline msel::Choice choose_pipeline(const amsm_ctx* ctx, const amsm_bases* bases, size_t n, int group_shift, bool skewed) {
@@ -494,6 +495,7 @@ int msm_enqueue_direct_batch(amsm_ctx* ctx, Slot* sl, const MsmJob* jobs, size_t
   const MsmGeom g = sl->geom;
   const amsm_bases* bases = jobs[0].key;
   sl->job = jobs[0];
+  sl->unit_nv = 0;
   sl->rerun = &msm_rerun_chunked<Fq, Fr>;
   // inside a batch the launches alternate between the two streams every caller has ordered behind the scalars' producers (the
   // caller's and the prep stream: prep_fork, the host-slice uploads): a sum kernel fills one wave per SIMD, two run side by side
@@ -545,6 +547,7 @@ int msm_enqueue(amsm_ctx* ctx, Slot* sl, const MsmJob& job, Place place) {
   if (shared && !(g.bpl == 1u && g.groups == 1u && g.precomp && g.n_sets == 1u)) return AMSM_E_INVALID_ARG;
   u32* d_buckets = shared ? (u32*)ctx->shared_buckets[share.buf].p : (u32*)sl->buckets.p;
   sl->job = job;
+  sl->unit_nv = 0;
   sl->share_overflow = false;
   sl->rerun = &msm_rerun_chunked<Fq, Fr>;
   // alone: the only MSM of a blocking call.  Nothing can overlap, and every hand-over between streams (an event wait on
@@ -578,7 +581,8 @@ int msm_enqueue(amsm_ctx* ctx, Slot* sl, const MsmJob& job, Place place) {
       if (rc != 0) return AMSM_E_HIP;
       stage_mark(ctx, sl, ST_SORT, st);
       stage_mark(ctx, sl, ST_BOUNDS, st);
-      (g.bpl == 2 ? ctx->n_bps : ctx->n_bpl)++;
+      if (g.bpl != 2) ctx->n_bpl++;
+      else if (!job.counted) ctx->n_bps++;  // (a unit's MSM run again on its own was counted with its unit)
     } else if (short_prep) {
       // short prep chain (prep_kernels.h: 5 dispatches + 2 for skewed inputs); the stage marks keep their names: "sort" = scatter + local sort
       PrepBuffers pb;
@@ -721,6 +725,138 @@ int msm_enqueue(amsm_ctx* ctx, Slot* sl, const MsmJob& job, Place place) {
   return AMSM_OK;
 }
 
+// ---- a unit of bucket-split MSMs: one launch per pipeline stage (msm_select.h: batch_units; DESIGN.md 4.2h) ----
+// What ONE bucket-split MSM of geometry g takes of a slot: msm_plan's expressions for vals_a, vals_b, bpl_grp, bpl_order, buckets and
+// prep_small.  batch_units keeps a unit's V of them below msel::BPS_BATCH_MAX_BYTES.
+template <class Fq>
+size_t bps_slot_bytes(const MsmGeom& g) {
+  const u32 P = prep_bps_partitions(g, g.bps_log2_l);
+  return (prep_bps_part_entries(g, g.bps_log2_l) * 4 + 64) + ((size_t)P * prep_bps_stride(g, g.bps_log2_l) * 4 + 64) + ((size_t)P * 16 * 8 + 64) +
+         ((size_t)g.B * 4 + 64) + (size_t)g.B * xyzz_bytes<Fq>() + (64 + prep_small_words(g) * sizeof(u32) + 256);
+}
+// The unit as its tail sees it: nv * n_sets bucket sets in one table, one result ("group") per MSM -- what msm_collect's horner hands out
+inline MsmGeom bps_unit_geom(const MsmGeom& g, u32 nv) {
+  MsmGeom u = g;
+  u.n_sets = g.n_sets * nv;
+  u.groups = nv;
+  u.B = g.B * nv;
+  return u;
+}
+inline msel::TailPlan bps_unit_tail(const MsmGeom& g, u32 nv, Place place) {
+  return msel::tail_plan(g.nb, g.n_sets * nv, g.B * nv, g.E * nv, false, place);
+}
+// Does the bucket-split geometry of n pairs at `off` of `bases` (the key the MSMs run over) take the batched kernels?  One bucket set
+// per MSM, and at most 16 entry slots per scalar (windows of 16 bits and more: what every key long enough for 2^16 pairs has --
+// k_prep_scatter_batch is built for that width only)
+inline bool bps_unit_geom_ok(amsm_ctx* ctx, const amsm_bases* bases, size_t off, size_t n, MsmGeom* g) {
+  return bps_geom(ctx, bases, off, n, -1, g) && g->n_sets == 1u && g->S <= 16u;
+}
+// What msm_multi_xyzz found when it formed the unit (bps_unit_geom_ok, once per run of jobs): ONE MSM's geometry, shared by all of the
+// unit's MSMs (skip_ones set), and the key they run over (a 20-bit key's twin)
+struct BpsUnitGeom {
+  MsmGeom g = {};
+  const amsm_bases* eff = nullptr;
+};
+// EVERY allocation of a unit of nv MSMs of geometry g on slot `sl` (the counterpart of direct_plan): nothing is launched.
+// AMSM_E_OOM: the caller runs the unit's MSMs singly.
+struct BpsBatchPlan {
+  BpsBatchBuffers buf;
+};
+template <class Fq>
+int bps_batch_plan(amsm_ctx* ctx, Slot* sl, const MsmGeom& g, size_t nv, BpsBatchPlan* out) {
+  if (nv < 2 || nv > (size_t)msel::BPS_BATCH || g.bpl != 2u || g.n_sets != 1u || g.S > 16u) return AMSM_E_INVALID_ARG;
+  const size_t rec = xyzz_bytes<Fq>();
+  const u32 P = prep_bps_partitions(g, g.bps_log2_l);
+  BpsBatchBuffers& b = out->buf;
+  // MSM v's share of every buffer: what msm_plan gives a single MSM (the 64 bytes of slack included), v strides in
+  b.small_stride = prep_bps_small_block_words();
+  b.part_stride = (u32)(prep_bps_part_entries(g, g.bps_log2_l) + 16);
+  b.ents_stride = (u32)((size_t)P * prep_bps_stride(g, g.bps_log2_l) + 16);
+  b.grp_stride = P * 16u + 8u;
+  b.order_stride = g.B + 16u;
+  if ((unsigned long long)P * prep_bps_stride(g, g.bps_log2_l) + 16ull >= (1ull << 31)) return AMSM_E_INVALID_ARG;
+  TRY(ensure(sl->vals_a, nv * (size_t)b.part_stride * 4));
+  TRY(ensure(sl->vals_b, nv * (size_t)b.ents_stride * 4));
+  TRY(ensure(sl->bpl_grp, nv * (size_t)b.grp_stride * 8));
+  TRY(ensure(sl->bpl_order, nv * (size_t)b.order_stride * 4));
+  TRY(ensure(sl->buckets, nv * (size_t)g.B * rec));
+  TRY(ensure(sl->prep_small, nv * (size_t)b.small_stride * 4 + 256));
+  TRY(reserve_tail<Fq>(ctx, sl, (size_t)g.n_sets * nv, msel::tail_plan_any_place(g.nb, g.n_sets * (u32)nv, g.B * (u32)nv, g.E * (u32)nv, false)));
+  b.small = (u32*)sl->prep_small.p;
+  b.part = (u32*)sl->vals_a.p;
+  b.ents_t = (u32*)sl->vals_b.p;
+  b.grp = sl->bpl_grp.p;
+  b.order = (u32*)sl->bpl_order.p;
+  return AMSM_OK;
+}
+template <class Fq, class Fr>
+int msm_rerun_unit(amsm_ctx* ctx, Slot* sl, void* out);
+// nv = 2 .. BPS_BATCH bucket-split MSMs that share key, range and scalar form (msm_select.h: batch_units) as FIVE commands: one fill,
+// scatter, local sort and accumulation with grid.y = MSM, one tail over the unit's nv bucket sets -- instead of five per MSM.  The
+// slot then carries nv results; msm_collect hands them out as nv "groups" of one record each, as for a batch of direct sums.
+// One pair of flag words for the unit: a scalar out of range fails the call, an overflowing prep sends ALL nv MSMs through the single
+// path again, one by one (msm_rerun_unit), each with its own chunked fallback.
+template <class Fq, class Fr>
+int msm_enqueue_bps_batch(amsm_ctx* ctx, Slot* sl, const MsmJob* jobs, size_t nv, const BpsUnitGeom& found, Place place) {
+  BpsBatchPlan bp;
+  const amsm_bases* bases = found.eff;
+  if (!bases) return AMSM_E_INVALID_ARG;
+  const MsmGeom g = found.g;
+  TRY(bps_batch_plan<Fq>(ctx, sl, g, nv, &bp));
+  const MsmGeom ug = bps_unit_geom(g, (u32)nv);
+  const msel::TailPlan tp = bps_unit_tail(g, (u32)nv, place);
+  sl->geom = ug;
+  sl->job = jobs[0];
+  sl->share_overflow = false;
+  sl->rerun = &msm_rerun_chunked<Fq, Fr>;
+  sl->rerun_unit = &msm_rerun_unit<Fq, Fr>;
+  for (size_t v = 0; v < nv; v++) sl->unit_jobs[v] = jobs[v];
+  sl->unit_nv = (u32)nv;
+  // LONE: the whole call is this unit (the provers' 2 .. 8 commits): one stream, no hand-overs.  Inside a longer call: the stages on
+  // their streams, as msm_enqueue places them
+  const bool one = place == Place::LONE;
+  hipStream_t st = one ? ctx->stream : ctx->s_prep, sm = ctx->stream;
+  hipStream_t tl = place != Place::BATCH_INNER ? ctx->stream : ctx->s_tail;
+  u32* d_err = bp.buf.small;
+  const u32* sp[msel::BPS_BATCH];
+  for (size_t v = 0; v < nv; v++) sp[v] = (const u32*)jobs[v].scalars;
+  stage_mark(ctx, sl, ST_DIGITS, st);
+  if (launch_prep_bps_batch<Fr>(st, sp, (u32)nv, jobs[0].mont, g, g.bps_log2_l, bp.buf) != 0) return AMSM_E_HIP;
+  stage_mark(ctx, sl, ST_SORT, st);
+  stage_mark(ctx, sl, ST_BOUNDS, st);
+  if (ctx->profiling) (void)hipEventRecord(sl->ev_prep_end, st);
+  AMSM_DBG("unit prep");
+  if (!one) {
+    HIP_TRY(hipEventRecord(sl->prep_done, st));
+    HIP_TRY(hipStreamWaitEvent(sm, sl->prep_done, 0));
+  }
+  stage_mark(ctx, sl, ST_ACCUM_L0, sm);
+  launch_accum_bps_batch<Fq>(sm, (const u32*)bases->d_table, bp.buf, (u32)nv, prep_bps_partitions(g, g.bps_log2_l) * 16u, g.bps_log2_l, g.B,
+                             (u32*)sl->buckets.p);
+  AMSM_DBG("unit accumulate");
+  if (ctx->profiling) (void)hipEventRecord(sl->ev_l0_end, sm);
+  sl->tail = tl;
+  if (tl != sm) {
+    HIP_TRY(hipEventRecord(sl->l0_done, sm));
+    HIP_TRY(hipStreamWaitEvent(tl, sl->l0_done, 0));
+  }
+  if (ctx->profiling) {
+    (void)hipEventRecord(sl->ev[ST_ACCUM_L12], tl);
+    (void)hipEventRecord(sl->ev[ST_REDUCE], tl);
+  }
+  launch_tail<Fq>(tl, tp, (const u32*)sl->buckets.p, ug, (u32*)sl->red2_rc.p, (u32*)sl->red_out.p, (u32*)sl->red_ticket.p, (u32*)sl->fold_out.p,
+                  d_err, (u32*)sl->h_pinned);
+  AMSM_DBG("unit tail");
+  if (ctx->profiling) (void)hipEventRecord(sl->ev[ST_COUNT], tl);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(sl->done, tl));
+  sl->busy = true;
+  ctx->n_bps += nv;  // each MSM once, when it is first put on the pipeline
+  ctx->n_bps_batched += nv;
+  ctx->n_bps_units++;
+  return AMSM_OK;
+}
+
 // Wait for slot `sl`, then host Horner over the window sums (plain key) -> one XYZZ per group on the host
 // (`out` has room for sl->geom.groups results).
 template <class Fq>
@@ -750,6 +886,8 @@ int msm_collect(amsm_ctx* ctx, Slot* sl, host::HXYZZ<Fq>* out) {
       return AMSM_OK;
     }
   } else if (g.bpl && *(u32*)((char*)h + g.n_sets * rec + 4)) {  // the prep's overflow flag: skewed digits (SURVEY.md F8)
+    // a unit shares one flag word: which of its preps overflowed is not known -- every MSM again on its own, each with its own fallback
+    if (sl->unit_nv) return sl->rerun_unit(ctx, sl, out);
     if (g.bpl == 2) ctx->n_bps_fallbacks++;
     else ctx->n_bpl_fallbacks++;
     TRY(sl->rerun(ctx, sl));
@@ -786,6 +924,25 @@ int msm_rerun_chunked(amsm_ctx* ctx, Slot* sl) {
   j.force_chunked = true;
   j.share = Share();
   return msm_enqueue<Fq, Fr>(ctx, sl, j, Place::BATCH_LAST);
+}
+
+// A unit one of whose preps overflowed (msm_collect): its MSMs one after the other through the single path on the same slot, on the
+// per-stage streams like any re-run.  Each was counted when the unit was enqueued (MsmJob::counted); the ones whose own prep
+// overflows again fall back to the chunked pipeline there and are counted as fallbacks, once.  The result does not depend on the path.
+template <class Fq, class Fr>
+int msm_rerun_unit(amsm_ctx* ctx, Slot* sl, void* out) {
+  host::HXYZZ<Fq>* res = (host::HXYZZ<Fq>*)out;
+  const u32 nv = sl->unit_nv;
+  MsmJob jobs[msel::BPS_BATCH];
+  for (u32 v = 0; v < nv; v++) jobs[v] = sl->unit_jobs[v];  // (msm_enqueue rewrites the slot's description)
+  sl->unit_nv = 0;
+  ctx->n_bps_unit_reruns++;
+  for (u32 v = 0; v < nv; v++) {
+    jobs[v].counted = true;
+    TRY((msm_enqueue<Fq, Fr>(ctx, sl, jobs[v], Place::BATCH_LAST)));
+    TRY(msm_collect<Fq>(ctx, sl, &res[v]));
+  }
+  return AMSM_OK;
 }
 
 void stage_begin(amsm_ctx* ctx) {
@@ -1045,12 +1202,78 @@ int msm_multi_xyzz(amsm_ctx* ctx, const std::vector<MsmJob>& jobs, std::vector<h
   std::vector<size_t> live;  // the non-empty jobs; the last one's tail is the only one the caller waits for
   for (size_t j = 0; j < k; j++)
     if (jobs[j].n) live.push_back(j);
-  std::vector<uint8_t> ovf(live.size(), 0);
+  // The ring runs over UNITS (msm_select.h: batch_units): a live job on today's path, or 2 .. BPS_BATCH consecutive bucket-split
+  // MSMs that differ in their scalars only, one launch per pipeline stage (msm_enqueue_bps_batch).  Every caller that ends here
+  // inherits the batching; a call of one job, or with the switch off, never looks at a geometry.
+  std::vector<msel::Unit> units(live.size());
+  size_t n_units = live.size();
+  std::vector<MsmJob> ujobs;  // the live jobs in order (a unit's are adjacent in memory)
+  std::vector<BpsUnitGeom> ugeom;  // per live job: the geometry its unit would run with (found once per run, handed to the plan)
+  if (live.size() >= 2 && ctx->bps_batch >= 2) {
+    std::vector<msel::BatchJob> bj(live.size());
+    ugeom.resize(live.size());
+    const msel::Switches sw = switches_of(ctx);
+    size_t last_eval = live.size();  // the last job whose geometry was looked at (none yet)
+    for (size_t i = 0; i < live.size(); i++) {
+      const MsmJob& j = jobs[live[i]];
+      msel::BatchJob& b = bj[i];
+      b = msel::BatchJob{j.key, key_desc(j.key), j.off, j.n, j.mont, j.group_shift, j.share.buf >= 0, j.force_chunked, j.skip_ones, false, 0};
+      if (j.group_shift >= 0 || j.share.buf >= 0 || j.force_chunked || choose_pipeline(ctx, j.key, j.n, -1, false).pipeline != msel::BUCKET_SPLIT)
+        continue;
+      // one geometry per run -- taken from a neighbour only if that neighbour's geometry was itself looked at (a job skipped above,
+      // a skewed vector for instance, says nothing about the jobs behind it)
+      if (last_eval + 1 == i && msel::batch_same_run(bj[last_eval], b)) {
+        b.geom_ok = bj[last_eval].geom_ok;
+        b.slot_bytes = bj[last_eval].slot_bytes;
+        ugeom[i] = ugeom[last_eval];
+        last_eval = i;
+        continue;
+      }
+      last_eval = i;
+      // bps_geom must take the run's geometry, over the key the MSMs run over (a 20-bit key's twin; one that cannot be had is the
+      // single path's to report)
+      ugeom[i].eff = j.key;
+      if ((!j.key->bpl || bases_alt<Fq>(ctx, j.key, &ugeom[i].eff) == AMSM_OK) && bps_unit_geom_ok(ctx, ugeom[i].eff, j.off, j.n, &ugeom[i].g)) {
+        ugeom[i].g.skip_ones = j.skip_ones ? 1u : 0u;
+        b.geom_ok = true;
+        b.slot_bytes = bps_slot_bytes<Fq>(ugeom[i].g);
+      }
+    }
+    n_units = msel::batch_units(bj.data(), bj.size(), sw, units.data());
+    ujobs.reserve(live.size());
+    for (size_t i : live) ujobs.push_back(jobs[i]);
+  } else {
+    for (size_t i = 0; i < live.size(); i++) units[i] = msel::Unit{i, 1};
+  }
+  std::vector<uint8_t> ovf(n_units, 0), degraded(n_units, 0);
   const int rc = run_ring(
-      ctx, live.size(), [&](size_t i, Slot* sl) { return msm_enqueue<Fq, Fr>(ctx, sl, jobs[live[i]], place_of(i, live.size())); },
-      [&](size_t i, Slot* sl) { return msm_collect<Fq>(ctx, sl, &(*part)[live[i]]); }, ovf.data());
+      ctx, n_units,
+      [&](size_t u, Slot* sl) -> int {
+        const msel::Unit un = units[u];
+        if (un.count == 1) return msm_enqueue<Fq, Fr>(ctx, sl, jobs[live[un.first]], place_of(u, n_units));
+        int r = msm_enqueue_bps_batch<Fq, Fr>(ctx, sl, &ujobs[un.first], un.count, ugeom[un.first], place_of(u, n_units));
+        if (r != AMSM_E_OOM) return r;
+        // the unit's buffers could not be had (nothing was launched): its MSMs singly on this slot, the last one left to the ring
+        (void)hipGetLastError();
+        degraded[u] = 1;
+        for (size_t v = 0; v < un.count; v++) {
+          TRY((msm_enqueue<Fq, Fr>(ctx, sl, ujobs[un.first + v], Place::BATCH_LAST)));
+          if (v + 1 < un.count) TRY(msm_collect<Fq>(ctx, sl, &(*part)[live[un.first + v]]));
+        }
+        return AMSM_OK;
+      },
+      [&](size_t u, Slot* sl) -> int {
+        const msel::Unit un = units[u];
+        if (un.count == 1 || degraded[u]) return msm_collect<Fq>(ctx, sl, &(*part)[live[un.first + un.count - 1]]);
+        host::HXYZZ<Fq> res[msel::BPS_BATCH];
+        TRY(msm_collect<Fq>(ctx, sl, res));
+        for (size_t v = 0; v < un.count; v++) (*part)[live[un.first + v]] = res[v];
+        return AMSM_OK;
+      },
+      ovf.data());
   if (overflow)
-    for (size_t i = 0; i < live.size(); i++) (*overflow)[live[i]] = ovf[i];
+    for (size_t u = 0; u < n_units; u++)
+      if (units[u].count == 1) (*overflow)[live[units[u].first]] = ovf[u];
   return rc;
 }
 

@@ -45,6 +45,7 @@ struct MsmJob {
   int group_shift = -1;            // >= 0: two sums by that bit of the index (the IPA rounds)
   bool force_chunked = false;      // skew probe verdict, or a prep that overflowed: no bucket-per-lane / bucket-split attempt
   bool skip_ones = false;          // the vector's unit scalars are summed apart (msm_multi_split_xyzz): MsmGeom::skip_ones
+  bool counted = false;            // already counted in amsm_ctx::n_bps (a unit's MSM run again on its own: msm_rerun_unit)
   Share share;                     // buf >= 0: one range of a shared bucket set
 };
 
@@ -71,6 +72,11 @@ struct Slot {  // buffers and events of one MSM in flight (the streams belong to
   // or bucket-split MSM whose prep reports a skewed input is re-run from here through the chunked pipeline (msm_collect)
   MsmJob job;
   int (*rerun)(amsm_ctx*, Slot*) = nullptr;
+  // a unit of bucket-split MSMs in one launch per stage (msm_enqueue_bps_batch): its unit_nv >= 2 jobs (0: the slot carries one MSM), and
+  // how msm_collect runs them again one by one when a prep of the unit overflowed (out: unit_nv results, host::HXYZZ<Fq>*)
+  MsmJob unit_jobs[msel::BPS_BATCH];
+  u32 unit_nv = 0;
+  int (*rerun_unit)(amsm_ctx*, Slot*, void* out) = nullptr;
   void* h_pinned = nullptr;
   size_t h_pinned_bytes = 0;
   MsmGeom geom = {};
@@ -201,6 +207,10 @@ struct amsm_ctx {
   int bps = 2;            // AMSM_BPS: bucket-split pipeline 0 never, 1 grouped MSMs only, 2 every candidate of 2^16 .. 2^17 pairs
   int split_log2 = 21;    // AMSM_SPLIT_LOG2: MSMs of 2^22 pairs and more over a key without a 20-bit table run as ranges of 2^this (0: whole)
   unsigned long long n_bps = 0, n_bps_fallbacks = 0;
+  // AMSM_BPS_BATCH=<0..8>: bucket-split MSMs of one call that share key, range and scalar form run as units of up to this many, one
+  // launch per pipeline stage (msm_select.h: batch_units); 0 or 1: every MSM a chain of its own
+  int bps_batch = msel::BPS_BATCH;
+  unsigned long long n_bps_units = 0, n_bps_batched = 0, n_bps_unit_reruns = 0;  // units enqueued / their MSMs / units run again singly
   unsigned long long n_direct = 0;  // MSMs summed straight from a small key's 512-points-per-generator table (k_direct_sum)
   int direct_max_log2 = 15;         // keys of up to 2^this generators carry that table (AMSM_DIRECT_SUM_MAX_LOG2; 0: none)
   unsigned direct_rr = 0;           // which stream the next direct sum of a batch takes

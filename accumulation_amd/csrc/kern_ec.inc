@@ -59,6 +59,13 @@ void launch_accum_bps<AMSM_FQ>(hipStream_t st, const u32* table, const u32* ents
                      (const BplGroupHdr*)grp, order, n_groups, log2_l, flags, buckets);
 }
 template <>
+void launch_accum_bps_batch<AMSM_FQ>(hipStream_t st, const u32* table, const BpsBatchBuffers& b, u32 nv, u32 n_groups, u32 log2_l,
+                                     u32 n_buckets, u32* buckets) {
+  hipLaunchKernelGGL((k_accum_bps_batch<FQD>), dim3(cdiv_(n_groups, 4), nv), dim3(256), 0, st, table, (const u32*)b.ents_t, b.ents_stride,
+                     (const BplGroupHdr*)b.grp, b.grp_stride, (const u32*)b.order, b.order_stride, n_groups, log2_l, (const u32*)b.small,
+                     buckets, n_buckets);
+}
+template <>
 int accum_l0_blocks_per_cu<AMSM_FQ>() {
   int n = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_accum_l0<FQD>, 256, 0) != hipSuccess) {

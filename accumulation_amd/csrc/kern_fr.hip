@@ -220,6 +220,9 @@ int prep_bps_choose(const MsmGeom& g) {
   }
   return -1;
 }
+// what launch_prep_bps zeroes of one MSM: the 16 flag words, the partition totals / starts / cursors, the heavy count
+constexpr size_t PREP_BPS_ZERO_BYTES = (((16 + 4 * (PREP_MAX_P + 1) + 1) * sizeof(u32)) + 255) & ~(size_t)255;
+u32 prep_bps_small_block_words() { return (u32)(PREP_BPS_ZERO_BYTES / sizeof(u32)); }
 static std::atomic<unsigned long long> prep_bps_attr_devices{0};
 static void prep_bps_attr() {
   int dev = 0;
@@ -228,6 +231,7 @@ static void prep_bps_attr() {
   if (dev != 63 && (prep_bps_attr_devices.load(std::memory_order_acquire) & bit)) return;
   static_assert(BPS_LOCAL_BUDGET_WORDS * sizeof(u32) <= 152 * 1024, "k_prep_local_s's LDS must fit its attribute");
   (void)hipFuncSetAttribute((const void*)k_prep_local_s, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+  (void)hipFuncSetAttribute((const void*)k_prep_local_s_batch, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
   prep_bps_attr_devices.fetch_or(bit, std::memory_order_release);
 }
 
@@ -352,6 +356,37 @@ void launch_tv_probe(hipStream_t st, const u32* scalars, u32 n, u32* out16, cons
     hipLaunchKernelGGL(k_prep_local_s, dim3(pg.P), dim3(1024), prep_bps_local_lds(pg), st,                           \
                        pg.FIX ? part_cursor : part_start, b.part, g, pg,                                             \
                        prep_bps_stride(g, log2_l), log2_l, b.ents_t, (BplGroup*)b.grp, b.order, b.err);              \
+    return 0;                                                                                                        \
+  }                                                                                                                  \
+  template <>                                                                                                        \
+  int launch_prep_bps_batch<FR>(hipStream_t st, const u32* const* scalars, u32 nv, int mont, MsmGeom g, u32 log2_l,   \
+                                const BpsBatchBuffers& b) {                                                          \
+    PrepGeom pg = prep_bps_geom(g, log2_l);                                                                          \
+    const u32 stride = prep_bps_stride(g, log2_l);                                                                   \
+    /* every MSM's share of the buffers holds what launch_prep_bps would write of it */                              \
+    /* (16 entry slots per scalar: every key long enough for a bucket-split MSM has windows of 16 bits or more; the */ \
+    /* 32-slot scatter with the record of pointers would spill to scratch and is not built: bps_batch_plan asks)   */ \
+    if (nv < 1u || nv > (u32)PREP_BPS_BATCH || !pg.FIX || g.S > 16u || b.small_stride < prep_bps_small_block_words() || \
+        (b.small_stride & 63u) || b.part_stride < prep_bps_part_entries(g, log2_l) ||                                \
+        (unsigned long long)b.ents_stride < (unsigned long long)pg.P * stride || b.grp_stride < pg.P * BPS_GROUPS ||  \
+        b.order_stride < g.B)                                                                                        \
+      return -1;                                                                                                     \
+    BpsBatchScalars sc;                                                                                              \
+    for (u32 v = 0; v < (u32)PREP_BPS_BATCH; v++) sc.scalars[v] = scalars[v < nv ? v : 0u];                          \
+    u32* part_start0 = b.small + 16 + (PREP_MAX_P + 1);                                                              \
+    u32* part_cursor0 = b.small + 16 + 2 * (PREP_MAX_P + 1);                                                         \
+    /* ONE fill: all nv blocks of flag words and small arrays */                                                     \
+    if (hipMemsetAsync(b.small, 0, (size_t)nv * b.small_stride * sizeof(u32), st) != hipSuccess) return -1;          \
+    prep_bps_attr();                                                                                                 \
+    const size_t lds_scatter = prep_scatter_lds(g, pg);                                                              \
+    if (lds_scatter > 64 * 1024)                                                                                     \
+      (void)hipFuncSetAttribute((const void*)k_prep_scatter_batch<FR, 16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                (int)PREP_LDS_LIMIT);                                                                \
+    hipLaunchKernelGGL((k_prep_scatter_batch<FR, 16, 1>), dim3(cdiv_(g.n, pg.SPB), nv), dim3(512), lds_scatter, st, sc, mont, g,   \
+                       pg, part_start0, part_cursor0, b.small_stride, b.part, b.part_stride, b.small);               \
+    hipLaunchKernelGGL(k_prep_local_s_batch, dim3(pg.P, nv), dim3(1024), prep_bps_local_lds(pg), st, part_cursor0,   \
+                       b.small_stride, b.part, b.part_stride, g, pg, stride, log2_l, b.ents_t, b.ents_stride,        \
+                       (BplGroup*)b.grp, b.grp_stride, b.order, b.order_stride, b.small);                            \
     return 0;                                                                                                        \
   }                                                                                                                  \
   template <>                                                                                                        \

@@ -164,6 +164,28 @@ int launch_prep_bps(hipStream_t st, const u32* scalars, int mont, MsmGeom g, u32
 template <class Fq>
 void launch_accum_bps(hipStream_t st, const u32* table, const u32* ents_t, const void* grp, const u32* order, u32 n_groups,
                       u32 log2_l, const u32* flags, u32* buckets);
+// A unit of nv <= msel::BPS_BATCH bucket-split MSMs that share one geometry (msm_select.h: batch_units), one launch per stage with
+// grid.y = MSM.  MSM v's buffers sit v strides behind MSM 0's; the strides are at least what one MSM needs (PrepBplBuffers).
+struct BpsBatchBuffers {
+  u32* small;        // nv blocks of small_stride words: 16 flag words (block 0's are the unit's: err) and the MSM's small arrays
+  u32 small_stride;  // >= prep_bps_small_block_words(), a multiple of 64 (ONE fill clears all nv blocks)
+  u32* part;         // interchange entries
+  u32 part_stride;   // words
+  u32* ents_t;       // entry blocks
+  u32 ents_stride;   // words
+  void* grp;         // group headers
+  u32 grp_stride;    // headers (8 bytes each)
+  u32* order;        // bucket order
+  u32 order_stride;  // words
+};
+u32 prep_bps_small_block_words();  // the words of a block that must start at zero, rounded up to a whole number of 256-byte lines
+// the fill, the scatter and the local sort of the whole unit: three commands
+template <class Fr>
+int launch_prep_bps_batch(hipStream_t st, const u32* const* scalars, u32 nv, int mont, MsmGeom g, u32 log2_l, const BpsBatchBuffers& b);
+// buckets: MSM v's g.B records at v * g.B (one contiguous table of nv * g.n_sets sets for the unit's one tail)
+template <class Fq>
+void launch_accum_bps_batch(hipStream_t st, const u32* table, const BpsBatchBuffers& b, u32 nv, u32 n_groups, u32 log2_l, u32 n_buckets,
+                            u32* buckets);
 template <class Fr>
 int launch_prep(hipStream_t st, const u32* scalars, int mont, MsmGeom g, const PrepBuffers& b);
 

@@ -262,10 +262,11 @@ __global__ void __launch_bounds__(256)
 
 // accumulate, bucket-split (k_prep_local_s): lane l of group gw sums part (l mod L) of the bucket at position (64 gw + l) / L; after the
 // rows, log2 L exchanges add the parts and the first lane of every bucket stores it.  Same loop as k_accum_bpl.
+// (the body takes its pointers as arguments: k_accum_bps hands on its own, k_accum_bps_batch those of MSM blockIdx.y; no
+// __restrict__ on them -- the kernels' parameters carry it: prep_kernels.h, prep_scatter_body)
 template <class Fq>
-__global__ void __launch_bounds__(256)
-    k_accum_bps(const u32* __restrict__ table, const u32* __restrict__ ents_t, const BplGroupHdr* __restrict__ grp,
-                const u32* __restrict__ order, u32 n_groups, u32 log2_l, const u32* __restrict__ flags, u32* __restrict__ buckets) {
+AMSM_DEV void accum_bps_body(const u32* table, const u32* ents_t, const BplGroupHdr* grp, const u32* order, u32 n_groups, u32 log2_l,
+                             const u32* flags, u32* buckets) {
   __shared__ __attribute__((aligned(16))) u32 lds[2 * 4 * GatherLds<Fq>::WAVE_BYTES / 4];
   if (flags[1]) return;  // the prep overflowed: the host reruns this MSM through the chunked pipeline
   const u32 lane = threadIdx.x & 63u;
@@ -319,6 +320,24 @@ __global__ void __launch_bounds__(256)
   }
   // (position in the partition's size order -> bucket: k_prep_local_s)
   if ((lane & ((1u << log2_l) - 1u)) == 0u) xyzz_store<Fq>(buckets, (size_t)order[(gw * 64u + lane) >> log2_l], acc);
+}
+template <class Fq>
+__global__ void __launch_bounds__(256)
+    k_accum_bps(const u32* __restrict__ table, const u32* __restrict__ ents_t, const BplGroupHdr* __restrict__ grp,
+                const u32* __restrict__ order, u32 n_groups, u32 log2_l, const u32* __restrict__ flags, u32* __restrict__ buckets) {
+  accum_bps_body<Fq>(table, ents_t, grp, order, n_groups, log2_l, flags, buckets);
+}
+// MSM blockIdx.y of a unit of bucket-split MSMs over one key (prep_kernels.h: k_prep_local_s_batch wrote the layout): its entry
+// blocks, group headers, bucket order and bucket table sit v strides behind MSM 0's; flags: the unit's words -- one overflowing prep
+// stops every MSM of the unit, the host runs them again one by one.
+template <class Fq>
+__global__ void __launch_bounds__(256)
+    k_accum_bps_batch(const u32* __restrict__ table, const u32* __restrict__ ents0, u32 ents_stride, const BplGroupHdr* __restrict__ grp0,
+                      u32 grp_stride, const u32* __restrict__ order0, u32 order_stride, u32 n_groups, u32 log2_l,
+                      const u32* __restrict__ flags, u32* __restrict__ buckets0, u32 bucket_stride) {
+  const size_t v = blockIdx.y;  // wave-uniform: the derived pointers stay in scalar registers, like the single kernel's arguments
+  accum_bps_body<Fq>(table, ents0 + v * ents_stride, grp0 + v * grp_stride, order0 + v * order_stride, n_groups, log2_l, flags,
+                     buckets0 + v * bucket_stride * (size_t)(4 * Fq::W));
 }
 
 // Butterfly reduction of one XYZZ per lane over aligned groups of WIDTH lanes (WIDTH = 64: whole wave) with

@@ -87,6 +87,7 @@ struct Switches {              // the context's documented switches (include/ams
   int split_log2 = 21;         // AMSM_SPLIT_LOG2: range of an MSM over a key WITHOUT a 20-bit table (0: never cut)
   bool direct = true;          // AMSM_DIRECT_SUM_MAX_LOG2=0: no direct sums
   bool window_override = false;  // amsm_ctx_set_window: everything chunked with that width
+  int bps_batch = 8;           // AMSM_BPS_BATCH: bucket-split MSMs per launch (batch_units below); 0 or 1: every MSM a chain of its own
 };
 struct Row {
   KeyKind kind;
@@ -163,6 +164,63 @@ inline bool wants_skew_probe(const KeyDesc& k, size_t n, const Switches& sw) {
   const size_t r = range_of(k, n, sw);
   const Choice ch = choose(k, r ? r : n, false, false, false, sw);
   return ch.pipeline == BUCKET_PER_LANE || ch.pipeline == BUCKET_SPLIT;
+}
+
+// ---- the jobs of one call: which bucket-split MSMs run as ONE launch per pipeline stage ---------------------------------------------
+// One bucket-split MSM of 2^16 pairs fills about a sixth of the chip and is a chain of five commands; the provers issue 2 .. 11 such
+// commitments per round over one key.  batch_units cuts the live job list of a call into UNITS: one job (today's path), or a run
+// of 2 .. BPS_BATCH consecutive jobs that share everything but their scalars -- key, range, scalar form, unit-scalar handling -- and
+// so one MsmGeom; the unit runs as memset, scatter, local sort, accumulate (grid.y = MSM) and one tail over all its bucket sets
+// (api_pipeline.inc: msm_enqueue_bps_batch).  6 to 8 MSMs of 2^16 pairs fill the chip: BPS_BATCH = 8.
+constexpr int BPS_BATCH = 8;
+// what a unit may take of a slot (entry buffers, group headers, bucket order, buckets, small arrays of all its MSMs).  A stated
+// cap, not a measurement: three slots then stay below 1.5 GiB
+constexpr size_t BPS_BATCH_MAX_BYTES = (size_t)512 << 20;
+struct BatchJob {
+  const void* key;     // identity of the key the job names
+  KeyDesc desc;        // ... and how it looks to `choose`
+  size_t off, n;
+  int mont;
+  int group_shift;     // >= 0: grouped (never joins a unit)
+  bool shared;         // one range of a shared bucket set (never joins a unit)
+  bool force_chunked;
+  bool skip_ones;
+  bool geom_ok;        // the bucket-split geometry exists for it (api_pipeline.inc: bps_geom)
+  size_t slot_bytes;   // what ONE such MSM takes of a slot
+};
+struct Unit {
+  size_t first, count;  // jobs [first, first + count)
+};
+// may job j stand in a unit at all?
+inline bool batch_candidate(const BatchJob& j, const Switches& sw) {
+  if (sw.bps_batch < 2 || j.n == 0 || j.group_shift >= 0 || j.shared || j.force_chunked || !j.geom_ok) return false;
+  return choose(j.desc, j.n, false, false, false, sw).pipeline == BUCKET_SPLIT;
+}
+inline bool batch_same_run(const BatchJob& a, const BatchJob& b) {
+  return a.key == b.key && a.off == b.off && a.n == b.n && a.mont == b.mont && a.skip_ones == b.skip_ones;
+}
+// units[0 .. return) cover jobs [0, k) in order (room for k units); a run longer than the cap is cut into full units, a remainder of one
+// is a single
+inline size_t batch_units(const BatchJob* jobs, size_t k, const Switches& sw, Unit* units) {
+  size_t n_units = 0;
+  for (size_t i = 0; i < k;) {
+    size_t run = 1;
+    if (batch_candidate(jobs[i], sw))
+      while (i + run < k && batch_candidate(jobs[i + run], sw) && batch_same_run(jobs[i], jobs[i + run])) run++;
+    size_t cap = (size_t)(sw.bps_batch < BPS_BATCH ? sw.bps_batch : BPS_BATCH);
+    if (run > 1 && jobs[i].slot_bytes) {
+      const size_t fit = BPS_BATCH_MAX_BYTES / jobs[i].slot_bytes;
+      if (fit < cap) cap = fit;
+    }
+    if (cap < 1) cap = 1;
+    for (size_t done = 0; done < run;) {
+      const size_t v = run - done < cap ? run - done : cap;
+      units[n_units++] = Unit{i + done, v};
+      done += v;
+    }
+    i += run;
+  }
+  return n_units;
 }
 
 // ---- the vectors of one call: which skip the windowed pipelines, which run them without their unit scalars -------------------------

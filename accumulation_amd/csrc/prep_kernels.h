@@ -23,6 +23,7 @@
 // workgroup would loop over it; k_prep_heavy_count / k_prep_heavy_place split such partitions over 64 workgroups.
 #pragma once
 #include "fp.h"
+#include "msm_select.h"  // BPS_BATCH
 #include "msm_types.h"
 #include "vec_kernels.h"  // digit_step
 
@@ -201,10 +202,13 @@ __global__ void __launch_bounds__(1024)
 // the 64-byte runs back, 110 us and a slower batch.  512 partitions x 512 scalars it is.)
 // WIDE (the bucket-per-lane pipeline, 20-bit windows): 64-bit interchange entries -- low word = negate | table index, high word
 // = the bucket id's low bits -- because 1 + 10 + 24 bits do not fit one word; `part` then holds E 8-byte entries (P even).
-template <class Fr, int MAXW, int SPT, bool WIDE = false>
-__global__ void __launch_bounds__(512)
-    k_prep_scatter(const u32* __restrict__ scalars, int mont, MsmGeom g, PrepGeom pg, const u32* __restrict__ part_start,
-                   u32* __restrict__ part_cursor, u32* __restrict__ part, u32* __restrict__ err = nullptr) {
+// The body takes its pointers as arguments: k_prep_scatter hands on its own, k_prep_scatter_batch those of MSM blockIdx.y.
+// (No __restrict__ here: the kernels' parameters carry it.  Either way the existing instantiations keep their register, LDS and
+// scratch figures but not their exact instruction order: the compiler allocates and schedules an inlined callee a little
+// differently -- DESIGN.md 4.2h has the resource tables and the A/B that guards the 2^20 headline.)
+template <class Fr, int MAXW, int SPT, bool WIDE>
+AMSM_DEV void prep_scatter_body(const u32* scalars, int mont, MsmGeom g, PrepGeom pg, const u32* part_start, u32* part_cursor, u32* part,
+                                u32* err) {
   extern __shared__ u32 prep_lds[];
   const u32 cap = pg.SPB * g.S;  // staged entries (upper bound)
   u32* cnt = prep_lds;           // entries per partition (rank counters in step 1)
@@ -309,6 +313,28 @@ __global__ void __launch_bounds__(512)
     if (WIDE) reinterpret_cast<u64*>(part)[dst] = reinterpret_cast<const u64*>(staged)[j];
     else part[dst] = staged[j];
   }
+}
+template <class Fr, int MAXW, int SPT, bool WIDE = false>
+__global__ void __launch_bounds__(512)
+    k_prep_scatter(const u32* __restrict__ scalars, int mont, MsmGeom g, PrepGeom pg, const u32* __restrict__ part_start,
+                   u32* __restrict__ part_cursor, u32* __restrict__ part, u32* __restrict__ err = nullptr) {
+  prep_scatter_body<Fr, MAXW, SPT, WIDE>(scalars, mont, g, pg, part_start, part_cursor, part, err);
+}
+// A unit of up to BPS_BATCH bucket-split MSMs that share one geometry (msm_select.h: batch_units) in one launch, grid.y = MSM: MSM v's
+// scalars come from the by-value record, its block of small arrays, interchange entries, entry blocks, group headers and bucket
+// order sit v strides into the slot's buffers (launch.h: BpsBatchBuffers).  The flag words are the unit's: block 0's.
+constexpr int PREP_BPS_BATCH = msel::BPS_BATCH;
+struct BpsBatchScalars {
+  const u32* scalars[PREP_BPS_BATCH];
+};
+template <class Fr, int MAXW, int SPT>
+__global__ void __launch_bounds__(512)
+    k_prep_scatter_batch(BpsBatchScalars b, int mont, MsmGeom g, PrepGeom pg, const u32* __restrict__ part_start0,
+                         u32* __restrict__ part_cursor0, u32 small_stride, u32* __restrict__ part0, u32 part_stride,
+                         u32* __restrict__ err) {
+  const size_t v = blockIdx.y;  // (wave-uniform as it comes: the pointers below are scalar registers like the single kernel's arguments)
+  prep_scatter_body<Fr, MAXW, SPT, false>(b.scalars[v], mont, g, pg, part_start0 + v * small_stride, part_cursor0 + v * small_stride,
+                                          part0 + v * part_stride, err);
 }
 
 // One workgroup (1024 lanes: a partition is ~32 k entries and there are only ~512 of them) per partition: counting
@@ -728,10 +754,10 @@ constexpr u32 BPS_LANES = 1024, BPS_GROUPS = BPS_LANES / BPL_GROUP;  // lane slo
 // uniform 2^16-pair MSM spread over 8 +- 2 entries per part -- 12.4 rows for 8.3 of work; sorted, a group's parts differ by
 // one.  `order[p * NBP + pos]` = the bucket at position pos (k_accum_bps stores there).
 // dynamic LDS: (4 * NBP + 1024 + BPL_BINS + 2 * 16 + 2 + CAP) words.
-__global__ void __launch_bounds__(1024)
-    k_prep_local_s(const u32* __restrict__ part_start, const u32* __restrict__ part, MsmGeom g, PrepGeom pg, u32 stride,
-                   u32 log2_l, u32* __restrict__ ents_t, BplGroup* __restrict__ grp, u32* __restrict__ order,
-                   u32* __restrict__ err) {
+// (the body takes its pointers as arguments: k_prep_local_s hands on its own, k_prep_local_s_batch those of MSM blockIdx.y; no
+// __restrict__ on them, see prep_scatter_body)
+AMSM_DEV void prep_local_s_body(const u32* part_start, const u32* part, MsmGeom g, PrepGeom pg, u32 stride, u32 log2_l, u32* ents_t,
+                                BplGroup* grp, u32* order, u32* err) {
   extern __shared__ u32 prep_lds[];
   const u32 NBP = 1u << pg.SH, L = 1u << log2_l, NG = BPS_GROUPS;
   u32* cnt = prep_lds;        // entries per bucket
@@ -828,6 +854,23 @@ __global__ void __launch_bounds__(1024)
     const u32 i = (k << log2_l) + r;  // entry i of bucket kb belongs to part i mod L
     ents_t[(size_t)p * stride + j] = i < cnt[kb] ? stage[beg[kb] + i] : BPL_ENTRY_PAD;
   }
+}
+__global__ void __launch_bounds__(1024)
+    k_prep_local_s(const u32* __restrict__ part_start, const u32* __restrict__ part, MsmGeom g, PrepGeom pg, u32 stride,
+                   u32 log2_l, u32* __restrict__ ents_t, BplGroup* __restrict__ grp, u32* __restrict__ order,
+                   u32* __restrict__ err) {
+  prep_local_s_body(part_start, part, g, pg, stride, log2_l, ents_t, grp, order, err);
+}
+// MSM blockIdx.y of a unit (k_prep_scatter_batch): its cursors, interchange entries, entry blocks, group headers and bucket order
+// sit v strides behind MSM 0's; bucket ids and entry offsets stay relative to the MSM's own buffers.  err: the unit's flag words.
+__global__ void __launch_bounds__(1024)
+    k_prep_local_s_batch(const u32* __restrict__ part_cursor0, u32 small_stride, const u32* __restrict__ part0, u32 part_stride,
+                         MsmGeom g, PrepGeom pg, u32 stride, u32 log2_l, u32* __restrict__ ents0, u32 ents_stride,
+                         BplGroup* __restrict__ grp0, u32 grp_stride, u32* __restrict__ order0, u32 order_stride,
+                         u32* __restrict__ err) {
+  const size_t v = blockIdx.y;
+  prep_local_s_body(part_cursor0 + v * small_stride, part0 + v * part_stride, g, pg, stride, log2_l, ents0 + v * ents_stride,
+                    grp0 + v * grp_stride, order0 + v * order_stride, err);
 }
 
 }  // namespace amsm

@@ -116,7 +116,11 @@ class Context:
         ffi.check(self._lib.amsm_ctx_pipeline_stats(self._h, C.byref(a), C.byref(b)), "amsm_ctx_pipeline_stats")
         c, d = C.c_ulonglong(), C.c_ulonglong()
         ffi.check(self._lib.amsm_ctx_pipeline_stats_small(self._h, C.byref(c), C.byref(d)), "amsm_ctx_pipeline_stats_small")
+        # bucket-split MSMs that ran as units, one launch per pipeline stage: units / the MSMs in them / units run again one by one
+        u, m, r = C.c_ulonglong(), C.c_ulonglong(), C.c_ulonglong()
+        ffi.check(self._lib.amsm_ctx_batched_split_stats(self._h, C.byref(u), C.byref(m), C.byref(r)), "amsm_ctx_batched_split_stats")
         return {"bucket_per_lane": a.value, "fallbacks": b.value, "bucket_split": c.value, "bucket_split_fallbacks": d.value,
+                "bucket_split_units": u.value, "bucket_split_batched": m.value, "bucket_split_unit_reruns": r.value,
                 "direct_sum": int(self._lib.amsm_ctx_direct_sum_msms(self._h)),
                 "shared_bucket_sets": int(self._lib.amsm_ctx_shared_bucket_msms(self._h)),
                 "unit_scalar_sums": int(self._lib.amsm_ctx_unit_scalar_msms(self._h))}

@@ -62,6 +62,7 @@ SIGNATURES = {
     "amsm_ctx_shared_bucket_msms": (C.c_ulonglong, [_vp]),
     "amsm_ctx_pipeline_stats": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "amsm_ctx_pipeline_stats_small": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "amsm_ctx_batched_split_stats": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "amsm_ctx_destroy": (None, [_vp]),
     "amsm_ctx_curve": (C.c_int, [_vp]),
     "amsm_ctx_fq_limbs": (C.c_int, [_vp]),

@@ -181,6 +181,15 @@ int amsm_ctx_pipeline_stats(const amsm_ctx* ctx, unsigned long long* n_bucket_pe
  * 2 .. 64 adjacent lanes, no partial records): enqueued / re-run through the chunked pipeline over the same key because the
  * scalars were skewed. */
 int amsm_ctx_pipeline_stats_small(const amsm_ctx* ctx, unsigned long long* n_bucket_split, unsigned long long* n_fallbacks);
+/* Bucket-split MSMs that ran as UNITS: the MSMs of one call (amsm_msm_batch_device, amsm_msm_multi_device, amsm_pedersen_commit_batch,
+ * the staged host-slice batches, the per-device job lists of a multi-device context) that share key, range and scalar form and
+ * differ in their scalars only run 2 .. 8 at a time as ONE launch per pipeline stage (five commands per unit instead of five per
+ * MSM; AMSM_BPS_BATCH=<0..8> caps the unit, 0 or 1 turns it off).  *n_units = units enqueued, *n_msms = the MSMs in them (each is
+ * also counted once by amsm_ctx_pipeline_stats_small), *n_unit_reruns = units one of whose vectors turned out skewed and whose
+ * MSMs were therefore run again one by one, each with its own chunked fallback.  Results do not depend on the path.  Any pointer
+ * may be NULL; a host-backend context reports zeros. */
+int amsm_ctx_batched_split_stats(const amsm_ctx* ctx, unsigned long long* n_units, unsigned long long* n_msms,
+                                 unsigned long long* n_unit_reruns);
 void amsm_ctx_destroy(amsm_ctx* ctx);
 int amsm_ctx_curve(const amsm_ctx* ctx);
 /* limbs (u64) of a base-field element: 4 (Pallas, Vesta, BN254, Grumpkin) or 6 (BLS12-381). */
@@ -219,7 +228,11 @@ int amsm_ctx_set_table_budget(amsm_ctx* ctx, size_t bytes_per_table);
 unsigned long long amsm_ctx_tables_denied(const amsm_ctx* ctx);
 
 /* Per-stage device timings of the LAST msm call (hipEvent pairs on the context's stream).
- * Enable with on != 0; stage names: amsm_stage_name(i), i in [0, amsm_stage_count()). */
+ * Enable with on != 0; stage names: amsm_stage_name(i), i in [0, amsm_stage_count()).  The times are means over the call's
+ * samples: one per MSM, and ONE per unit of bucket-split MSMs that ran as one launch per stage (amsm_ctx_batched_split_stats):
+ * the unit records its stage events once, whatever the number of MSMs in it.  A re-run adds samples of its own: an MSM that fell
+ * back to the chunked pipeline counts twice (the aborted attempt and the re-run), a unit that was run again singly counts once
+ * for the aborted unit and once per MSM run again. */
 int amsm_ctx_set_profiling(amsm_ctx* ctx, int on);
 int amsm_stage_count(void);
 const char* amsm_stage_name(int stage);

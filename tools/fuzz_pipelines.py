@@ -192,7 +192,8 @@ while time.time() < t_end:
     else:  # ---- small MSMs: bucket-split pipeline (grouped by default, everything with AMSM_BPS=2)
         bps = int(rs.choice([1, 2]))
         probe = int(rs.rand() < 0.5)
-        ctx = ctx_with(c.curve_id, AMSM_BPS=bps, AMSM_BPL_PROBE=probe)
+        cap = int(rs.choice([0, 2, 3, 8]))  # units of bucket-split MSMs, one launch per stage (AMSM_BPS_BATCH; 0: off)
+        ctx = ctx_with(c.curve_id, AMSM_BPS=bps, AMSM_BPL_PROBE=probe, AMSM_BPS_BATCH=cap)
         kn = int(rs.choice([1 << 16, 1 << 17, (1 << 16) + 777, 100000]))
         ck = CommitterKey.generate(ctx, int(rs.randint(1 << 30)), kn)
         xy, _ = ck.read()
@@ -201,7 +202,17 @@ while time.time() < t_end:
             n = min(n, kn)
             off = int(rs.randint(0, kn - n + 1))
             sc, kind = scalars(c, n)
-            if rs.rand() < 0.5:
+            if rs.rand() < 0.4:
+                # a batch of 2 .. 10 vectors of one length over one range: runs of them form units, a skewed one in the middle splits
+                # the run (probe) or sends its unit back to single MSMs (no probe)
+                kb = int(rs.randint(2, 11))
+                batch = [(sc, kind)] + [(cref.rng_scalars(int(rs.randint(1 << 30)), n), "uniform") if rs.rand() < 0.7 else scalars(c, n)
+                                        for _ in range(kb - 1)]
+                pts, infs = VariableBaseMSM.multi_scalar_mul_batch(ck, [ctx.upload(s) for s, _ in batch], mont=False, base_off=off)
+                for v, (s, kd) in enumerate(batch):
+                    check(c, xy, s, pts[v], infs[v], off, f"batch[{v}/{kb}] {kd} bps={bps} probe={probe} cap={cap}")
+                n_cases += kb - 1
+            elif rs.rand() < 0.5:
                 got, inf = VariableBaseMSM.multi_scalar_mul(ck, ctx.upload(sc), base_off=off)
                 check(c, xy, sc, got, inf, off, f"small {kind} bps={bps} probe={probe}")
             else:
