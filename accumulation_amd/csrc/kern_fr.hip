@@ -98,6 +98,8 @@ constexpr u32 BPL_LOCAL_FIXED_WORDS = 3u * BPL_NB + 2u * BPL_BINS + 2u * BPL_GRO
 // round 4: the whole 160 KiB a workgroup may declare (round 3: 148 KiB, and 1792 more fixed words) -- a plain-key MSM of 2^20
 // pairs over 16 bucket sets of 2^15 puts 32 768 entries into a partition, 36 200 into those of the top window on BLS12-381
 constexpr u32 BPL_LOCAL_BUDGET_WORDS = 40960u;
+static_assert(BPL_LOCAL_BUDGET_WORDS - BPL_LOCAL_FIXED_WORDS <= BPL_LOCAL_SLOTS * BPL_NB,
+              "k_prep_local_t keeps a partition of CAP entries in BPL_LOCAL_SLOTS registers per lane");
 static PrepGeom prep_bpl_geom(const MsmGeom& g) {
   PrepGeom pg;
   pg.SH = 10;

@@ -620,76 +620,110 @@ AMSM_DEV void bpl_slot(u32 s, u32& pos, u32& half) {
   }
 }
 
+// Inclusive prefix sum over the lanes of a workgroup of up to 1024 lanes: a shuffle scan inside every wave, then the
+// totals of the waves in front.  wt: 16 words of LDS that nothing else touches until the next barrier; ONE barrier.
+AMSM_DEV u32 block_scan_inclusive(u32 v, u32* wt) {
+  const u32 lane = __lane_id(), w = threadIdx.x >> 6;
+#pragma unroll
+  for (u32 d = 1; d < 64u; d <<= 1) {
+    const u32 o = __shfl_up(v, d);
+    if (lane >= d) v += o;
+  }
+  if (lane == 63u) wt[w] = v;
+  __syncthreads();
+  u32 before = 0;
+#pragma unroll
+  for (u32 i = 0; i < 15u; i++) before += i < w ? wt[i] : 0u;
+  return v + before;
+}
+
+// k_prep_local_t keeps its partition in REGISTERS between the count and the placement pass: entry i * 1024 + t in slot i of
+// lane t, BPL_LOCAL_SLOTS slots (kern_fr.hip asserts that they hold CAP entries), loaded and walked in blocks of
+// BPL_SLOT_BLOCK that a short partition skips whole.  f(b): slots [b, b + BPL_SLOT_BLOCK), b a constant after unrolling.
+constexpr u32 BPL_LOCAL_SLOTS = 37, BPL_SLOT_BLOCK = 8;
+template <class F>
+AMSM_DEV void bpl_slot_blocks(u32 n, F&& f) {
+#pragma unroll
+  for (u32 b = 0; b < BPL_LOCAL_SLOTS; b += BPL_SLOT_BLOCK)
+    if (b * BPL_NB < n) f(b);  // (the same in every lane of the workgroup)
+}
+
 // dynamic LDS: (3 * NB + 2 * BPL_BINS + 2 * BPL_GROUPS + 2 + CAP) words, NB = 2^SH = 1024 (kern_fr.hip: BPL_LOCAL_FIXED_WORDS).
-// Round 4: the 1024 scan words of the bucket-size prefix live in the (still empty) entry stage and a bucket's first staged
-// entry is its cursor's final value minus its count -- 1792 words more for entries.
+// The partition is read from memory ONCE, every load of a lane in flight before the first is used (the earlier two passes
+// of one dependent 8-byte load per trip were latency chains on a CU this workgroup holds alone); the prefix sums are
+// wave-level; the transposed write gives whole rows to waves, so that a lane looks its slot's bucket up once per group and the
+// steady state is one LDS read and one coalesced 256-byte row store per wave.
 __global__ void __launch_bounds__(1024)
     k_prep_local_t(const u32* __restrict__ part_start, const u64* __restrict__ part, MsmGeom g, PrepGeom pg, u32 stride,
                    u32* __restrict__ ents_t, BplGroup* __restrict__ grp, u32* __restrict__ order, u32* __restrict__ err) {
   extern __shared__ u32 prep_lds[];
-  const u32 NB = BPL_NB, NG = BPL_GROUPS;
-  u32* cnt = prep_lds;            // entries per bucket
-  u32* cur = cnt + NB;            // placement cursor: the bucket's first staged entry, after the placement its end
-  u32* ord = cur + NB;            // bucket at position i of the size order
-  u32* bins = ord + NB;           // BPL_BINS size classes: count, then first position
-  u32* bscan = bins + BPL_BINS;   // BPL_BINS scan words of the size-class prefix
-  u32* gm = bscan + BPL_BINS;     // NG: rows per group
-  u32* gb = gm + NG;              // NG + 1: first entry of the group inside the partition's block
-  u32* stage = gb + NG + 1;       // CAP sorted entries
-  u32* sl = stage;                // 1024 scan words of the bucket-size prefix: done before the first entry is staged
-  const u32 p = blockIdx.x, t = threadIdx.x, T = blockDim.x;
+  constexpr u32 NB = BPL_NB, NG = BPL_GROUPS, T = BPL_NB, SLOTS = BPL_LOCAL_SLOTS, BLK = BPL_SLOT_BLOCK;  // blockDim.x == T
+  u32* cnt = prep_lds;            // entries per bucket; after the size order: entries of the bucket at position i
+  u32* cur = cnt + NB;            // placement cursor of the bucket; after the size order: first staged entry of position i
+  u32* wt = cur + NB;             // 2 x 16 wave totals of the two prefix sums (NB words are set aside here)
+  u32* bins = wt + NB;            // BPL_BINS size classes: buckets in the class
+  u32* first = bins + BPL_BINS;   // BPL_BINS: first position of the class in the (descending) size order
+  u32* gm = first + BPL_BINS;     // NG: rows per group
+  u32* stage = gm + 2u * NG + 1u;  // CAP sorted entries (NG + 1 words in front of them are spare)
+  const u32 p = blockIdx.x, t = threadIdx.x;
   // fixed partitions (PrepGeom::FIX): `part_start` is the scatter's CURSOR array -- entries reserved, possibly more than fit
   const u32 ps = pg.FIX ? p * pg.FIX : part_start[p];
   const u32 n_p = pg.FIX ? part_start[p] : part_start[p + 1] - ps;
   const u32 pe = ps + (pg.FIX ? min(n_p, pg.FIX) : n_p);
   const u32 low = NB - 1u, idx_mask = (1u << pg.IB) - 1u, b0 = p << pg.SH;
   const bool fits = n_p <= pg.CAP && (!pg.FIX || n_p <= pg.FIX);  // (beyond FIX the scatter dropped entries)
-  for (u32 k = t; k < NB; k += T) cnt[k] = 0;
-  for (u32 k = t; k < BPL_BINS; k += T) bins[k] = 0;
-  for (u32 k = t; k < NG; k += T) gm[k] = 0;
+  const u32 n = fits ? min(pe - ps, SLOTS * T) : 0u;              // entries sorted here (CAP <= SLOTS * T)
+  // the whole partition into registers; a lane past the end re-reads the last entry and never uses it
+  u64 e[SLOTS];
+#pragma unroll
+  for (u32 i = 0; i < SLOTS; i++) e[i] = 0;
+  bpl_slot_blocks(n, [&](u32 b) {
+#pragma unroll
+    for (u32 i = b; i < b + BLK && i < SLOTS; i++) e[i] = part[ps + min(i * T + t, n - 1u)];
+  });
+  cnt[t] = 0;
+  if (t < BPL_BINS) bins[t] = 0;
+  if (t < NG) gm[t] = 0;
   __syncthreads();
-  if (fits)
-    for (u32 j = ps + t; j < pe; j += T) atomicAdd(&cnt[(u32)(part[j] >> 32) & low], 1u);
+  bpl_slot_blocks(n, [&](u32 b) {
+#pragma unroll
+    for (u32 i = b; i < b + BLK && i < SLOTS; i++)
+      if (i * T + t < n) atomicAdd(&cnt[(u32)(e[i] >> 32) & low], 1u);
+  });
   __syncthreads();
   // exclusive prefix of the bucket sizes: lane t owns bucket t (NB == T)
-  const u32 c_t = t < NB ? cnt[t] : 0u;
-  sl[t] = c_t;
-  __syncthreads();
-  for (u32 d = 1; d < T; d <<= 1) {
-    u32 v = t >= d ? sl[t - d] : 0u;
-    __syncthreads();
-    sl[t] += v;
-    __syncthreads();
-  }
-  if (t < NB) cur[t] = sl[t] - c_t;
+  const u32 c_t = cnt[t];
+  const u32 first_t = block_scan_inclusive(c_t, wt) - c_t;
+  cur[t] = first_t;
   // size class of my bucket and my rank inside it
   const u32 bin = min(c_t, BPL_BINS - 1u);
-  u32 rank = 0;
-  if (t < NB) rank = atomicAdd(&bins[bin], 1u);
-  __syncthreads();  // (every lane has read its sl[t]: the stage may be written)
-  // entries to their bucket's run (order inside a bucket is arbitrary: the sum does not depend on it)
-  if (fits)
-    for (u32 j = ps + t; j < pe; j += T) {
-      const u64 e = part[j];
-      const u32 k = (u32)(e >> 32) & low, lo = (u32)e;
-      const u32 pos = atomicAdd(&cur[k], 1u);
-      stage[pos] = (lo & 0x80000000u) | entry_abs_index(g, lo & idx_mask);
+  const u32 rank = atomicAdd(&bins[bin], 1u);
+  __syncthreads();
+  // entries to their bucket's run (order inside a bucket is arbitrary: the sum does not depend on it); a block's cursor
+  // atomics are all issued before the first staged entry is written
+  bpl_slot_blocks(n, [&](u32 b) {
+    u32 pos[BLK];
+#pragma unroll
+    for (u32 i = b; i < b + BLK && i < SLOTS; i++) {
+      pos[i - b] = 0;
+      if (i * T + t < n) pos[i - b] = atomicAdd(&cur[(u32)(e[i] >> 32) & low], 1u);
     }
-  // descending size order: first position of class b = buckets in larger classes
-  if (t < BPL_BINS) bscan[t] = bins[BPL_BINS - 1u - t];  // reversed, so that an inclusive scan counts the larger classes
-  __syncthreads();
-  for (u32 d = 1; d < BPL_BINS; d <<= 1) {
-    u32 v = (t < BPL_BINS && t >= d) ? bscan[t - d] : 0u;
-    __syncthreads();
-    if (t < BPL_BINS) bscan[t] += v;
-    __syncthreads();
-  }
-  if (t < BPL_BINS) bins[BPL_BINS - 1u - t] = bscan[t] - bins[BPL_BINS - 1u - t];  // exclusive
-  __syncthreads();
-  u32 my_pos = 0;
-  if (t < NB) {
-    my_pos = bins[bin] + rank;
-    ord[my_pos] = t;
+#pragma unroll
+    for (u32 i = b; i < b + BLK && i < SLOTS; i++) {
+      const u32 lo = (u32)e[i];
+      if (i * T + t < n) stage[pos[i - b]] = (lo & 0x80000000u) | entry_abs_index(g, lo & idx_mask);
+    }
+  });
+  // descending size order: first position of class b = buckets in larger classes (classes reversed, so that the inclusive
+  // prefix counts the larger ones)
+  const u32 in_class = t < BPL_BINS ? bins[BPL_BINS - 1u - t] : 0u;
+  const u32 larger = block_scan_inclusive(in_class, wt + 16) - in_class;
+  if (t < BPL_BINS) first[BPL_BINS - 1u - t] = larger;
+  __syncthreads();  // (the barrier inside the prefix sum closed the placement: cnt[] and cur[] are free to be reordered)
+  const u32 my_pos = first[bin] + rank;
+  cnt[my_pos] = c_t;
+  cur[my_pos] = first_t;
+  {
     // rows of the group(s) my bucket's lane(s) sit in (the last class is not sorted inside: maxima, not first elements)
     const u32 h0 = (c_t + 1u) >> 1;
     if (my_pos < BPL_SPLIT / 2u) atomicMax(&gm[0], h0);
@@ -697,40 +731,57 @@ __global__ void __launch_bounds__(1024)
     else atomicMax(&gm[my_pos / BPL_GROUP], c_t);
   }
   __syncthreads();
-  if (t == 0) {
-    u32 run = 0;
-    for (u32 q = 0; q < NG; q++) {
-      gb[q] = run;
-      run += gm[q] * BPL_GROUP;
-    }
-    gb[NG] = run;
+  // every lane adds up the rows of the 17 groups itself: lane q < NG keeps the first entry of group q for its header
+  u32 total = 0, my_gb = 0;
+#pragma unroll
+  for (u32 q = 0; q < NG; q++) {
+    if (q == t) my_gb = total;
+    total += gm[q] * BPL_GROUP;
   }
-  __syncthreads();
-  const u32 total = gb[NG];
   const bool ok = fits && total <= stride;
   if (!ok && t == 0) atomicOr(err + 1, 1u);  // overflow: the host falls back to the chunked pipeline
   if (t < NG) {
     BplGroup h;
-    h.base = p * stride + gb[t];
+    h.base = p * stride + my_gb;
     h.m = ok ? gm[t] : 0u;
     grp[p * NG + t] = h;
   }
-  if (t < NB) {  // which bucket each lane slot sums (both halves of a split bucket name it; the odd lane does not store)
+  {  // which bucket each lane slot sums (both halves of a split bucket name it; the odd lane does not store)
     u32* o = order + (size_t)p * BPL_LANES;
     if (my_pos < BPL_SPLIT / 2u) o[2u * my_pos] = o[2u * my_pos + 1u] = b0 + t;
     else if (my_pos < BPL_SPLIT) o[BPL_NB + 2u * (my_pos - BPL_SPLIT / 2u)] = o[BPL_NB + 2u * (my_pos - BPL_SPLIT / 2u) + 1u] = b0 + t;
     else o[my_pos] = b0 + t;
   }
   if (!ok) return;
-  for (u32 j = t; j < total; j += T) {
-    u32 q = 0;
-    while (q + 1u < NG && gb[q + 1u] <= j) q++;  // the group holding row element j (NG = 17 bases, ascending)
-    const u32 k = (j - gb[q]) / BPL_GROUP, l = j % BPL_GROUP;
+  // Transposed write.  The partition's block is a list of 64-entry rows (group 0's, then group 1's, ...); wave w writes the
+  // rows r = w (mod 16) of that list, so the 16 waves share every group evenly.  Lane l of the wave stands for lane slot
+  // 64 q + l while it is inside group q: it reads the slot's size and first staged entry once per group (the next group's while
+  // it writes this one's), then each row is one LDS read and one 256-byte store.
+  const u32 w = t >> 6, l = t & 63u;
+  auto slot_of = [&](u32 q, u32& sz, u32& src) {  // entries of lane slot 64 q + l and where they are staged
     u32 pos, half;
     bpl_slot(q * BPL_GROUP + l, pos, half);
-    const u32 kb = ord[pos], c = cnt[kb], h0 = (c + 1u) >> 1;
-    const u32 off = half == 2u ? h0 : 0u, sz = half == 0u ? c : (half == 1u ? h0 : c - h0);
-    ents_t[(size_t)p * stride + j] = k < sz ? stage[cur[kb] - c + off + k] : BPL_ENTRY_PAD;  // (cur = the bucket's end now)
+    const u32 c = cnt[pos], h0 = (c + 1u) >> 1;
+    sz = half == 0u ? c : (half == 1u ? h0 : c - h0);
+    src = cur[pos] + (half == 2u ? h0 : 0u);
+  };
+  u32* out = ents_t + (size_t)p * stride + l;
+  u32 row0 = 0, sz, src, m = gm[0];
+  slot_of(0, sz, src);
+  for (u32 q = 0; q < NG; q++) {
+    u32 sz_n = 0, src_n = 0, m_n = 0;
+    if (q + 1u < NG) {
+      m_n = gm[q + 1u];
+      slot_of(q + 1u, sz_n, src_n);
+    }
+    for (u32 k = (w - row0) & 15u; k < m; k += 16u) {
+      const u32 v = stage[k < sz ? src + k : 0u];
+      out[(size_t)(row0 + k) * BPL_GROUP] = k < sz ? v : BPL_ENTRY_PAD;
+    }
+    row0 += m;
+    sz = sz_n;
+    src = src_n;
+    m = m_n;
   }
 }
 
