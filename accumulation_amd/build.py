@@ -19,7 +19,7 @@ OBJ = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(HERE, "libamsm.so")
 ARCH = "gfx950"
 UNITS = ["api.hip", "kern_pallas.hip", "kern_bls12_381.hip", "kern_vesta.hip", "kern_bn254.hip", "kern_grumpkin.hip",
-         "kern_fr.hip"]
+         "kern_bls12_377.hip", "kern_fr.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result", "-Wno-pass-failed",
          "-Rpass-analysis=kernel-resource-usage"]
 
@@ -72,7 +72,7 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
     todo = [u for u in UNITS if force or _stale(os.path.join(OBJ, u.replace(".hip", ".o")), _unit_deps(u, deps))]
     if todo and verbose:
         print(f"[accumulation_amd.build] hipcc --offload-arch={ARCH}: {', '.join(todo)}", flush=True)
-    with ThreadPoolExecutor(max_workers=7) as ex:  # one worker per unit
+    with ThreadPoolExecutor(max_workers=8) as ex:  # one worker per unit
         list(ex.map(_compile, todo))
     objs = [os.path.join(OBJ, u.replace(".hip", ".o")) for u in UNITS]
     if todo or not os.path.exists(LIB):

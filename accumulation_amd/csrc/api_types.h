@@ -347,7 +347,7 @@ struct amsm_sponge {  // host-side Poseidon sponge over the curve's base field (
   int curve = 0;
   // one state per base field of curves.h; only the curve's own is used (of<Fq>())
   std::tuple<host::PoseidonSponge<PallasFq>, host::PoseidonSponge<Bls12381Fq>, host::PoseidonSponge<VestaFq>,
-             host::PoseidonSponge<Bn254Fq>, host::PoseidonSponge<GrumpkinFq>>
+             host::PoseidonSponge<Bn254Fq>, host::PoseidonSponge<GrumpkinFq>, host::PoseidonSponge<Bls12377Fq>>
       states;
   template <class Fq>
   host::PoseidonSponge<Fq>& of() { return std::get<host::PoseidonSponge<Fq>>(states); }

@@ -33,6 +33,13 @@ struct Bls12381Curve {  // ark-bls12-381 0.2 G1: y^2 = x^3 + 4, cofactor != 1
   static constexpr u64 gy[6] = {0x0caa232946c5e7e1ull, 0xd03cc744a2888ae4ull, 0x00db18cb2c04b3edull,
                                 0xfcf5e095d5d00af6ull, 0xa09e30ed741d8ae4ull, 0x08b3f481e3aaa0f1ull};
   static constexpr u64 cofactor[2] = {0x8c00aaab0000aaabull, 0x396c8c005555e156ull};  // #E(Fq) / r
+  // the subgroup test (points_check_kernels.h): |z| = 0xd201000000010000 (z is negative; the test only uses z^2), z^2, and the
+  // primitive cube root of unity beta (a canonical integer) for which phi(x, y) = (beta x, y) is -[z^2] on G1
+  static constexpr int z_bits = 64, z2_bits = 128;
+  AMSM_TABLE(z_word, 2, 0x00010000u, 0xd2010000u)
+  AMSM_TABLE(z2_word, 4, 0x00000000u, 0x00000001u, 0x0001a402u, 0xac45a401u)
+  static constexpr u64 beta[6] = {0x2e01fffffffefffeull, 0xde17d813620a0002ull, 0xddb3a93be6f89688ull,
+                                  0xba69c6076a0f77eaull, 0x5f19672fdf76ce51ull, 0};
 };
 struct VestaCurve {  // ark-vesta 0.2: y^2 = x^3 + 5, cofactor 1; Fq = Pallas Fr, Fr = Pallas Fq
   using Fq = VestaFq;
@@ -67,6 +74,28 @@ struct GrumpkinCurve {  // ark-grumpkin: y^2 = x^3 - 17, cofactor 1; Fq = BN254 
   static constexpr u64 cofactor[2] = {1, 0};
 };
 
+// ark-bls12-377 G1: y^2 = x^3 + 1, z = 0x8508c00000000001 (positive), r = z^4 - z^2 + 1 (253 bits), cofactor (z - 1)^2 / 3 =
+// 0x170b5d44300000000000000000000000: EVEN (divisible by 2^92), so the curve has points of order 2 (y = 0: (p - 1, 0)) and 6
+// ((2, 3)) beside (0, 1) of order 3 -- the group law meets y = 0 here and nowhere else (fp.h: HasTwoTorsion)
+struct Bls12377Curve {
+  using Fq = Bls12377Fq;
+  using Fr = Bls12377Fr;
+  static constexpr int id = AMSM_BLS12_377_G1;
+  static constexpr int b = 1;
+  static constexpr bool subgroup_check = true;
+  static constexpr u64 gx[6] = {0xeab9b16eb21be9efull, 0xd5481512ffcd394eull, 0x188282c8bd37cb5cull,
+                                0x85951e2caa9d41bbull, 0xc8fc6225bf87ff54ull, 0x008848defe740a67ull};
+  static constexpr u64 gy[6] = {0xfd82de55559c8ea6ull, 0xc2fe3d3634a9591aull, 0x6d182ad44fb82305ull,
+                                0xbd7fb348ca3e52d9ull, 0x1f674f5d30afeec4ull, 0x01914a69c5102effull};
+  static constexpr u64 cofactor[2] = {0, 0x170b5d4430000000ull};  // #E(Fq) / r
+  // the subgroup test: z (64 bits, weight 7), z^2 (127 bits, weight 22) and the beta with [z^2]P = (beta x, -y) on G1
+  static constexpr int z_bits = 64, z2_bits = 127;
+  AMSM_TABLE(z_word, 2, 0x00000001u, 0x8508c000u)
+  AMSM_TABLE(z2_word, 4, 0x00000001u, 0x0a118000u, 0x90000001u, 0x452217ccu)
+  static constexpr u64 beta[6] = {0xffffffffffffffffull, 0xd1e945779fffffffull, 0x59064ee822fb5bffull,
+                                  0xb8882a75cc9bc8e3ull, 0xbc8756ba8f8c524eull, 0x01ae3a4617c510eaull};
+};
+
 // base field pack -> its curve
 template <class Fq>
 struct CurveOf;
@@ -90,6 +119,10 @@ template <>
 struct CurveOf<GrumpkinFq> {
   using type = GrumpkinCurve;
 };
+template <>
+struct CurveOf<Bls12377Fq> {
+  using type = Bls12377Curve;
+};
 
 // f(Curve{}) for the curve with this id; `unknown` for any other id
 template <class R, class F>
@@ -100,6 +133,7 @@ R with_curve_or(int curve, R unknown, F&& f) {
     case AMSM_VESTA: return f(VestaCurve{});
     case AMSM_BN254_G1: return f(Bn254Curve{});  // (ids 3 and 5 are not curves: include/amsm.h)
     case AMSM_GRUMPKIN: return f(GrumpkinCurve{});
+    case AMSM_BLS12_377_G1: return f(Bls12377Curve{});  // (7 is not a curve either)
     default: return unknown;
   }
 }

@@ -9,7 +9,7 @@
 // canonical affine result is.
 //
 // The formulas are written once, in the bound-aware primitives of fp.h.  On a saturated field every value is
-// canonical and the K's are ignored.  On an unsaturated field (fpu.h; Pallas / Vesta Fq, cap = 2^261 ~ 128 p; BN254 and Grumpkin Fq, 169 p: the bounds below are written for 128) values are
+// canonical and the K's are ignored.  On an unsaturated field (fpu.h; Pallas / Vesta Fq, cap = 2^261 ~ 128 p; BN254 and Grumpkin Fq, 169 p; BLS12-381 Fq 2520 p, BLS12-377 Fq 38996 p: the bounds below are written for 128) values are
 // only bounded; the invariant of a point held in registers or memory is
 //        X < 8p      Y < 3p      ZZ, ZZZ < 2p      (affine / loaded coordinates: canonical, < p)
 // and the comments `[< k p]` give the bound of each intermediate: a product of A < a p and B < b p is
@@ -66,6 +66,12 @@ AMSM_DEV XYZZ<P> xyzz_from_affine(const Affine<P>& p) {
 template <class P>
 AMSM_DEV XYZZ<P> xyzz_dbl(const XYZZ<P>& p) {
   if (xyzz_is_inf<P>(p)) return p;
+  // A point of order 2 (Y = 0 mod p; BLS12-377 only, fp.h: HasTwoTorsion) doubles to the identity.  The formulas do give
+  // ZZ = 0 mod p, but on an unsaturated field as a non-zero multiple of p, which xyzz_is_inf (a test of the limbs) takes for a
+  // finite point: every later addition then returns 0 mod p in all four coordinates instead of the other operand.
+  if constexpr (HasTwoTorsion<P>::value) {
+    if (fe_is_zero_mod<P, 4>(p.y)) return xyzz_inf<P>();  // Y < 3p
+  }
   Fe<P> u = fe_dbl<P>(p.y);                                  // [< 16p]
   Fe<P> v = fe_sqr<P>(u);                                    // [< 3p]
   Fe<P> w = fe_mul<P>(u, v);                                 // [< 1.4p]
@@ -97,7 +103,7 @@ AMSM_DEV XYZZ<P> xyzz_dbl_affine(const Affine<P>& p) {  // p.x < 2p, p.y <= 2p (
   Fe<P> t = fe_sub_k<P, 8>(s, r.x);                          // [< 9.1p]
   // K = 4, not 2: y reaches 2p when xyzz_madd doubles a NEGATED point (q.y = 2p - y, y small), and K p - y is formed limb-wise
   // without a carry pass -- its top limb must not go negative, i.e. y < K p - 2^(B (L - 1)).  With K = 2 a point whose y lies
-  // (in the internal Montgomery radix) below 2^(B (L - 1)) (one in 2^17 for BLS12-381, one in 2^22 for Pallas, Vesta, BN254 and Grumpkin) doubled to garbage on that path: found by
+  // (in the internal Montgomery radix) below 2^(B (L - 1)) (one in 2^17 for BLS12-381, one in 6883 for BLS12-377, one in 2^22 for Pallas, Vesta, BN254 and Grumpkin) doubled to garbage on that path: found by
   // tools/fuzz_msm.py as ONE wrong point in a 124 124-point key fold by x = r - 2 (tests/golden/bls12_381_negated_doubling.json).
   r.y = fe_mul_sub_mul_k<P, 4>(m, t, p.y, w);                // (m t + (4p - y) w) / R': (30 + 4.4) / 128  [< 1.3p]
   r.zz = v;
@@ -196,7 +202,7 @@ AMSM_DEV Affine<P> affine_neg_if(const Affine<P>& p, bool negate) {
 // doublings and ~43 mixed additions per point): the doubling is 3M + 4S against XYZZ's 6M + 3S, the mixed addition 8M + 3S
 // against 8M + 2S -- 1/6 fewer multiplier passes over a fold.  (The bucket accumulation adds, it does not double: XYZZ stays
 // there.)  ark-ec's own formulas for these curves are Jacobian as well (ec.h header); only canonical affine results are compared.
-// Invariant of a point held in registers (unsaturated fields, cap = 2^261 ~ 128 p for Pallas and Vesta, 169 p for BN254 and Grumpkin, far more for BLS12-381):
+// Invariant of a point held in registers (unsaturated fields, cap = 2^261 ~ 128 p for Pallas and Vesta, 169 p for BN254 and Grumpkin, far more for BLS12-381 and BLS12-377):
 //        X < 12p      Y < 13p      Z < 3p        all tight
 // with the same bound notation as above.
 // ---------------------------------------------------------------------------------------------
@@ -220,6 +226,9 @@ AMSM_DEV bool jac_is_inf(const Jac<P>& p) {
 template <class P>
 AMSM_DEV Jac<P> jac_dbl(const Jac<P>& p) {
   if (jac_is_inf<P>(p)) return p;
+  if constexpr (HasTwoTorsion<P>::value) {  // as xyzz_dbl: Z3 = 2 Y Z would be a non-zero multiple of p
+    if (fe_is_zero_mod<P, 16>(p.y)) return jac_inf<P>();  // Y < 13p
+  }
   const Fe<P> zero = fe_zero<P>();
   Fe<P> xx = fe_sqr<P>(p.x);                                  // [< 2.2p]
   Fe<P> yy = fe_sqr<P>(p.y);                                  // [< 2.4p]
@@ -315,6 +324,9 @@ AMSM_DEV Fe<P> fe_sel4(u32 k, const Fe<P>& a0, const Fe<P>& a1, const Fe<P>& a2,
 template <class P>
 AMSM_DEV XYZZ<P> xyzz_dbl_quad(const XYZZ<P>& p) {
   if (xyzz_is_inf<P>(p)) return p;
+  if constexpr (HasTwoTorsion<P>::value) {  // as xyzz_dbl; uniform over the quad (replicated operands)
+    if (fe_is_zero_mod<P, 4>(p.y)) return xyzz_inf<P>();
+  }
   const u32 k = __lane_id() & 3u;
   const Fe<P> zero = fe_zero<P>();
   Fe<P> u = fe_dbl<P>(p.y);

@@ -146,6 +146,31 @@ struct GrumpkinFr {  // scalar field of Grumpkin (= BN254 Fq); 254 bits
   AMSM_TABLE(r2, 8, 0x538afa89u, 0xf32cfc5bu, 0xd44501fbu, 0xb5e71911u, 0x0a417ff6u, 0x47ab1effu, 0xcab8351fu, 0x06d89f71u)
 };
 
+// BLS12-377 G1 (ark-bls12-377: z = 0x8508c00000000001, r = z^4 - z^2 + 1, p = (z - 1)^2 r / 3 + z).  Both moduli are 1 mod 2^32
+// (2-adicity 46 and 47), so INV = 2^32 - 1 and limb 0 is 1 as on the Pasta fields; no other limb is zero.
+struct Bls12377Fq {  // base field of BLS12-377; 377 bits, 2-adicity 46
+  static constexpr int L = 12;  // register limbs
+  static constexpr int W = 12;  // 32-bit words in memory
+  static constexpr bool UNSAT = false;
+  static constexpr u32 INV = 0xffffffffu;
+  AMSM_TABLE(mod, 12, 0x00000001u, 0x8508c000u, 0x30000000u, 0x170b5d44u, 0xba094800u, 0x1ef3622fu, 0x00f5138fu, 0x1a22d9f3u,
+             0x6ca1493bu, 0xc63b05c0u, 0x17c510eau, 0x01ae3a46u)
+  AMSM_TABLE(one, 12, 0xffffff68u, 0x02cdffffu, 0x7fffffb1u, 0x51409f83u, 0x8a7d3ff2u, 0x9f7db3a9u, 0x6e7c6305u, 0x7b4e97b7u,
+             0x803c84e8u, 0x4cf495bfu, 0xe2fdf49au, 0x008d6661u)
+  AMSM_TABLE(r2, 12, 0x9400cd22u, 0xb786686cu, 0xb00431b1u, 0x0329fcaau, 0x62d6b46du, 0x22a5f111u, 0x827dc3acu, 0xbfdf7d03u,
+             0x41790bf9u, 0x837e92f0u, 0x1e914b88u, 0x006dfccbu)
+};
+
+struct Bls12377Fr {  // scalar field of BLS12-377; 253 bits, 2-adicity 47
+  static constexpr int L = 8;  // register limbs
+  static constexpr int W = 8;  // 32-bit words in memory
+  static constexpr bool UNSAT = false;
+  static constexpr u32 INV = 0xffffffffu;
+  AMSM_TABLE(mod, 8, 0x00000001u, 0x0a118000u, 0xd0000001u, 0x59aa76feu, 0x5c37b001u, 0x60b44d1eu, 0x9a2ca556u, 0x12ab655eu)
+  AMSM_TABLE(one, 8, 0xfffffff3u, 0x7d1c7fffu, 0x6ffffff2u, 0x7257f50fu, 0x512c0feeu, 0x16d81575u, 0x2bbb9a9du, 0x0d4bda32u)
+  AMSM_TABLE(r2, 8, 0xb861857bu, 0x25d577bau, 0x8860591fu, 0xcc2c27b5u, 0xe5dc8593u, 0xa7cc008fu, 0xeff1c939u, 0x011fdae7u)
+};
+
 // ------------------------------------------------------------------------------------------------
 // Element type and helpers
 // ------------------------------------------------------------------------------------------------
@@ -155,11 +180,11 @@ struct Fe {
 };
 
 }  // namespace amsm
-#include "fpu.h"  // unsaturated-limb packs (PallasFqU, VestaFqU, Bls12381FqU, Bn254FqU, GrumpkinFqU) and their u_* primitives
+#include "fpu.h"  // unsaturated-limb packs (PallasFqU, VestaFqU, Bls12381FqU, Bn254FqU, GrumpkinFqU, Bls12377FqU) and their u_* primitives
 namespace amsm {
 
 // Field the DEVICE kernels compute in for a given ABI field: Pallas, Vesta, BN254 and Grumpkin Fq run on 9 x 29-bit unsaturated limbs
-// (internal Montgomery radix 2^261, fpu.h), BLS12-381 Fq on 14 x 28-bit limbs (radix 2^392).  (The saturated 32-bit-limb
+// (internal Montgomery radix 2^261, fpu.h), BLS12-381 and BLS12-377 Fq on 14 x 28-bit limbs (radix 2^392).  (The saturated 32-bit-limb
 // schedules serve both scalar fields; for the base fields they measured 21 % / 23 % slower: DESIGN.md 4.1.)
 template <class Fq>
 struct DevField {
@@ -184,6 +209,26 @@ struct DevField<Bn254Fq> {  // 9 x 29 bits through the general reduction (fpu.h:
 template <>
 struct DevField<GrumpkinFq> {  // the same general reduction over the other modulus of the cycle (fpu.h: GrumpkinFqU)
   using type = GrumpkinFqU;
+};
+template <>
+struct DevField<Bls12377Fq> {  // the second 14 x 28 field, the first of that shape with p_0 = 1 (fpu.h: Bls12377FqU)
+  using type = Bls12377FqU;
+};
+
+// Does the curve over this base field have points with y = 0 (order 2)?  Only a curve of EVEN order does: BLS12-377, whose cofactor
+// is divisible by 2^92.  There a doubling can meet Y = 0 mod p, and on an unsaturated field that zero may arrive as a non-zero
+// multiple of p (ec.h: xyzz_dbl).  Every other curve here has odd order and keeps its doublings as they are.
+template <class P>
+struct HasTwoTorsion {
+  static constexpr bool value = false;
+};
+template <>
+struct HasTwoTorsion<Bls12377Fq> {
+  static constexpr bool value = true;
+};
+template <>
+struct HasTwoTorsion<Bls12377FqU> {
+  static constexpr bool value = true;
 };
 
 template <class P>

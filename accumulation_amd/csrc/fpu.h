@@ -1,5 +1,5 @@
 // Unsaturated-limb Montgomery arithmetic for the base fields of the MSM hot loop (gfx950): Pallas Fq, Vesta Fq,
-// BN254 Fq and Grumpkin Fq on 9 x 29 bits, BLS12-381 Fq on 14 x 28 bits.
+// BN254 Fq and Grumpkin Fq on 9 x 29 bits, BLS12-381 Fq and BLS12-377 Fq on 14 x 28 bits.
 //
 // gfx950 has no carry-in on v_mad_u64_u32 and a VALU carry write costs wait states, so the saturated 8 x 32-bit
 // schedule (fp_mul_gfx950.h) pays one v_addc per product.  Here an element is L limbs of B bits (Pallas Fq: 9 x 29,
@@ -115,6 +115,32 @@ struct Bls12381FqU {  // 14 x 28 bits, R' = 2^392 ~ 2520 p: measured against the
   AMSM_TABLE(one, 14, 0x0347fcb8u, 0x0d800000u, 0x0002b119u, 0x00cde6d2u, 0x0c7212e0u, 0x083a2090u, 0x0037669fu, 0x0da0f73eu, 0x09b09b42u, 0x01297bb0u, 0x0515d98fu, 0x0012ca7cu, 0x0659fcfau, 0x0000577au)
   AMSM_TABLE(k_import, 14, 0x080e6299u, 0x03500034u, 0x0eb12856u, 0x0deb2699u, 0x0c988670u, 0x04ef6697u, 0x070983e8u, 0x0a4e6fe9u, 0x03e8a053u, 0x0ecf271eu, 0x0c20d323u, 0x06eb6385u, 0x047f1286u, 0x000156dau)
   AMSM_TABLE(k_export, 14, 0x0002fffdu, 0x00900000u, 0x0c000276u, 0x0000bc40u, 0x08baebf4u, 0x05753c75u, 0x055f4898u, 0x07052574u, 0x07ce5853u, 0x056ec6d7u, 0x071a97a2u, 0x0e4935c0u, 0x0ec3fa80u, 0x00015f65u)
+};
+
+struct Bls12377Fq;
+// BLS12-377 Fq: 377 bits on the 14 x 28 shape, R' = 2^392 ~ 38996 p (BLS12-381: 2520), so every `[< k p]` line of ec.h holds with
+// room to spare, and p > 6883 * 2^364 gives u_kp_minus_lazy's exact condition y < K p - 2^(B (L - 1)) from y < (K - 1) p.  The first
+// 14-limb field with p = 1 mod 2^28: NINV = 2^28 - 1, so u_red_low takes the p_0 = 1 branch (no m_k p_0 product, one 64-bit add of a
+// constant) at B = 28.  No limb of p is zero and none above limb 0 is a power of two: 13 reduction products per column against
+// BLS12-381's 14.  Column sums as for BLS12-381 (same limb widths): 2 * 14 products with one lazy operand (< 2^57 each) + 13
+// reduction products (< 2^56) + an addend and the carry stay below 2^63.
+struct Bls12377FqU {
+  using Sat = Bls12377Fq;
+  static constexpr int L = 14;
+  static constexpr int W = 12;
+  static constexpr int B = 28;
+  static constexpr bool UNSAT = true;
+  static constexpr u32 NINV = 0x0fffffffu;  // -p^-1 mod 2^B: p_0 = 1
+  // measured both ways in two runs of tools/fp_bench.hip beside BLS12-381's lines, the order of the two settings swapped (MI355X, cycles
+  // per SIMD at 2 waves per SIMD, chain / no chain): mixed addition 21 400 / 22 489 and 21 724 / 22 618 (BLS12-381: 22 796, 22 832) --
+  // the mixed addition decides, 4-5 % in either order; the bare multiplication's 3 % follow the position in the run.  The
+  // accumulation kernels keep 2 waves without scratch with it; the three ladder kernels (k_generate_bases, k_sample_finish,
+  // k_points_check_subgroup<1>) drop to 1 wave: profiles/bls12_377_fp_bench.txt, DESIGN.md 4.1
+  static constexpr bool CHAIN = true;
+  AMSM_TABLE(mod, 14, 0x00000001u, 0x008c0000u, 0x00000085u, 0x05d44300u, 0x0800170bu, 0x02fba094u, 0x0f1ef362u, 0x000f5138u, 0x0a22d9f3u, 0x0a1493b1u, 0x0b05c06cu, 0x010eac63u, 0x0a4617c5u, 0x00001ae3u)
+  AMSM_TABLE(one, 14, 0x0fff67acu, 0x020fffffu, 0x0fb0d727u, 0x0e9203ffu, 0x0249b0e4u, 0x0e172345u, 0x0955d771u, 0x02bf89aau, 0x0b2833b2u, 0x098e116bu, 0x07dc5c97u, 0x00d43e93u, 0x02e3314bu, 0x000003b4u)
+  AMSM_TABLE(k_import, 14, 0x0f67abddu, 0x0cdbffffu, 0x00d714f0u, 0x05fed6fbu, 0x01adbe5bu, 0x0ebc50d7u, 0x049c2b74u, 0x0d718fccu, 0x056fe5f2u, 0x0d413a69u, 0x0a9348beu, 0x0f3d01dcu, 0x0b9c0b1bu, 0x0000070eu)
+  AMSM_TABLE(k_export, 14, 0x0fffff68u, 0x0cdfffffu, 0x0fffb102u, 0x09f837ffu, 0x0ff25140u, 0x0a98a7d3u, 0x059f7db3u, 0x06e7c630u, 0x0b4e97b7u, 0x03c84e87u, 0x0495bf80u, 0x0f49a4cfu, 0x0661e2fdu, 0x000008d6u)
 };
 
 template <class P>

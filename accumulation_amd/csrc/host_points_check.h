@@ -12,10 +12,6 @@
 namespace amsm {
 namespace host {
 
-// BLS12-381: the primitive cube root of unity beta (a canonical integer) for which phi(x, y) = (beta x, y) is -[z^2] on G1
-constexpr u64 BLS12_381_BETA[6] = {0x2e01fffffffefffeull, 0xde17d813620a0002ull, 0xddb3a93be6f89688ull,
-                                   0xba69c6076a0f77eaull, 0x5f19672fdf76ce51ull, 0};
-
 template <class Fq>
 inline PointsCheckConsts points_check_consts() {
   using C = typename CurveOf<Fq>::type;
@@ -25,9 +21,9 @@ inline PointsCheckConsts points_check_consts() {
   const HFe<Fq> b = curve_b_mont<Fq>(C::b);
   memcpy(k.b, b.v, 8 * N);
   if constexpr (C::subgroup_check) {
-    static_assert(N == 6, "the endomorphism constant is BLS12-381's");
+    static_assert(sizeof(C::beta) == 8 * N, "the curve's endomorphism constant (curves.h), one word per limb");
     HFe<Fq> beta;
-    memcpy(beta.v, BLS12_381_BETA, 8 * N);
+    memcpy(beta.v, C::beta, 8 * N);
     beta = h_to_mont<Fq>(beta);
     memcpy(k.beta, beta.v, 8 * N);
   }

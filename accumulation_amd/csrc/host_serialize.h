@@ -7,11 +7,11 @@
 //       ceil((MODULUS_BITS + flag bits) / 8) bytes; the flags occupy the top bits of the LAST byte.
 //   SW affine point, compressed (`GroupAffine::serialize`): x with SWFlags (2 flag bits): bit 7 of the last byte =
 //       "y is the larger of (y, -y)" (`SWFlags::from_y_sign(y > -y)`), bit 6 = point at infinity (x = 0).  Both set is
-//       invalid.  Pallas, Vesta: 255 + 2 bits -> 33 bytes; BN254 G1, Grumpkin: 254 + 2 -> 32 bytes; BLS12-381 G1: 381 + 2 -> 48 bytes.
+//       invalid.  Pallas, Vesta: 255 + 2 bits -> 33 bytes; BN254 G1, Grumpkin: 254 + 2 -> 32 bytes; BLS12-381 G1: 381 + 2 -> 48 bytes; BLS12-377 G1: 377 + 2 -> 48 bytes.
 //   SW affine point, uncompressed (`serialize_uncompressed`): x (no flags) then y with SWFlags (infinity bit only):
-//       Pallas / Vesta 32 + 33 = 65 bytes, BN254 G1 / Grumpkin 32 + 32 = 64 bytes, BLS12-381 G1 48 + 48 = 96 bytes.
+//       Pallas / Vesta 32 + 33 = 65 bytes, BN254 G1 / Grumpkin 32 + 32 = 64 bytes, BLS12-381 G1 and BLS12-377 G1 48 + 48 = 96 bytes.
 //   Deserialisation rejects non-canonical integers (>= modulus), x without a square root, points off the curve
-//       (uncompressed) and points outside the prime-order subgroup (BLS12-381 G1; Pallas, Vesta, BN254 G1 and Grumpkin have cofactor 1).
+//       (uncompressed) and points outside the prime-order subgroup (BLS12-381 G1, BLS12-377 G1; Pallas, Vesta, BN254 G1 and Grumpkin have cofactor 1).
 #pragma once
 #include "host_field.h"
 
@@ -64,7 +64,7 @@ inline bool h_gt_canonical(const HFe<P>& a, const HFe<P>& b) {
   return false;
 }
 
-// Square root by Tonelli-Shanks (any odd prime; Pallas and Vesta Fq have 2-adicity 32, Grumpkin Fq 28, BLS12-381 and BN254 Fq 1).  Returns false when a is
+// Square root by Tonelli-Shanks (any odd prime; Pallas and Vesta Fq have 2-adicity 32, Grumpkin Fq 28, BLS12-377 Fq 46, BLS12-381 and BN254 Fq 1).  Returns false when a is
 // not a square.
 template <class P>
 inline bool h_sqrt(const HFe<P>& a, HFe<P>* out) {

@@ -1,5 +1,5 @@
 // Launcher definitions for the elliptic-curve kernels of ONE curve; included by kern_pallas.hip,
-// kern_bls12_381.hip, kern_vesta.hip, kern_bn254.hip and kern_grumpkin.hip with AMSM_FQ set to the (C-ABI) base-field parameter pack.  The kernels are instantiated
+// kern_bls12_381.hip, kern_vesta.hip, kern_bn254.hip, kern_grumpkin.hip and kern_bls12_377.hip with AMSM_FQ set to the (C-ABI) base-field parameter pack.  The kernels are instantiated
 // for FQD = DevField<AMSM_FQ>::type, the field the device computes in (fp.h).
 #include <algorithm>
 #include <atomic>

@@ -550,5 +550,6 @@ AMSM_FR_LAUNCHERS(Bls12381Fr)
 AMSM_FR_LAUNCHERS(VestaFr)
 AMSM_FR_LAUNCHERS(Bn254Fr)
 AMSM_FR_LAUNCHERS(GrumpkinFr)
+AMSM_FR_LAUNCHERS(Bls12377Fr)
 
 }  // namespace amsm

@@ -1,5 +1,5 @@
 // Host-callable launchers for the device kernels.  The heavy elliptic-curve kernels are compiled in one
-// translation unit per curve (kern_pallas.hip / kern_bls12_381.hip / kern_vesta.hip / kern_bn254.hip / kern_grumpkin.hip), the scalar-field kernels in
+// translation unit per curve (kern_pallas.hip / kern_bls12_381.hip / kern_vesta.hip / kern_bn254.hip / kern_grumpkin.hip / kern_bls12_377.hip), the scalar-field kernels in
 // kern_fr.hip, so the library builds in parallel; api.hip only sees these declarations.
 #pragma once
 #include <hip/hip_runtime.h>

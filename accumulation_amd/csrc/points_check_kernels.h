@@ -3,15 +3,16 @@
 //     0 valid            flagged infinite (coordinates ignored, as k_apply_inf ignores them), or (0, 0), or none of the below
 //     1 non-canonical    the integer in the words of x or of y is >= p (tested on the words as they arrive)
 //     2 off the curve    y^2 != x^3 + b
-//     3 off the subgroup [r]P != O (curves.h: subgroup_check -- BLS12-381 G1 only; Pallas, Vesta, BN254 G1 and Grumpkin have cofactor 1)
+//     3 off the subgroup [r]P != O (curves.h: subgroup_check -- BLS12-381 G1 and BLS12-377 G1; Pallas, Vesta, BN254 G1 and Grumpkin have cofactor 1)
 // -- in two kernels, so that the cheap pass does not inherit the ladder's registers:
 //   k_points_check_curve     every curve: rules 1 and 2, three multiplications per point over 64 or 96 bytes (memory-shaped: 16-byte
 //                            loads as k_points_import makes them).  Writes every status byte.
-//   k_points_check_subgroup  BLS12-381: rule 3 for the points the first kernel left at 0 (the identity apart); every other lane idles.
+//   k_points_check_subgroup  BLS12-381, BLS12-377: rule 3 for the points the first kernel left at 0 (the identity apart); every other lane idles.
 // Both count the bad points by status into counters[0..2] and keep the smallest bad index in counters[PCHK_FIRST_BAD] (atomics of
 // the rare bad lanes only).
 //
-// The subgroup test is not [r]P.  With z = -0xd201000000010000 (r = z^4 - z^2 + 1) and phi(x, y) = (beta x, y), beta a primitive
+// The subgroup test is not [r]P.  With z = -0xd201000000010000 on BLS12-381, z = 0x8508c00000000001 on BLS12-377 (r = z^4 - z^2 + 1; only
+// z^2 enters, so the sign of z does not; |z|, z^2, their bit lengths and beta are the curve's, curves.h) and phi(x, y) = (beta x, y), beta a primitive
 // cube root of unity, phi^2 + phi + 1 = 0 on the whole curve; on G1 phi acts as the scalar -z^2 (for the beta of
 // host_points_check.h; G1 is cyclic, so checking the generator settles it).  Hence
 //     P in G1   =>   [z^2]P = -phi(P) = (beta x, -y), and [z^2]P != O unless P = O          (complete)
@@ -20,8 +21,12 @@
 // Two ladders compute [z^2]P, both over public constant digits (no lane diverges inside them):
 //   LADDER 1  one stage over z^2 (128 bits, weight 17): 127 doublings and 16 mixed additions of P; holds one XYZZ value and P
 //   LADDER 2  [|z|]([|z|]P) (|z|: 64 bits, weight 6): 126 doublings, 5 mixed and 5 full additions; holds two XYZZ values and P
+//   (BLS12-377: z^2 has 127 bits and weight 22 -- 126 doublings and 21 mixed additions; z 64 bits, weight 7 -- 126 doublings, 6 mixed
+//   and 6 full additions.)
 // Inputs outside the subgroup make intermediates hit O and +-P (points of order 3, 11, 10177; (0, 2), of order 3 with x = 0): every
-// addition is one of ec.h's exact-exception forms.
+// addition is one of ec.h's exact-exception forms.  BLS12-377's cofactor is even: (p - 1, 0) has order 2 and (2, 3) order 6, whose
+// ladders double a point with Y = 0 mod p -- the one case where ZZ = 0 mod p comes out of a multiplication and not out of
+// xyzz_inf(); xyzz_dbl returns the identity's limbs there (ec.h, fp.h: HasTwoTorsion).
 #pragma once
 #include "curves.h"
 #include "ec.h"
@@ -29,10 +34,6 @@
 #include "sample_kernels.h"
 
 namespace amsm {
-
-// |z| and z^2 of BLS12-381 as 32-bit words, low word first
-AMSM_HD constexpr u32 bls_z_word(int i) { return i == 0 ? 0x00010000u : 0xd2010000u; }
-AMSM_HD constexpr u32 bls_z2_word(int i) { return i == 0 ? 0u : (i == 1 ? 1u : (i == 2 ? 0x0001a402u : 0xac45a401u)); }
 
 template <class P, u32 KMAX>
 AMSM_DEV Fe<P> fe_canon_k(const Fe<P>& a) {  // tight, value < KMAX p -> canonical (no-op on a saturated field)
@@ -119,16 +120,17 @@ __global__ void __launch_bounds__(256)
   p = affine_import<FQD>(p);
   p.x = fe_canon<FQD>(p.x);
   p.y = fe_canon<FQD>(p.y);
+  using C = typename CurveOf<typename SatOf<FQD>::type>::type;  // |z|, z^2 and their bit lengths: the curve's (curves.h)
   XYZZ<FQD> acc;
   if constexpr (LADDER == 1) {
-    acc = points_check_ladder<FQD, 128>(p, [](int w) { return bls_z2_word(w); });
+    acc = points_check_ladder<FQD, C::z2_bits>(p, [](int w) { return C::z2_word(w); });
   } else {
-    const XYZZ<FQD> q = points_check_ladder<FQD, 64>(p, [](int w) { return bls_z_word(w); });
+    const XYZZ<FQD> q = points_check_ladder<FQD, C::z_bits>(p, [](int w) { return C::z_word(w); });
     acc = q;
 #pragma unroll 1
-    for (int bit = 62; bit >= 0; bit--) {
+    for (int bit = C::z_bits - 2; bit >= 0; bit--) {
       acc = xyzz_dbl<FQD>(acc);
-      if ((bls_z_word(bit >> 5) >> (bit & 31)) & 1u) xyzz_add<FQD>(acc, q);
+      if ((C::z_word(bit >> 5) >> (bit & 31)) & 1u) xyzz_add<FQD>(acc, q);
     }
   }
   // [z^2]P == (beta x, -y)?  X == beta x ZZ, Y + y ZZZ == 0, ZZ != 0, on canonical limbs

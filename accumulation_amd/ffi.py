@@ -19,6 +19,7 @@ AMSM_BLS12_381_G1 = 1
 AMSM_VESTA = 2
 AMSM_BN254_G1 = 4
 AMSM_GRUMPKIN = 6  # (3 and 5 are not curves and are refused on purpose; Grumpkin is 6)
+AMSM_BLS12_377_G1 = 8  # (7 is not a curve either)
 
 AMSM_OK = 0
 AMSM_E_INVALID_ARG = -1

@@ -31,9 +31,9 @@ from .sponge import CryptographicSponge, Sha256Sponge
 CHALLENGE_SIZE = 128
 # (smallest log2(d+1) whose opening folds at all, fold while the key has more than 2^T generators), measured on MI355X:
 # Pallas 2^20 42 -> 34 ms, 2^18 19.0 -> 18.4, 2^16 better without; BLS12-381 2^20 89 -> 70 ms, 2^16 25 -> 23; Vesta takes
-# Pallas's (same limb shape, not measured separately) and so do BN254 and Grumpkin (same limb count; unmeasured).  The same table as include/amsm.hpp: amsm::ipa_fold_thresholds.
+# Pallas's (same limb shape, not measured separately) and so do BN254 and Grumpkin (same limb count; unmeasured); BLS12-377 takes BLS12-381's (same limb shape; unmeasured).  The same table as include/amsm.hpp: amsm::ipa_fold_thresholds.
 IPA_FOLD = {ffi.AMSM_PALLAS: (18, 15), ffi.AMSM_BLS12_381_G1: (16, 15), ffi.AMSM_VESTA: (18, 15),
-            ffi.AMSM_BN254_G1: (18, 15), ffi.AMSM_GRUMPKIN: (18, 15)}
+            ffi.AMSM_BN254_G1: (18, 15), ffi.AMSM_GRUMPKIN: (18, 15), ffi.AMSM_BLS12_377_G1: (16, 15)}
 _lincomb = ASForHadamardProducts._lincomb
 
 

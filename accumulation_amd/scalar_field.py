@@ -12,6 +12,7 @@ MODULI = {
     ffi.AMSM_VESTA: 0x40000000000000000000000000000000224698FC094CF91B992D30ED00000001,  # = Pallas's base field
     ffi.AMSM_BN254_G1: 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001,
     ffi.AMSM_GRUMPKIN: 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47,  # = BN254's base field
+    ffi.AMSM_BLS12_377_G1: 0x12AB655E9A2CA55660B44D1E5C37B00159AA76FED00000010A11800000000001,
 }
 _R = 1 << 256
 _M64 = (1 << 64) - 1

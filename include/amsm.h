@@ -11,7 +11,7 @@
  *
  * Data formats (identical to ark-ff 0.2 memory, so Rust slices can be passed zero-copy):
  *   - field element  : little-endian u64 limbs of x*R mod m (Montgomery form), R = 2^(64*limbs);
- *                      limbs = 4 for Pallas, Vesta, BN254 and Grumpkin Fq/Fr and BLS12-381 Fr, 6 for BLS12-381 Fq.
+ *                      limbs = 4 for Pallas, Vesta, BN254 and Grumpkin Fq/Fr and BLS12-381 / BLS12-377 Fr, 6 for BLS12-381 and BLS12-377 Fq.
  *   - scalar (BigInt): 4 little-endian u64 limbs of the canonical integer in [0, r)  (`into_repr()`),
  *                      or Montgomery form when the `scalars_mont` argument is non-zero (raw `Vec<Fr>`).
  *   - affine point   : 2*limbs u64 = x_mont | y_mont, plus a separate is_inf byte (ark-ec
@@ -55,6 +55,9 @@ enum amsm_curve {
   AMSM_BN254_G1 = 4,     /* ark_bn254::G1Affine (alt_bn128): y^2 = x^3 + 3 over a 254-bit field, cofactor 1, generator (1, 2); extension */
   AMSM_GRUMPKIN = 6,     /* ark_grumpkin::Affine: y^2 = x^3 - 17 over BN254's scalar field, cofactor 1, generator (1, sqrt(-16)); its scalar field is
                             BN254's base field -- BN254's partner in that cycle (Fq = BN254 Fr, Fr = BN254 Fq); extension */
+  /* 7 is not a curve and is refused */
+  AMSM_BLS12_377_G1 = 8, /* ark_bls12_377::G1Affine: y^2 = x^3 + 1 over a 377-bit field (6 limbs), 253-bit scalar field, cofactor
+                            0x170b5d44300000000000000000000000 (even: the curve has points of order 2); extension */
 };
 
 enum amsm_status {
@@ -192,7 +195,7 @@ int amsm_ctx_batched_split_stats(const amsm_ctx* ctx, unsigned long long* n_unit
                                  unsigned long long* n_unit_reruns);
 void amsm_ctx_destroy(amsm_ctx* ctx);
 int amsm_ctx_curve(const amsm_ctx* ctx);
-/* limbs (u64) of a base-field element: 4 (Pallas, Vesta, BN254, Grumpkin) or 6 (BLS12-381). */
+/* limbs (u64) of a base-field element: 4 (Pallas, Vesta, BN254, Grumpkin) or 6 (BLS12-381, BLS12-377). */
 int amsm_ctx_fq_limbs(const amsm_ctx* ctx);
 /* Override the Pippenger window width c (bits); 0 restores the automatic choice. */
 int amsm_ctx_set_window(amsm_ctx* ctx, int c_bits);
@@ -258,7 +261,7 @@ int amsm_bases_generate(amsm_ctx* ctx, uint64_t seed, size_t n, unsigned flags, 
  *     v = BLAKE2s-256(M(i,j,0)) || BLAKE2s-256(M(i,j,1)) as a little-endian integer (RFC 7693, unkeyed)
  *     x = v mod 2^bits, bits = bit length of p;  sign = bit 511 of v;  reject x >= p;  reject x^3 + b not a non-zero square
  *     y = the root with (y > p - y) == sign (canonical integers: the wire format's "larger root" rule)
- *     G_i = (x, y) on Pallas, Vesta, BN254 G1 and Grumpkin (bits = 255, 255, 254, 254; b = -17 on Grumpkin is q - 17);  G_i = [h](x, y), h = 0x396c8c005555e1568c00aaab0000aaab, on BLS12-381 G1 (reject the identity)
+ *     G_i = (x, y) on Pallas, Vesta, BN254 G1 and Grumpkin (bits = 255, 255, 254, 254; b = -17 on Grumpkin is q - 17);  G_i = [h](x, y), h = 0x396c8c005555e1568c00aaab0000aaab, on BLS12-381 G1 and h = 0x170b5d44300000000000000000000000 on BLS12-377 G1 (bits = 381, 377; reject the identity)
  * for the first attempt j = 0, 1, ... that is not rejected.  At most 256 attempts are made per index; should an index exhaust them
  * (probability below 2^-100 per key) the call returns AMSM_E_UNSUPPORTED and creates no key.  Sampled on the device straight into
  * the resident key (host backend: on the host pool, the same bits).  Flags, error codes, the n >= 2^31 rule and n == 0 as for
@@ -275,7 +278,7 @@ int amsm_bases_sample(amsm_ctx* ctx, const uint8_t* domain, size_t domain_len, u
  *                          (0, 0) (the ABI's identity), or none of the rules below applies
  *     1  non-canonical     the integer held in the limbs of x or of y is >= p (the words as they arrive, before any conversion)
  *     2  not on the curve  y^2 != x^3 + b
- *     3  outside the prime-order subgroup   [r]P != O -- BLS12-381 G1 only (cofactor about 2^126); Pallas, Vesta, BN254 G1 and Grumpkin have
+ *     3  outside the prime-order subgroup   [r]P != O -- BLS12-381 G1 (cofactor about 2^126) and BLS12-377 G1 (about 2^125); Pallas, Vesta, BN254 G1 and Grumpkin have
  *                          cofactor 1 and never report 3
  * report[0..2]: the number of points of status 1, 2 and 3; report[3]: the index of the first point whose status is not 0 (n when
  * there is none).  n == 0: AMSM_OK and an all-zero report.  What `GroupAffine::deserialize`'s checks (ark-ec ^0.2.0, ext) do for
@@ -482,7 +485,7 @@ int amsm_fr_from_mont(int curve, const uint64_t* a_mont, size_t n, uint64_t* out
  * assembled from these in include/amsm_serialize.hpp.  PARITY UNPINNED (accumulation_amd/csrc/host_serialize.h).
  *   field element : canonical integer, little-endian, 32 bytes (Fr of every curve)
  *   point         : compressed = x with 2 flag bits in the top of the last byte (bit 7: y is the larger root, bit 6:
- *                   infinity) -- 33 bytes (Pallas, Vesta) / 32 (BN254 G1, Grumpkin: 254 + 2 bits) / 48 (BLS12-381 G1); uncompressed = x | y+flags -- 65 / 64 / 96 bytes.
+ *                   infinity) -- 33 bytes (Pallas, Vesta) / 32 (BN254 G1, Grumpkin: 254 + 2 bits) / 48 (BLS12-381 G1, BLS12-377 G1: 377 + 2 bits); uncompressed = x | y+flags -- 65 / 64 / 96 bytes.
  * Deserialisation returns AMSM_E_INVALID_ARG for a non-canonical integer, an x without a point, a point off the curve or
  * outside the prime-order subgroup, or both flag bits set. */
 size_t amsm_fr_serialized_size(int curve);
@@ -506,7 +509,7 @@ void amsm_poseidon_free(amsm_sponge* s);
 /* `fork(domain)`: a clone that absorbed (domain.len() as u64 LE || domain) as a byte string. */
 int amsm_poseidon_fork(const amsm_sponge* s, const uint8_t* domain, size_t n, amsm_sponge** out);
 /* absorb: native elements (base field, Montgomery); one usize / bool / Option tag; a byte string (31-byte LE chunks for
- * Pallas, Vesta, BN254 and Grumpkin, 47 for BLS12-381, one element each); affine points (x, y, infinity each; a flagged identity absorbs as 0, 1, 1 whatever
+ * Pallas, Vesta, BN254 and Grumpkin, 47 for BLS12-381 and BLS12-377, one element each); affine points (x, y, infinity each; a flagged identity absorbs as 0, 1, 1 whatever
  * xy_mont holds: ark-ec ^0.2.0's `GroupAffine::zero()`). */
 int amsm_poseidon_absorb_native(amsm_sponge* s, const uint64_t* fq_mont, size_t n);
 int amsm_poseidon_absorb_u64(amsm_sponge* s, uint64_t v);

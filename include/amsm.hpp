@@ -44,6 +44,7 @@ inline CurveInfo curve_info(int curve) {
     case AMSM_VESTA: return {4, 18, 15};         // Pallas's (same limb shape; not measured separately)
     case AMSM_BN254_G1: return {4, 18, 15};      // Pallas's (same limb count; not measured)
     case AMSM_GRUMPKIN: return {4, 18, 15};      // Pallas's (same limb count; not measured)
+    case AMSM_BLS12_377_G1: return {6, 16, 15};  // BLS12-381's (same limb shape; not measured)
     default: return {0, 99, 99};
   }
 }

@@ -6,13 +6,20 @@
 #include <vector>
 #include "ec.h"
 using namespace amsm;
-// Bn254FqU / GrumpkinFqU with the other CHAIN setting (fpu.h: u_opaque), so that ONE run decides it: same tables, same kernels
+// Bn254FqU / GrumpkinFqU / Bls12377FqU with the other CHAIN setting (fpu.h: u_opaque), so that ONE run decides it: same tables, same kernels
 struct Bn254FqUOther : Bn254FqU {
   static constexpr bool CHAIN = !Bn254FqU::CHAIN;
 };
 struct GrumpkinFqUOther : GrumpkinFqU {
   static constexpr bool CHAIN = !GrumpkinFqU::CHAIN;
 };
+struct Bls12377FqUOther : Bls12377FqU {
+  static constexpr bool CHAIN = !Bls12377FqU::CHAIN;
+};
+namespace amsm {
+template <>
+struct HasTwoTorsion<Bls12377FqUOther> : HasTwoTorsion<Bls12377FqU> {};
+}  // namespace amsm
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 
 template <class P, int MODE, int MINW = 1>
@@ -93,6 +100,13 @@ int main() {
     run<Bls12381FqU, 0>("bls12-381 14x28 fe_mul", w, 1000, 1, d_out);
     run<Bls12381FqU, 4>("bls12-381 14x28 fe_sqr", w, 1000, 1, d_out);
     run<Bls12381FqU, 3>("bls12-381 14x28 xyzz_madd", w, 200, 1, d_out);
+    run<Bls12377Fq, 0>("bls12-377 fe_mul (asm)", w, 1000, 1, d_out);
+    run<Bls12377FqU, 0>(Bls12377FqU::CHAIN ? "bls12-377 14x28 fe_mul (chain)" : "bls12-377 14x28 fe_mul (no chain)", w, 1000, 1, d_out);
+    run<Bls12377FqU, 4>(Bls12377FqU::CHAIN ? "bls12-377 14x28 fe_sqr (chain)" : "bls12-377 14x28 fe_sqr (no chain)", w, 1000, 1, d_out);
+    run<Bls12377FqU, 3>(Bls12377FqU::CHAIN ? "bls12-377 14x28 xyzz_madd (chain)" : "bls12-377 14x28 xyzz_madd (no chain)", w, 200, 1, d_out);
+    run<Bls12377FqUOther, 0>(Bls12377FqUOther::CHAIN ? "bls12-377 14x28 fe_mul (chain)" : "bls12-377 14x28 fe_mul (no chain)", w, 1000, 1, d_out);
+    run<Bls12377FqUOther, 4>(Bls12377FqUOther::CHAIN ? "bls12-377 14x28 fe_sqr (chain)" : "bls12-377 14x28 fe_sqr (no chain)", w, 1000, 1, d_out);
+    run<Bls12377FqUOther, 3>(Bls12377FqUOther::CHAIN ? "bls12-377 14x28 xyzz_madd (chain)" : "bls12-377 14x28 xyzz_madd (no chain)", w, 200, 1, d_out);
   }
   return 0;
 }

@@ -33,6 +33,12 @@ field("Bn254Fq", 8, 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D8
 field("Bn254Fr", 8, 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001)
 field("GrumpkinFq", 8, 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001)  # = BN254 Fr
 field("GrumpkinFr", 8, 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47)  # = BN254 Fq
+field("Bls12377Fq", 12, 0x1AE3A4617C510EAC63B05C06CA1493B1A22D9F300F5138F1EF3622FBA094800170B5D44300000008508C00000000001)
+field("Bls12377Fr", 8, 0x12AB655E9A2CA55660B44D1E5C37B00159AA76FED00000010A11800000000001)
+
+# fields whose functions are appended BEHIND the sums of products of the fields above: a curve added now adds lines at the end of the
+# header and moves none of the existing ones
+APPENDED = ("Bls12377Fq", "Bls12377Fr")
 
 MAX_TERMS = 11  # terms per asm statement (operand limit 30: 2*terms + acc + c2 + 3 sgpr temps)
 
@@ -183,6 +189,8 @@ def main():
     hdr.append("#pragma once")
     hdr.append("namespace amsm {")
     for name in FIELDS:
+        if name in APPENDED:
+            continue
         hdr.append(gen_twin(name, twin_of(name)) if twin_of(name) else gen_field(name))
         hdr.append("")
     # the scalar-field vector kernels (vec_kernels.h).  GrumpkinFr's are generated under its own name: its twin is a base field only,
@@ -191,6 +199,12 @@ def main():
         for T in (2, 3):
             hdr.append(gen_field(name, T))
             hdr.append("")
+    for name in APPENDED:
+        hdr.append(gen_twin(name, twin_of(name)) if twin_of(name) else gen_field(name))
+        hdr.append("")
+    for T in (2, 3):  # BLS12-377's scalar field; its base field is no curve's scalar field and gets none
+        hdr.append(gen_field("Bls12377Fr", T))
+        hdr.append("")
     hdr.append("}  // namespace amsm")
     sys.stdout.write("\n".join(hdr) + "\n")
 

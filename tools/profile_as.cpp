@@ -8,7 +8,7 @@
 // configs 4, 5) get the same treatment here.
 //
 //   profile_as <scheme: trivial_pc_as | ipa_pc_as | hp_as | r1cs_nark_as | all> <log_min> <log_max>
-//              [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] [--curve 0|1|2|4|6] [--constant] [--uniform] [--no-roundtrip]
+//              [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] [--curve 0|1|2|4|6|8] [--constant] [--uniform] [--no-roundtrip]
 //              [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--transparent DOMAIN]
 //   --transparent DOMAIN  every committer key is a transparent one over DOMAIN (amsm.h amsm_bases_sample, the setup_transparent of
 //                the headers) instead of the seeded synthetic key; the Python mirrors take the same key from setup(domain=...).
@@ -77,7 +77,7 @@ static double timed_proves(const Opt& o, F&& prove_once);
 
 // ark_std::test_rng() stand-in: a fixed stream of 254-bit integers, reduced mod r -- the schemes' rng returns CANONICAL scalars
 // (amsm_hp_as.hpp: Rng).  Every 255-bit r exceeds the stream, so nothing is subtracted there; BN254's and Grumpkin's r lie between 2^253 and 2^254:
-// one conditional subtraction (the Python mirror takes the same integers mod r).
+// one conditional subtraction; BLS12-377's between 2^252 and 2^253: up to three (the Python mirror takes the same integers mod r).
 struct HarnessRng {
   uint64_t seed, i = 0;
   Fr r_minus_1{};
@@ -99,21 +99,21 @@ struct HarnessRng {
     }
     i++;
     x[3] &= (1ull << 62) - 1;
-    bool above = false;  // x > r - 1 ?
-    for (int k = 3; k >= 0; k--)
-      if (x[k] != r_minus_1[k]) {
-        above = x[k] > r_minus_1[k];
-        break;
-      }
-    if (above) {  // x -= r, as x - (r - 1) - 1
-      unsigned __int128 borrow = 1;
+    for (;;) {
+      bool above = false;  // x > r - 1 ?
+      for (int k = 3; k >= 0; k--)
+        if (x[k] != r_minus_1[k]) {
+          above = x[k] > r_minus_1[k];
+          break;
+        }
+      if (!above) return x;
+      unsigned __int128 borrow = 1;  // x -= r, as x - (r - 1) - 1
       for (int k = 0; k < 4; k++) {
         unsigned __int128 d = (unsigned __int128)x[k] - r_minus_1[k] - borrow;
         x[k] = (uint64_t)d;
         borrow = (uint64_t)(d >> 64) ? 1 : 0;
       }
     }
-    return x;
   }
 };
 
@@ -493,7 +493,7 @@ int main(int argc, char** argv) {
   Opt o;
   if (argc < 4) {
     fprintf(stderr, "usage: %s <scheme|all> <log_min> <log_max> [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] "
-                    "[--curve 0|1|2|4|6] [--constant] [--uniform] [--no-roundtrip] [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--replicate-below L] [--transparent DOMAIN]\n", argv[0]);
+                    "[--curve 0|1|2|4|6|8] [--constant] [--uniform] [--no-roundtrip] [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--replicate-below L] [--transparent DOMAIN]\n", argv[0]);
     return 2;
   }
   o.scheme = argv[1];

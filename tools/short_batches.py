@@ -1,7 +1,7 @@
 """Batches the size a prover issues (2, 3, 6 MSMs per call) next to the 40-MSM batches of tools/mid_sizes.py: ms per CALL.
 `AMSM_LIB_PATH` selects another build for an A/B.  Not a test.
 
-    python tools/short_batches.py [--curve pallas|bls12_381|vesta|bn254|grumpkin] [--k 1,2,3,6,40] [--jsonl FILE --label NAME] [--scale S] [LOG2 ...]
+    python tools/short_batches.py [--curve pallas|bls12_381|vesta|bn254|grumpkin|bls12_377] [--k 1,2,3,6,40] [--jsonl FILE --label NAME] [--scale S] [LOG2 ...]
 
 --jsonl appends one record per (size, k) to FILE, tagged with --label (which build ran): what profiles/bps_batch_ab.jsonl holds."""
 import argparse
@@ -16,7 +16,7 @@ import torch  # noqa: F401,E402
 from accumulation_amd import CommitterKey, Context, VariableBaseMSM, ffi  # noqa: E402
 
 CURVES = {"pallas": ffi.AMSM_PALLAS, "bls12_381": ffi.AMSM_BLS12_381_G1, "vesta": ffi.AMSM_VESTA, "bn254": ffi.AMSM_BN254_G1,
-          "grumpkin": ffi.AMSM_GRUMPKIN}
+          "grumpkin": ffi.AMSM_GRUMPKIN, "bls12_377": ffi.AMSM_BLS12_377_G1}
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--curve", default="pallas", choices=sorted(CURVES))
