@@ -370,6 +370,22 @@ int vec_random(uint64_t seed, size_t n, int mont, void* out) {
   });
   return AMSM_OK;
 }
+// amsm_vec_sample: the text of blind.h that k_vec_sample runs
+template <class Fq, class Fr>
+int vec_sample(int curve, const uint8_t* key, uint32_t stream, uint64_t first, size_t n, int mont, void* out) {
+  const blind::Key k = blind::key_words(key);
+  par_for(n, 1024, [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; i++) {
+      u32 w[8];
+      blind::scalar<Fr>(k, (u32)curve, stream, first + i, w);
+      host::HFe<Fr> s;
+      memcpy(s.v, w, 32);
+      if (mont) s = host::h_to_mont<Fr>(s);
+      st<Fr>(out, i, s);
+    }
+  });
+  return AMSM_OK;
+}
 template <class Fq, class Fr>
 int vec_hadamard(const void* a, const void* b, void* out, size_t n) {
   par_for(n, 4096, [&](size_t lo, size_t hi) {

@@ -101,6 +101,7 @@ int amsm_ctx_create(amsm_ctx** out, int curve, int device_id, void* stream) {
   if (const char* e = getenv("AMSM_SHARE_BUCKETS")) c->share_buckets = atoi(e) != 0;
   if (const char* e = getenv("AMSM_HOST_HALVES")) c->host_halves = atoi(e) != 0;
   if (const char* e = getenv("AMSM_SUBGROUP_LADDER")) c->subgroup_ladder = atoi(e) == 2 ? 2 : 1;
+  if (const char* e = getenv("AMSM_VEC_SAMPLE_FORM")) c->vec_sample_form = std::max(0, std::min(2, atoi(e)));
   *out = c;
   return AMSM_OK;
 }

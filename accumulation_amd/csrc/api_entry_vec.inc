@@ -201,6 +201,17 @@ int amsm_vec_random(amsm_ctx* c, uint64_t seed, size_t n, int mont, void* d_out)
   return AMSM_OK;
 }
 
+int amsm_vec_sample(amsm_ctx* c, const uint8_t key[32], uint32_t stream, uint64_t first, size_t n, int mont, void* d_out) {
+  if (!c || !key || !d_out || n >= (1ull << 32) || first + n < first) return AMSM_E_INVALID_ARG;
+  if (c->host_only) return CPU_CALL(c, vec_sample, c->curve, key, stream, first, n, mont, d_out);
+  TRY(bind_device(c));
+  if (!n) return AMSM_OK;
+  const blind::Key k = blind::key_words(key);  // a kernel argument: the key is staged in no buffer and printed nowhere
+  DISPATCH_DO(c, launch_vec_sample<Fr>(c->stream, (u32*)d_out, k, (u32)c->curve, stream, first, (u32)n, mont, c->vec_sample_form));
+  HIP_TRY(hipGetLastError());
+  return AMSM_OK;
+}
+
 int amsm_vec_hadamard(amsm_ctx* c, const void* d_a, const void* d_b, void* d_out, size_t n) {
   if (!c || (n && (!d_a || !d_b || !d_out)) || n >= (1ull << 32)) return AMSM_E_INVALID_ARG;
   if (c->host_only) return CPU_CALL(c, vec_hadamard, d_a, d_b, d_out, n);

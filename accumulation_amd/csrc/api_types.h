@@ -250,6 +250,7 @@ struct amsm_ctx {
   DevBuf oneshot_table, oneshot_inf;
   DevBuf check_ws;      // amsm_points_check[_device]: counters, status bytes and the uploaded piece (api_keys.inc)
   int subgroup_ladder = 1;  // AMSM_SUBGROUP_LADDER: the shape of the BLS12-381 subgroup ladder (points_check_kernels.h; 2: the A/B's other side)
+  int vec_sample_form = 0;  // AMSM_VEC_SAMPLE_FORM: the kernel form of amsm_vec_sample (launch.h: launch_vec_sample; 0: the one that ships)
   DevBuf xyzz_scratch;  // unconverted sums of large key folds / precompute levels (launch.h: batch_affine_pays)
   // two-valued device vectors (api_pipeline.inc: msm_multi_split_xyzz): every scalar is 0 or one value v -> v * (sum of the
   // generators with a non-zero scalar), on its own stream beside the batch's other MSMs.  AMSM_TWO_VALUED=0 turns it off.

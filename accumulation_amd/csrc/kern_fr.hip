@@ -448,6 +448,18 @@ void launch_tv_probe(hipStream_t st, const u32* scalars, u32 n, u32* out16, cons
     hipLaunchKernelGGL((k_vec_random<FR>), dim3(cdiv_(n, 256)), dim3(256), 0, st, out, seed, n, mont);               \
   }                                                                                                                  \
   template <>                                                                                                        \
+  void launch_vec_sample<FR>(hipStream_t st, u32* out, const blind::Key& key, u32 curve_id, u32 stream, u64 first,   \
+                             u32 n, int mont, int form) {                                                            \
+    static_assert(VEC_SAMPLE_TILE == 1024u || VEC_SAMPLE_TILE == 4096u, "one of the two instantiated tiles");        \
+    if (form == 0) form = VEC_SAMPLE_TILE == 1024u ? 1 : 2;                                                          \
+    if (form == 1)                                                                                                   \
+      hipLaunchKernelGGL((k_vec_sample<FR, 1024>), dim3(cdiv_(n, 1024)), dim3(256), 0, st, out, key, curve_id,       \
+                         stream, first, n, mont);                                                                    \
+    else                                                                                                             \
+      hipLaunchKernelGGL((k_vec_sample<FR, 4096>), dim3(cdiv_(n, 4096)), dim3(256), 0, st, out, key, curve_id,       \
+                         stream, first, n, mont);                                                                    \
+  }                                                                                                                  \
+  template <>                                                                                                        \
   void launch_vec_hadamard<FR>(hipStream_t st, const u32* a, const u32* b, u32* out, u32 n) {                        \
     hipLaunchKernelGGL((k_vec_hadamard<FR>), dim3(stream_grid(n)), dim3(256), 0, st, a, b, out, n);                  \
   }                                                                                                                  \

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "blind.h"
 #include "msm_select.h"
 #include "msm_types.h"
 
@@ -195,6 +196,11 @@ void launch_skew_probe(hipStream_t st, const u32* scalars, int mont, u32 n, Digi
                        const u32* d_tv_words = nullptr);
 template <class Fr>
 void launch_vec_random(hipStream_t st, u32* out, u64 seed, u32 n, int mont);
+// amsm_vec_sample (vec_kernels.h: k_vec_sample).  form: 0 the form that ships (VEC_SAMPLE_TILE), 1 / 2 tiles of 1024 / 4096 scalars
+// (the A/B of tools/vec_sample_rates.py) -- the same values from every form
+constexpr u32 VEC_SAMPLE_TILE = 1024;
+template <class Fr>
+void launch_vec_sample(hipStream_t st, u32* out, const blind::Key& key, u32 curve_id, u32 stream, u64 first, u32 n, int mont, int form);
 template <class Fr>
 void launch_vec_hadamard(hipStream_t st, const u32* a, const u32* b, u32* out, u32 n);
 template <class Fr>

@@ -10,6 +10,7 @@
 #pragma once
 #include "fp.h"
 #include "msm_types.h"
+#include "blind.h"
 #include "rng.h"
 
 namespace amsm {
@@ -599,6 +600,65 @@ __global__ void __launch_bounds__(256) k_vec_random(u32* __restrict__ out, u64 s
   rng_scalar_fr<Fr>(seed, i, s.v);
   if (mont) s = fe_to_mont<Fr>(s);
   fe_store<Fr>(out + (size_t)i * 8, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// amsm_vec_sample: out[j] = scalar first + j of the keyed stream "amsm-blind-v1" (blind.h), j < n.
+// A lane that loops until its own scalar is accepted makes its wave wait for the unluckiest of 64 (Pallas accepts half its
+// candidates: about 7 hashes where the mean is 2).  So a 256-lane workgroup owns a tile of T consecutive scalars and compacts its
+// rejects: pass t hashes candidate t of every scalar still pending; accepted lanes convert and store, rejected lanes append the
+// scalar's tile-local index to the next pending list in LDS (ballot / mbcnt prefix per wave, one LDS counter per list; two lists of
+// T 16-bit indices used alternately), and pass t + 1 hands that list out densely.  Every entry of a list is at the same attempt, so
+// a list carries no t; pass 0 needs no list.  blind::attempt accepts whatever it is given at t = MAX_ATTEMPTS - 1, so the lists run
+// empty.  A value depends on (key, stream, i) only -- never on list order, T or the grid.
+// T = 1024 ships (launch.h: VEC_SAMPLE_TILE): at 2^18 scalars 4096-scalar tiles leave three quarters of the CUs idle (1.6 - 1.8 x
+// slower), at 2^20 they are at most 13 % faster; the lane-per-scalar loop the A/B began with was 1.3 - 1.9 x slower than T = 1024
+// everywhere and is gone (profiles/vec_sample_rates.jsonl).
+// ---------------------------------------------------------------------------------------------
+template <class Fr>
+AMSM_DEV void vec_sample_store(u32* __restrict__ out, size_t j, Fe<Fr> s, int mont) {
+  if (mont) s = fe_to_mont<Fr>(s);
+  fe_store<Fr>(out + j * 8, s);
+}
+template <class Fr, u32 T>
+__global__ void __launch_bounds__(256) k_vec_sample(u32* __restrict__ out, blind::Key key, u32 curve_id, u32 stream, u64 first, u32 n,
+                                                     int mont) {
+  static_assert(T % 256u == 0 && T <= 65536u, "whole rounds of the workgroup; 16-bit tile-local indices");
+  __shared__ uint16_t list[2][T];
+  __shared__ u32 cnt[2];
+  const u32 tid = threadIdx.x;
+  const u32 base = blockIdx.x * T;  // < n
+  if (tid == 0) cnt[0] = cnt[1] = 0;
+  __syncthreads();
+  u32 pending = min(T, n - base);
+  u32 cur = 1;  // pass t reads list[cur] (t > 0) and appends to list[cur ^ 1]
+  for (u32 t = 0; pending; t++) {
+#pragma unroll 1
+    for (u32 j0 = 0; j0 < pending; j0 += 256u) {  // uniform bounds: whole waves reach the ballot
+      const u32 j = j0 + tid;
+      const bool live = j < pending;
+      const u32 idx = live ? (t ? (u32)list[cur][j] : j) : 0u;
+      bool again = false;
+      if (live) {
+        Fe<Fr> s;
+        again = !blind::attempt<Fr>(key, curve_id, stream, first + base + idx, t, s.v);
+        if (!again) vec_sample_store<Fr>(out, (size_t)base + idx, s, mont);
+      }
+      const u64 mask = __ballot(again);
+      if (mask) {
+        const u32 before = __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
+        u32 at = 0;
+        if (before == 0 && again) at = atomicAdd(&cnt[cur ^ 1], (u32)__popcll(mask));  // the first rejected lane of the wave
+        at = __shfl(at, __ffsll((unsigned long long)mask) - 1);
+        if (again) list[cur ^ 1][at + before] = (uint16_t)idx;  // at + before < pending <= T
+      }
+    }
+    if (tid == 0) cnt[cur] = 0;  // read as `pending` before this pass began; the next pass appends to it
+    __syncthreads();
+    pending = cnt[cur ^ 1];
+    __syncthreads();  // everyone has read the count before the pass after next resets it
+    cur ^= 1;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------

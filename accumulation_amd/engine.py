@@ -188,6 +188,16 @@ class Context:
         ffi.check(self._lib.amsm_vec_random(self._h, seed, n, 1 if mont else 0, v.ptr), "amsm_vec_random")
         return v
 
+    def sample_vector(self, key: bytes, stream: int, n: int, mont: bool = True, first: int = 0) -> "FrVector":
+        """Scalars first .. first + n - 1 of stream `stream` of the keyed derivation "amsm-blind-v1" (amsm_vec_sample): uniform in
+        [0, r), made on the device.  `key`: 32 secret bytes; a (key, stream) pair is used for ONE vector (VectorRng hands them out)."""
+        key = bytes(key)
+        if len(key) != 32:
+            raise ValueError("a key of 32 bytes")
+        v = FrVector(self, n)
+        ffi.check(self._lib.amsm_vec_sample(self._h, key, stream, first, n, 1 if mont else 0, v.ptr), "amsm_vec_sample")
+        return v
+
     # ---- polynomials (coefficient vectors, little-endian in the degree) ----
     def poly_evaluate(self, vectors: Sequence["FrVector"], point_mont: np.ndarray) -> np.ndarray:
         """p_k(point) for every vector in one call (amsm_poly_evaluate_batch) -> (k, 4) uint64, Montgomery."""

@@ -149,6 +149,7 @@ SIGNATURES = {
     "amsm_ipa_jump_fold": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "amsm_msm_oneshot": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, C.c_int, _vp, _vp]),
     "amsm_vec_random": (C.c_int, [_vp, C.c_uint64, _sz, C.c_int, _vp]),
+    "amsm_vec_sample": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, _sz, C.c_int, _vp]),
     "amsm_vec_hadamard": (C.c_int, [_vp, _vp, _vp, _vp, _sz]),
     "amsm_vec_combine": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), _sz, _vp, _vp, _sz, _vp, _sz]),
     "amsm_bases_from_device": (C.c_int, [_vp, _vp, _sz, C.c_uint, C.POINTER(_vp)]),

@@ -116,6 +116,25 @@ class MissingRng(ASError):
     pass
 
 
+class VectorRng:
+    """Where the zk proves take their LONG random vectors from when they are to be made on the device (Context.sample_vector,
+    "amsm-blind-v1"): a 32-byte secret key and the number of the next unused stream.  Every long vector a prove samples takes the
+    next stream number, so a key must not be reused across proves unless the same object (its next_stream) is carried on: the same
+    (key, stream) gives the same vector.  The handful of single scalars of a prove still come from its `rng`."""
+
+    def __init__(self, key: bytes, next_stream: int = 0):
+        key = bytes(key)
+        if len(key) != 32:
+            raise ValueError("a key of 32 bytes")
+        self.key = key
+        self.next_stream = next_stream
+
+    def take_stream(self) -> int:
+        s = self.next_stream
+        self.next_stream += 1
+        return s
+
+
 def _zero_point(ctx):
     return (np.zeros((2 * ctx.fq_limbs,), dtype=np.uint64), True)
 

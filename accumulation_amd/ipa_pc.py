@@ -180,8 +180,10 @@ class InnerProductArgPC:
     # ---- open ---------------------------------------------------------------------------------------
     @classmethod
     def open(cls, ck: CommitterKey, polynomial: FrVector, commitment: Commitment, point: int, rand: int = 0,
-             hiding: bool = False, rng=None) -> Proof:
-        """open_individual_opening_challenges for ONE polynomial with opening challenge 1."""
+             hiding: bool = False, rng=None, vector_rng=None) -> Proof:
+        """open_individual_opening_challenges for ONE polynomial with opening challenge 1.  vector_rng (hiding, optional): a
+        VectorRng -- the d + 1 coefficients of the hiding polynomial are then sampled on the device from its next stream
+        (Context.sample_vector) instead of being drawn from rng one by one and uploaded; rng still gives the single scalars."""
         ctx = ck.comm_key.ctx
         fr = Fr(ctx.curve)
         d = ck.supported_degree()
@@ -199,7 +201,10 @@ class InnerProductArgPC:
         if hiding:
             assert rng is not None
             # random polynomial that vanishes at `point`
-            hp = ctx.upload(fr.to_limbs_many([rng.field() for _ in range(n)]))
+            if vector_rng is not None:
+                hp = ctx.sample_vector(vector_rng.key, vector_rng.take_stream(), n, mont=True)
+            else:
+                hp = ctx.upload(fr.to_limbs_many([rng.field() for _ in range(n)]))
             hv = cls._inner_product(ctx, fr, hp, z)
             hp = combine_vectors(ctx, [hp, ctx.upload(fr.to_limbs_many([(-hv) % fr.r]))], np.stack([one, one]))
             hiding_rand = rng.field()

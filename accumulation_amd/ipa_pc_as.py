@@ -149,7 +149,8 @@ class AtomicASForInnerProductArgPC:
     # ---- prove ------------------------------------------------------------------------------------
     @classmethod
     def prove(cls, pk: ProverKey, inputs: Sequence[InputInstance], old_accumulators: Sequence[InputInstance], rng=None,
-              sponge=None):
+              sponge=None, vector_rng=None):
+        """vector_rng (zk, optional): handed to the hiding opening (IpaPC.open), which samples its hiding polynomial on the device."""
         if sponge is not None:
             raise NotImplementedError("ASForIpaPC is unable to accept sponge objects until IpaPC gets updated to "
                                       "accept them.")  # :566-570
@@ -194,7 +195,7 @@ class AtomicASForInnerProductArgPC:
         ffi.check(ctx._lib.amsm_vec_powers(ctx._h, _ptr(fr.to_limbs(challenge)), poly.n, z.ptr), "amsm_vec_powers")
         evaluation = IpaPC._inner_product(ctx, fr, poly, z)
         ipa_proof = IpaPC.open(ipa_ck, poly, randomized, challenge, proof.commitment_randomness if proof else 0,
-                               hiding=proof is not None, rng=rng)
+                               hiding=proof is not None, rng=rng, vector_rng=vector_rng)
         return Accumulator(InputInstance(randomized, challenge, evaluation, ipa_proof)), proof
 
     # ---- verify (host only apart from nothing: no MSM) -------------------------------------------------

@@ -196,9 +196,11 @@ def compute_challenge(fr: Fr, matrices_hash: bytes, input: Sequence[int], msg: F
 
 
 def prove(ipk: IndexProverKey, input: Sequence[int], witness: FrVector, make_zk: bool,
-          sponge: Optional[CryptographicSponge] = None, rng=None) -> Proof:
+          sponge: Optional[CryptographicSponge] = None, rng=None, vector_rng=None) -> Proof:
     """R1CSNark::prove (:127-332).  input: instance assignment (canonical ints, incl. the leading one);
-    witness: FrVector.  rng (zk only): object with .field()."""
+    witness: FrVector.  rng (zk only): object with .field().  vector_rng (zk, optional): a VectorRng -- the witness-length
+    blinder r is then sampled on the device from its next stream (Context.sample_vector) instead of being drawn from rng scalar
+    by scalar and uploaded; the single scalars still come from rng, in the same order."""
     ctx = ipk.ck.ctx
     fr = Fr(ctx.curve)
     commit = PedersenCommitment.commit
@@ -213,7 +215,10 @@ def prove(ipk: IndexProverKey, input: Sequence[int], witness: FrVector, make_zk:
         compute_challenge(fr, ipk.index_info.matrices_hash, input, first, sponge)  # gamma is squeezed but unused
         return Proof(first, SecondRoundMessage(witness, None))
     assert rng is not None
-    r = ctx.upload(fr.to_limbs_many([rng.field() for _ in range(witness.n)]))  # :168-172
+    if vector_rng is not None:
+        r = ctx.sample_vector(vector_rng.key, vector_rng.take_stream(), witness.n, mont=True)
+    else:
+        r = ctx.upload(fr.to_limbs_many([rng.field() for _ in range(witness.n)]))  # :168-172
     zeros = ctx.upload(np.zeros((len(input), 4), dtype=np.uint64))
     r_a = matrix_vec_mul(ipk.a, zeros, r)
     r_b = matrix_vec_mul(ipk.b, zeros, r)

@@ -445,6 +445,24 @@ int amsm_dev_download(amsm_ctx* ctx, void* h_dst, const void* d_src, size_t byte
 /* Fill d_out with n synthetic scalars of stream `seed` (oracle/pyref.py:rng_scalar), canonical
  * integers (mont == 0) or the Montgomery form of the same integers (mont != 0). */
 int amsm_vec_random(amsm_ctx* ctx, uint64_t seed, size_t n, int mont, void* d_out);
+/* Blinding vectors on the device: d_out[j] = scalar first + j (j < n < 2^32) of stream `stream` under the 32-byte `key`, uniform in
+ * [0, r), as the canonical integer (mont == 0) or the Montgomery form of the same integer (mont != 0).  The derivation
+ * "amsm-blind-v1" (csrc/blind.h): scalar i is the first accepted candidate t = 0, 1, .. of
+ *     M(i, t) = key[32] || "amsm-blind-v1" (13 bytes) || u8 curve_id || u16_le t || u32_le stream || u64_le i       (60 bytes)
+ *     cand    = BLAKE2s-256(M) as a little-endian integer, masked to bitlen(r) bits;  accepted iff cand < r
+ * (every candidate is accepted with probability r / 2^bitlen(r) >= 1/2; after 128 rejections, probability <= 2^-128, the value is
+ * candidate 127 minus r).  A value depends on (curve, key, stream, i) only: `first` lets a caller fill a long vector in pieces, or
+ * from several contexts or backends, and get the same vector.  Stream-ordered on the context's stream like the other vector
+ * kernels; the call blocks for nothing.  The key is passed to the kernel as an argument: it is staged in no buffer that outlives
+ * the call and is never printed under AMSM_DEBUG.  AMSM_E_INVALID_ARG: a NULL ctx, key or d_out, n >= 2^32, first + n past 2^64;
+ * n == 0 is AMSM_OK and launches nothing.  On a multi-device context it writes where amsm_vec_random writes.
+ *   - The key is a SECRET: whoever knows it knows every blinder made from it.  Take it from the system's generator.
+ *   - Streams never repeat under a key: two vectors sampled with the same (key, stream) are the same vector, and two proofs blinded
+ *     with one of them leak their witnesses' difference.  One key per prove, or carry the stream counter on (VectorRng).
+ *   - Not an arkworks format: no RngCore of the reference produces these values.
+ * (AMSM_VEC_SAMPLE_FORM=1|2 at context creation picks the kernel's tile -- 1024 scalars, the default, or 4096 -- for the A/B of
+ * tools/vec_sample_rates.py; the values are the same.) */
+int amsm_vec_sample(amsm_ctx* ctx, const uint8_t key[32], uint32_t stream, uint64_t first, size_t n, int mont, void* d_out);
 
 /* out[i] = value for i < n  (`vec![x; len]`, src/hp_as/mod.rs:189-190).  value_mont: 4 u64. */
 int amsm_vec_fill(amsm_ctx* ctx, const uint64_t* value_mont, size_t n, void* d_out);

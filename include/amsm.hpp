@@ -121,6 +121,12 @@ class FrVector {
     check(amsm_vec_random(ctx.get(), seed, n, mont ? 1 : 0, v.p_), "amsm_vec_random");
     return v;
   }
+  // amsm_vec_sample: scalars first .. first + n - 1 of stream `stream` under the 32-byte secret `key` ("amsm-blind-v1"), uniform in [0, r)
+  static FrVector sample(Context& ctx, const std::array<uint8_t, 32>& key, uint32_t stream, size_t n, bool mont, uint64_t first = 0) {
+    FrVector v(ctx, n);
+    check(amsm_vec_sample(ctx.get(), key.data(), stream, first, n, mont ? 1 : 0, v.p_), "amsm_vec_sample");
+    return v;
+  }
   ~FrVector() {
     if (p_) amsm_dev_free(ctx_->get(), p_);
   }

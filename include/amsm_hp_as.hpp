@@ -321,6 +321,15 @@ inline std::shared_ptr<FrVector> filled(Context& ctx, const Fr& value_mont, size
 
 // `rng`: empty = MakeZK::Disabled, else returns CANONICAL scalars < r (MakeZK::Enabled(rng)).
 using Rng = std::function<Fr()>;
+// Where the zk proves take their LONG random vectors from when they are to be made on the device (FrVector::sample, the keyed
+// derivation "amsm-blind-v1" of amsm_vec_sample): a 32-byte SECRET key and the number of the next unused stream.  Every long vector
+// a prove samples takes the next stream number, and the same (key, stream) gives the same vector: a caller must not reuse a key
+// across proves unless it carries next_stream on (pass the same object again).  The single scalars still come from `rng`.
+struct VectorRng {
+  std::array<uint8_t, 32> key;
+  uint32_t next_stream = 0;
+  uint32_t take_stream() { return next_stream++; }
+};
 
 template <class Sponge = Sha256Sponge>
 class ASForHadamardProducts {

@@ -294,9 +294,10 @@ struct InnerProductArgPC {
     proof.c = c[0];
   }
 
-  // open_individual_opening_challenges for ONE polynomial with opening challenge 1
+  // open_individual_opening_challenges for ONE polynomial with opening challenge 1.  vrng (hiding, optional): the hiding polynomial's
+  // d + 1 coefficients are sampled on the device from its next stream -- no host vector, no upload; rng still gives the single scalars.
   static Proof open(const CommitterKey& ck, const FrVector& polynomial, const Commitment& commitment, const Fr& point, const Fr& rand,
-                    bool hiding, const hp_as::Rng& rng) {
+                    bool hiding, const hp_as::Rng& rng, hp_as::VectorRng* vrng = nullptr) {
     const amsm::CommitterKey& key = *ck.comm_key;
     Context& ctx = key.ctx();
     FrX fr(amsm_ctx_curve(ctx.get()));
@@ -314,10 +315,14 @@ struct InnerProductArgPC {
     if (hiding) {
       // d + 1 random coefficients: drawn in canonical form, uploaded as they are and taken to Montgomery form by ONE device kernel
       // (a Montgomery product with R^2: x R^2 R^-1 = x R) -- one amsm_fr_to_mont call per coefficient was 1.6 ms of a 2^16 prove
-      std::vector<Fr> hp_canon(n);
-      for (size_t i = 0; i < n; i++) hp_canon[i] = rng();
-      FrVector hp_raw(ctx, hp_canon);
-      FrVector hp0 = combine2(ctx, hp_raw.ptr(), n, fr.to_mont(one), hp_raw.ptr(), 0, zero, n);
+      auto draw_hp = [&]() {
+        if (vrng) return FrVector::sample(ctx, vrng->key, vrng->take_stream(), n, /*mont=*/true);
+        std::vector<Fr> hp_canon(n);
+        for (size_t i = 0; i < n; i++) hp_canon[i] = rng();
+        FrVector hp_raw(ctx, hp_canon);
+        return combine2(ctx, hp_raw.ptr(), n, fr.to_mont(one), hp_raw.ptr(), 0, zero, n);
+      };
+      FrVector hp0 = draw_hp();
       Fr hv = inner_product(ctx, hp0.ptr(), z.ptr(), n);
       FrVector shift(ctx, std::vector<Fr>{fr.neg(hv)});  // random polynomial that vanishes at `point`
       FrVector hp = combine2(ctx, hp0.ptr(), n, one, shift.ptr(), 1, one, n);
@@ -558,7 +563,7 @@ class AtomicASForInnerProductArgPC {
 
   // ---- prove (:555-676) ----------------------------------------------------------------------------------------
   static std::pair<Accumulator, Proof> prove(const ProverKey& pk, std::vector<InputInstance> ins, const std::vector<InputInstance>& olds,
-                                             const hp_as::Rng& rng = hp_as::Rng()) {
+                                             const hp_as::Rng& rng = hp_as::Rng(), hp_as::VectorRng* vrng = nullptr) {
     const CommitterKey& ipa_ck = pk.ipa_ck;
     Context& ctx = ipa_ck.comm_key->ctx();
     FrX fr(amsm_ctx_curve(ctx.get()));
@@ -630,7 +635,7 @@ class AtomicASForInnerProductArgPC {
     Fr evaluation = Ipa::inner_product(ctx, poly->ptr(), z.ptr(), poly->len());
     mark("evaluation");
     ipa_pc::Proof ipa_proof = Ipa::open(ipa_ck, *poly, comb.randomized, challenge, proof ? proof->commitment_randomness : fr.zero(),
-                                        proof.has_value(), rng);
+                                        proof.has_value(), rng, vrng);
     mark("open");
     return {InputInstance{comb.randomized, challenge, evaluation, ipa_proof}, proof};
   }

@@ -227,9 +227,10 @@ struct R1CSNark {
   }
 
   // prove (:127-332).  input: instance assignment, canonical, incl. the leading one; witness: device vector (Montgomery).
-  // rng: empty = no zk, else returns canonical scalars.
+  // rng: empty = no zk, else returns canonical scalars.  vrng (zk, optional): the witness-length blinder r is sampled on the device
+  // from its next stream -- no host vector, no upload; the single scalars still come from rng, in the same order.
   static Proof prove(const IndexProverKey& ipk, const std::vector<Fr>& input, std::shared_ptr<FrVector> witness,
-                     const hp_as::Rng& rng = hp_as::Rng(), Sponge sponge = Sponge()) {
+                     const hp_as::Rng& rng = hp_as::Rng(), Sponge sponge = Sponge(), hp_as::VectorRng* vrng = nullptr) {
     const CommitterKey& ck = *ipk.ck;
     Context& ctx = ck.ctx();
     FrOps fr{amsm_ctx_curve(ctx.get())};
@@ -247,10 +248,14 @@ struct R1CSNark {
     }
     // :168-172 -- drawn in canonical form and taken to Montgomery form on the device (one Montgomery product with R^2 per element,
     // one kernel: a witness-length loop of single-element amsm_fr_to_mont calls was ~25 ns per variable on the host)
-    std::vector<Fr> r_canon(witness->len());
-    for (size_t i = 0; i < r_canon.size(); i++) r_canon[i] = rng();
-    FrVector r_raw(ctx, r_canon);
-    FrVector r = hp_as::combine_vectors(ctx, {&r_raw}, {fr.to_mont(fr.one())});
+    auto draw_r = [&]() {
+      if (vrng) return FrVector::sample(ctx, vrng->key, vrng->take_stream(), witness->len(), /*mont=*/true);
+      std::vector<Fr> r_canon(witness->len());
+      for (size_t i = 0; i < r_canon.size(); i++) r_canon[i] = rng();
+      FrVector r_raw(ctx, r_canon);
+      return hp_as::combine_vectors(ctx, {&r_raw}, {fr.to_mont(fr.one())});
+    };
+    FrVector r = draw_r();
     FrVector zeros(ctx, std::vector<Fr>(input.size(), fr.zero()));
     FrVector r_a = ipk.a->vec_mul(zeros, r), r_b = ipk.b->vec_mul(zeros, r), r_c = ipk.c->vec_mul(zeros, r);
     Fr a_bl = fr.to_mont(rng()), b_bl = fr.to_mont(rng()), c_bl = fr.to_mont(rng());

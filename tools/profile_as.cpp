@@ -9,7 +9,10 @@
 //
 //   profile_as <scheme: trivial_pc_as | ipa_pc_as | hp_as | r1cs_nark_as | all> <log_min> <log_max>
 //              [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] [--curve 0|1|2|4|6|8] [--constant] [--uniform] [--no-roundtrip]
-//              [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--transparent DOMAIN]
+//              [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--transparent DOMAIN] [--device-blinders KEYHEX]
+//   --device-blinders KEYHEX  (64 hex digits: a 32-byte key) the zk proves of r1cs_nark_as, nark and ipa_pc_as take their long random
+//                vectors -- the NARK's witness-length blinder, the hiding polynomial of an opening -- from one VectorRng under this
+//                key (amsm_vec_sample: made on the device, no host loop, no upload); the JSON line gains "device_blinders": true.
 //   --transparent DOMAIN  every committer key is a transparent one over DOMAIN (amsm.h amsm_bases_sample, the setup_transparent of
 //                the headers) instead of the seeded synthetic key; the Python mirrors take the same key from setup(domain=...).
 //   --cold       no warm-up repetitions (the prove before the timed ones, the decide before the timed one): the CPU legs of
@@ -51,6 +54,15 @@ struct Opt {
   std::string dump;
   bool transparent = false;  // --transparent DOMAIN
   std::string domain;
+  bool device_blinders = false;  // --device-blinders KEYHEX: the zk proves sample their long random vectors on the device (VectorRng)
+  std::array<uint8_t, 32> blind_key{};
+};
+// the VectorRng of one workload: every zk prove of it takes the next stream under the one key
+struct Blinders {
+  hp_as::VectorRng vr;
+  bool on;
+  Blinders(const Opt& o, bool zk) : vr{o.blind_key, 0}, on(o.device_blinders && zk) {}
+  hp_as::VectorRng* get() { return on ? &vr : nullptr; }
 };
 
 static Context make_context(const Opt& o) {
@@ -131,11 +143,12 @@ static void report(const Opt& o, const char* scheme, int log_size, const char* s
   printf("JSON {\"kind\": \"profile_as\", \"scheme\": \"%s\", \"%s\": %d, \"shape\": \"%s\", \"zk\": %s, \"sponge\": \"%s\", "
          "\"index_ms\": %.3f, \"prove_ms\": %.3f, \"verify_ms\": %.3f, \"decide_ms\": %.3f, \"accumulations_per_s\": %.3f, "
          "\"accumulator_bytes\": %zu, \"instance_bytes\": %zu, \"witness_bytes\": %zu, \"verified\": %s, \"decided\": %s, "
-         "\"serialize_roundtrip_decides\": %s, \"reps\": %d, \"curve\": %d, \"host_backend\": %s, \"host_pool_threads\": %d}\n",
+         "\"serialize_roundtrip_decides\": %s, \"reps\": %d, \"curve\": %d, \"host_backend\": %s, \"host_pool_threads\": %d%s}\n",
          scheme, size_name, log_size, shape, zk ? "true" : "false", o.sponge.c_str(), r.index_ms, r.prove_ms, r.verify_ms,
          r.decide_ms, 1000.0 / r.prove_ms, r.acc_bytes, r.inst_bytes, r.wit_bytes, r.verified ? "true" : "false",
          r.decided ? "true" : "false", !o.roundtrip ? "null" : (r.roundtrip ? "true" : "false"), o.reps, o.curve,
-         (o.devices.size() < 2 && o.device < 0) ? "true" : "false", amsm_host_threads());
+         (o.devices.size() < 2 && o.device < 0) ? "true" : "false", amsm_host_threads(),
+         o.device_blinders ? ", \"device_blinders\": true" : "");
   fflush(stdout);
 }
 
@@ -234,6 +247,7 @@ static void profile_nark_as(const Opt& o, int lg, bool harness_shape) {
   const Fr one = {1, 0, 0, 0};
   HarnessRng hr(0xB0B ^ o.seed, o.curve);
   hp_as::Rng zk_rng = harness_shape ? hp_as::Rng([&hr]() { return hr.field(); }) : hp_as::Rng();
+  Blinders blind(o, harness_shape);
   Result r;
   auto t0 = Clock::now();
   // The reference's DummyCircuit (num_constraints - 1 copies of a * b = c over TWO witness variables) makes A z, B z, C z one value
@@ -273,7 +287,7 @@ static void profile_nark_as(const Opt& o, int lg, bool harness_shape) {
       wit = std::make_shared<FrVector>(ctx, std::vector<Fr>{am, bm});
     }
     auto sp = AS::sponges(hp_as::fresh_sponge<Sponge>(o.curve));  // (a sponge over THIS curve's base field before it is forked)
-    r1cs_nark::Proof proof = Nark::prove(ipk, inst, wit, zk_rng, sp.nark);
+    r1cs_nark::Proof proof = Nark::prove(ipk, inst, wit, zk_rng, sp.nark, blind.get());
     return r1cs_nark_as::Input{r1cs_nark_as::InputInstance{inst, proof.first_msg}, proof.second_msg};
   };
   std::vector<r1cs_nark_as::Input> inputs{make_input()};
@@ -325,6 +339,7 @@ static void profile_nark(const Opt& o, int lg, bool make_zk) {
   const Fr one = {1, 0, 0, 0};
   HarnessRng hr(0xB0B ^ o.seed, o.curve);
   hp_as::Rng zk_rng = make_zk ? hp_as::Rng([&hr]() { return hr.field(); }) : hp_as::Rng();
+  Blinders blind(o, make_zk);
   Result r;
   Fr a = hr.field(), b = hr.field();
   Fr am = fr.to_mont(a), bm = fr.to_mont(b), abm = fr.mul(am, bm), ab;
@@ -348,8 +363,8 @@ static void profile_nark(const Opt& o, int lg, bool make_zk) {
   std::vector<Fr> w(n_wit, am);
   w[1] = bm;
   auto wit = std::make_shared<FrVector>(ctx, w);
-  r1cs_nark::Proof proof = Nark::prove(ipk, inst, wit, zk_rng, Sponge());
-  r.prove_ms = median_ms(o.reps, [&] { proof = Nark::prove(ipk, inst, wit, zk_rng, Sponge()); });
+  r1cs_nark::Proof proof = Nark::prove(ipk, inst, wit, zk_rng, Sponge(), blind.get());
+  r.prove_ms = median_ms(o.reps, [&] { proof = Nark::prove(ipk, inst, wit, zk_rng, Sponge(), blind.get()); });
   t0 = Clock::now();
   r.verified = Nark::verify(ipk, inst, proof, Sponge());
   r.verify_ms = ms_since(t0);
@@ -377,6 +392,7 @@ static void profile_ipa(const Opt& o, int lg, bool harness_shape) {
   HarnessRng hr(0xD1 ^ o.seed, o.curve);
   hp_as::Rng prng([&hr]() { return hr.field(); });
   hp_as::Rng zk_rng = harness_shape ? prng : hp_as::Rng();
+  Blinders blind(o, harness_shape);
   Result r;
   ipa_pc::CommitterKey pp = o.transparent ? Ipa::setup_transparent(ctx, degree, o.domain) : Ipa::setup(ctx, degree, 0x1BA5EED);
   auto t0 = Clock::now();
@@ -390,13 +406,13 @@ static void profile_ipa(const Opt& o, int lg, bool harness_shape) {
   check(amsm_vec_powers(ctx.get(), point.data(), degree + 1, z.ptr()), "amsm_vec_powers");
   Fr value;
   check(amsm_vec_inner_product(ctx.get(), poly.ptr(), z.ptr(), degree + 1, value.data()), "amsm_vec_inner_product");
-  ipa_pc::Proof proof = Ipa::open(keys.pk.ipa_ck, poly, cr.first, point, cr.second, harness_shape, prng);
+  ipa_pc::Proof proof = Ipa::open(keys.pk.ipa_ck, poly, cr.first, point, cr.second, harness_shape, prng, blind.get());
   std::vector<ipa_pc_as::InputInstance> inputs{ipa_pc_as::InputInstance{cr.first, point, value, proof}};
-  auto first = AS::prove(keys.pk, inputs, {}, zk_rng);
+  auto first = AS::prove(keys.pk, inputs, {}, zk_rng, blind.get());
   std::vector<ipa_pc_as::Accumulator> old{first.first};
   if (harness_shape) old.push_back(first.first);
   std::pair<ipa_pc_as::Accumulator, ipa_pc_as::Proof> res;
-  r.prove_ms = timed_proves(o, [&] { res = AS::prove(keys.pk, inputs, old, zk_rng); });
+  r.prove_ms = timed_proves(o, [&] { res = AS::prove(keys.pk, inputs, old, zk_rng, blind.get()); });
   t0 = Clock::now();
   r.verified = AS::verify(ctx, keys.vk, inputs, old, res.first, res.second);
   r.verify_ms = ms_since(t0);
@@ -493,7 +509,7 @@ int main(int argc, char** argv) {
   Opt o;
   if (argc < 4) {
     fprintf(stderr, "usage: %s <scheme|all> <log_min> <log_max> [--shape harness|n2|both] [--reps R] [--sponge sha256|poseidon] "
-                    "[--curve 0|1|2|4|6|8] [--constant] [--uniform] [--no-roundtrip] [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--replicate-below L] [--transparent DOMAIN]\n", argv[0]);
+                    "[--curve 0|1|2|4|6|8] [--constant] [--uniform] [--no-roundtrip] [--device D | --devices a,b,..] [--seed S] [--dump FILE] [--cold] [--replicate-below L] [--transparent DOMAIN] [--device-blinders KEYHEX]\n", argv[0]);
     return 2;
   }
   o.scheme = argv[1];
@@ -519,6 +535,15 @@ int main(int argc, char** argv) {
     else if (a == "--replicate-below" && i + 1 < argc) o.replicate_log2 = atoi(argv[++i]);
     else if (a == "--seed" && i + 1 < argc) o.seed = strtoull(argv[++i], nullptr, 0);
     else if (a == "--dump" && i + 1 < argc) o.dump = argv[++i];
+    else if (a == "--device-blinders" && i + 1 < argc) {
+      const std::string hex = argv[++i];
+      if (hex.size() != 64 || hex.find_first_not_of("0123456789abcdefABCDEF") != std::string::npos) {
+        fprintf(stderr, "--device-blinders takes a key of 64 hex digits\n");
+        return 2;
+      }
+      for (int k = 0; k < 32; k++) o.blind_key[k] = (uint8_t)strtoul(hex.substr(2 * k, 2).c_str(), nullptr, 16);
+      o.device_blinders = true;
+    }
     else if (a == "--transparent" && i + 1 < argc) {
       o.transparent = true;
       o.domain = argv[++i];
