@@ -85,7 +85,7 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
 PROBE_SRC = os.path.join(ROOT, "tests", "hip", "field_probe.hip")
 PROBE_LIB = os.path.join(ROOT, "tests", "hip", "libfield_probe.so")
 PROBE_OBJ = os.path.join(ROOT, "build", "obj", "probe")
-PROBE_PACKS = [0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19]  # field_probe.hip: PROBE_PACKS
+PROBE_PACKS = [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22]  # field_probe.hip: PROBE_PACKS
 
 
 def probe_stale() -> bool:

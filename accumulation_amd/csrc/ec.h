@@ -91,6 +91,11 @@ AMSM_DEV XYZZ<P> xyzz_dbl(const XYZZ<P>& p) {
 // mdbl-2008-s-1 with a = 0 (affine input): 3M + 3S
 template <class P>
 AMSM_DEV XYZZ<P> xyzz_dbl_affine(const Affine<P>& p) {  // p.x < 2p, p.y <= 2p (a lazily negated y through fe_tight), tight
+  // As xyzz_dbl: the point of order 2 doubles to the identity.  y = 0 itself passes through the formulas as exact zeros, but
+  // y = p or 2p (a coordinate word >= p through fe_import, a lazy -0) gives v = (4 y^2 + m p) / R' = p exactly: ZZ = ZZZ = p.
+  if constexpr (HasTwoTorsion<P>::value) {
+    if (fe_is_zero_mod<P, 4>(p.y)) return xyzz_inf<P>();  // y <= 2p
+  }
   Fe<P> u = fe_dbl<P>(p.y);                                  // [< 4p]
   Fe<P> v = fe_sqr<P>(u);                                    // [< 1.2p]
   Fe<P> w = fe_mul<P>(u, v);                                 // [< 1.1p]

@@ -11,6 +11,11 @@ to the right value.  Nothing here is a copy of u_columns.
 The packs are parametrised by (p, L, B): p from the oracle's curves (oracle/pyref.py, tests/helpers.py), the limb shape
 from the width of p (9 x 29 bits up to 256 bits, 14 x 28 bits above); tests/test_field_probe_cpu.py compares the derived
 constants with the tables compiled into csrc/fpu.h.
+
+A curve of even order (BLS12-377) has a point T = (x, 0) of order 2.  Its doubling is the identity, and on an unsaturated
+field the formulas reach that identity as a NON-ZERO multiple of p unless the doubling tests Y = 0 mod p first (csrc/ec.h,
+fp.h: HasTwoTorsion).  For such a pack the group-law cases also hold T with Y written as every multiple of p its invariant
+admits, and the small-order points around it (SMALL_ORDER, _two_torsion_cases).
 """
 from __future__ import annotations
 
@@ -68,6 +73,10 @@ class Pack:
     curve: Optional[o.Curve] = None  # the curve this is the base field of (group-law layer)
     other: Optional[int] = None      # pack id of the same field with CHAIN flipped
     dots: bool = False               # fp_mul_gfx950.h generates fe_dot2 / fe_dot3 for it
+
+    @property
+    def two_torsion(self):  # the curve has even order: csrc/fp.h specialises HasTwoTorsion for this pack
+        return self.curve is not None and self.curve.name in SMALL_ORDER
 
     @property
     def Rp(self):  # the radix the registers compute in: R' = 2^(B L)
@@ -147,12 +156,16 @@ def _sat(name, pid, m, dots=False):
     return Pack(name, pid, m, W, 32, W, False, None, None, dots)
 
 
+# the small-order points of the curves of even order: T of order 2 (y = 0), S of order 6 (3 S = T), U of order 3 with x = 0
+SMALL_ORDER = {"bls12_377_g1": {"T": (h.BLS12_377_P - 1, 0), "S": (2, 3), "U": (0, 1)}}
+
 UNSAT_PACKS = [_unsat("PallasFqU", 0, o.PALLAS, 5), _unsat("Bls12381FqU", 1, o.BLS12_381_G1), _unsat("VestaFqU", 2, h.VESTA, 6),
-               _unsat("Bn254FqU", 3, h.BN254, 7), _unsat("GrumpkinFqU", 4, h.GRUMPKIN, 8)]
+               _unsat("Bn254FqU", 3, h.BN254, 7), _unsat("GrumpkinFqU", 4, h.GRUMPKIN, 8),
+               _unsat("Bls12377FqU", 9, h.BLS12_377, 20)]
 SAT_PACKS = [_sat("PallasFq", 10, o.PALLAS.p), _sat("PallasFr", 11, o.PALLAS.r, True), _sat("Bls12381Fq", 12, o.BLS12_381_G1.p),
              _sat("Bls12381Fr", 13, o.BLS12_381_G1.r, True), _sat("VestaFq", 14, h.VESTA.p), _sat("VestaFr", 15, h.VESTA.r),
              _sat("Bn254Fq", 16, h.BN254.p), _sat("Bn254Fr", 17, h.BN254.r, True), _sat("GrumpkinFq", 18, h.GRUMPKIN.p),
-             _sat("GrumpkinFr", 19, h.GRUMPKIN.r, True)]
+             _sat("GrumpkinFr", 19, h.GRUMPKIN.r, True), _sat("Bls12377Fq", 21, h.BLS12_377.p), _sat("Bls12377Fr", 22, h.BLS12_377.r, True)]
 
 
 @dataclass
@@ -333,6 +346,35 @@ def _bc_pairs(pk, lim, rng):
     return out
 
 
+def reduction_multipliers(pk, a, b):
+    """the limbs m_0 .. m_(L-1) the Montgomery reduction of a b multiplies p by: the one m < R' with a b + m p = 0 mod R'"""
+    return pk.limbs((-pk.value(a) * pk.value(b) * pow(pk.p, -1, pk.Rp)) % pk.Rp)
+
+
+def chosen_m_patterns(pk):
+    """named multiplier patterns for the reduction, column by column: alternating 0 / 2^B - 1 from either start, a single 1 and a
+    single 2^B - 1 in each column, all ones, one random pattern (its own seed: the streams of the older cases stay as they were)"""
+    L, M = pk.L, pk.M
+    rng = random.Random(f"chosen_m:{pk.name}")
+    pats = [("alt:0,M", [M * (i & 1) for i in range(L)]), ("alt:M,0", [M * (1 - (i & 1)) for i in range(L)])]
+    pats += [(f"one@{k}", [int(i == k) for i in range(L)]) for k in range(L)]
+    pats += [(f"M@{k}", [M * int(i == k) for i in range(L)]) for k in range(L)]
+    pats += [("all:1", [1] * L), ("rand", [rng.randrange(M + 1) for _ in range(L)])]
+    return pats
+
+
+def chosen_m_cases(pk):
+    """(tag, [a, 1]) with a = -m p mod R': a is tight, a * 1 is inside the Needs of the multiplication, and the reduction's
+    multipliers are exactly the limbs of m"""
+    one = pk.limbs(1)
+    out = []
+    for tag, m in chosen_m_patterns(pk):
+        a = pk.limbs((-pk.value(m) * pk.p) % pk.Rp)
+        assert pk.is_tight(a) and reduction_multipliers(pk, a, one) == m
+        out.append((f"m={tag}", [a, one]))
+    return out
+
+
 def _kp_plus(pk, KMAX, rs):
     return [(f"{k}p+{r:#x}"[:40], pk.limbs(k * pk.p + r)) for k in range(KMAX) for r in rs]
 
@@ -359,6 +401,7 @@ def field_cases(pid, op):
         for an, a in list(tc.items()) + list(lc.items()):
             for pn, b in _with_largest_partner(pk, a, 0):
                 cand += [(f"{an}*{pn}", [a, b]), (f"{pn}*{an}", [b, a])]
+        cand += chosen_m_cases(pk)  # appended: the cases before them are what they were
     elif base == "sqr":
         for an, a in tight_classes(pk, math.isqrt((Rp - p) * Rp), rng, all_limbs=True).items():
             cand.append((an, [a]))
@@ -518,7 +561,8 @@ MODES = ("min", "max", "rand")
 
 def _fixture_points(curve):
     name = {"pallas": "adversarial_points.json", "bls12_381_g1": "adversarial_points.json", "vesta": "adversarial_points.json",
-            "bn254_g1": "bn254_adversarial_points.json", "grumpkin": "grumpkin_adversarial_points.json"}[curve.name]
+            "bn254_g1": "bn254_adversarial_points.json", "grumpkin": "grumpkin_adversarial_points.json",
+            "bls12_377_g1": "bls12_377_adversarial_points.json"}[curve.name]
     fx = json.load(open(os.path.join(HERE, "golden", name)))
     kinds = {k: [(int(x, 16), int(y, 16)) for x, y in v] for k, v in fx["curves"][curve.name].items()}
     if "negated_doubling_pair" in fx:
@@ -623,6 +667,81 @@ def _pairs(pk):
 
 
 @functools.lru_cache(maxsize=None)
+def small_order_points(pid):
+    """-> {T, S, U, 2S} for a pack whose curve has even order, each checked to be on the curve and of the order claimed"""
+    pk = PACK_BY_ID[pid]
+    c = pk.curve
+    pts = dict(SMALL_ORDER[c.name])
+    for name, order in (("T", 2), ("S", 6), ("U", 3)):
+        P = pts[name]
+        assert o.is_on_curve(c, P) and o.mul(c, order, P) is None and all(o.mul(c, d, P) is not None for d in range(1, order)), name
+    assert pts["T"][1] == 0 and pts["U"][0] == 0 and o.mul(c, 3, pts["S"]) == pts["T"]
+    pts["2S"] = o.mul(c, 2, pts["S"])
+    assert o.is_on_curve(c, pts["2S"]) and o.mul(c, 3, pts["2S"]) is None and pts["2S"] is not None  # (on BLS12-377 it is U itself)
+    return pts
+
+
+def _with_y(limbs, pk, ky):
+    """a representation of T = (x, 0) with its second coordinate rewritten as ky p"""
+    return [limbs[0], pk.limbs(ky * pk.p)] + list(limbs[2:])
+
+
+def _two_torsion_cases(pk, op):
+    """[(tag, ins, expected)] for a pack whose curve has even order: the point T of order 2 with Y (or y) written as every multiple
+    of p that the operand's invariant admits -- the representatives the HasTwoTorsion guards of csrc/ec.h exist for -- and the points
+    of order 6 and 3 around it.  Own seed; appended to the cases every pack has."""
+    c, p = pk.curve, pk.p
+    so = small_order_points(pk.pid)
+    T, S, U, S2 = so["T"], so["S"], so["U"], so["2S"]
+    rng = random.Random(f"two_torsion:{pk.name}:{op}")
+    zero = [0] * pk.L
+    quad = op in QUAD_OPS
+    out = []
+    if op in ("xyzz_dbl", "xyzz_dbl_quad", "jac_dbl"):
+        rep, bound = (jac_rep, JAC_BOUND[1]) if op == "jac_dbl" else (xyzz_rep, XYZZ_BOUND[1])
+        for ky in range(bound):  # Y < 3p (XYZZ), Y < 13p (Jacobian)
+            for mode in MODES:
+                out.append((f"T:Y={ky}p:{mode}", _with_y(rep(pk, T, mode, rng), pk, ky), None))
+        for tag, P in (("S", S), ("2S", S2)):
+            for mode in MODES:
+                out.append((f"{tag}:{mode}", rep(pk, P, mode, rng), o.add(c, P, P)))
+    elif op == "xyzz_dbl_affine":  # y <= 2p is inside the stated Needs: 2p is what a lazily negated 0 would be
+        x = pk.to_m(T[0])
+        for kx in (0, 1):
+            for ky in (0, 1, 2):
+                out.append((f"T:x+{kx}p,y={ky}p", [pk.limbs(x + kx * p), pk.limbs(ky * p)], None))
+    elif op in ("xyzz_madd", "jac_madd"):
+        rep, bound = (xyzz_rep, XYZZ_BOUND[1]) if op == "xyzz_madd" else (jac_rep, JAC_BOUND[1])
+        qx = pk.limbs(pk.to_m(T[0]))
+        qys = [("y=0", zero), ("y=p:tight", pk.limbs(p)), ("y=p:lazy", pk.kp_bp(1, 1)), ("y=2p:tight", pk.limbs(2 * p)),
+               ("y=2p:lazy", pk.kp_bp(2, 1))]
+
+        def case(tag, acc, qy, want):
+            out.append((tag, acc + [zero] * (4 - len(acc)) + [qx, qy], want))
+        for ky in range(bound):
+            for qi, (qn, qy) in enumerate(qys):
+                for mode in (MODES if ky < 3 else (MODES[(ky + qi) % 3],)):
+                    case(f"q=acc=T:Y={ky}p:{mode}:{qn}", _with_y(rep(pk, T, mode, rng), pk, ky), qy, None)
+        for qn, qy in qys:
+            for mode in MODES:  # T reached as 3 S, in whatever representative the lift gives Y
+                case(f"acc=3S,q=T:{mode}:{qn}", rep(pk, o.mul(c, 3, S), mode, rng), qy, None)
+                case(f"acc=S,q=T:{mode}:{qn}", rep(pk, S, mode, rng), qy, o.add(c, S, T))
+            case(f"acc=inf,q=T:{qn}", rep(pk, None, "min", rng), qy, T)
+    elif op in ("xyzz_add", "xyzz_add_quad"):
+        n = 0
+        for k1 in range(XYZZ_BOUND[1]):
+            for k2 in range(XYZZ_BOUND[1]):
+                for mode in ((MODES[n % 3],) if quad else MODES):
+                    ins = _with_y(xyzz_rep(pk, T, mode, rng), pk, k1) + _with_y(xyzz_rep(pk, T, mode, rng), pk, k2)
+                    out.append((f"T+T:Y={k1}p,{k2}p:{mode}", ins, None))
+                n += 1
+        for tag, A, Q in (("S+2S", S, S2), ("T+U", T, U), ("U+T", U, T)):
+            for mode in MODES:
+                out.append((f"{tag}:{mode}", xyzz_rep(pk, A, mode, rng) + xyzz_rep(pk, Q, mode, rng), o.add(c, A, Q)))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
 def group_cases(pid, op):
     """[(tag, ins, expected)]: expected is the oracle's affine point (None = infinity), or for affine_neg_if the (x, y) values"""
     pk = PACK_BY_ID[pid]
@@ -669,8 +788,10 @@ def group_cases(pid, op):
                     out.append((f"{tag}:{mode}", jac_rep(pk, P, mode, rng), o.add(c, P, P) if op == "jac_dbl" else P))
     else:
         raise KeyError(op)
-    if op in QUAD_OPS:
-        out = out[:MAX_CASES // 4]
+    extra = _two_torsion_cases(pk, op) if pk.two_torsion else []
+    if op in QUAD_OPS:  # a quarter of the launch; the two-torsion class, where there is one, takes its room from the tail of the others
+        out = out[:MAX_CASES // 4 - len(extra)]
+    out += extra
     assert 0 < len(out) <= MAX_CASES, (pk.name, op, len(out))
     return out
 

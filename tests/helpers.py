@@ -17,6 +17,15 @@ _BN_R = 218882428718392752222464057452572750885483644004160343436982041865758084
 BN254 = o.Curve("bn254_g1", 4, p=_BN_P, r=_BN_R, b=3, gx=1, gy=2, limbs=4)
 GRUMPKIN = o.Curve("grumpkin", 6, p=_BN_R, r=_BN_P, b=_BN_R - 17, gx=1, gy=17631683881184975370165255887551781615748388533673675138860, limbs=4)
 
+# BLS12-377 G1 (AMSM_BLS12_377_G1 = 8): y^2 = x^3 + 1 over a 377-bit field, the one curve here of EVEN order (#E = h r, 2^92 | h).
+# tests/test_bls12_377_cpu.py re-derives p, r and h from the curve's parameter z and checks this object against them.
+BLS12_377_P = 0x1AE3A4617C510EAC63B05C06CA1493B1A22D9F300F5138F1EF3622FBA094800170B5D44300000008508C00000000001
+BLS12_377_R = 0x12AB655E9A2CA55660B44D1E5C37B00159AA76FED00000010A11800000000001
+BLS12_377_H = 0x170B5D44300000000000000000000000  # the cofactor
+BLS12_377 = o.Curve("bls12_377_g1", 8, BLS12_377_P, BLS12_377_R, b=1,
+                    gx=81937999373150964239938255573465948239988671502647976594219695644855304257327692006745978603320413799295628339695,
+                    gy=241266749859715473739788878240585681733927191168601896383759122102112907357779751001206799952863815012735208165030, limbs=6)
+
 
 def load_golden():
     with open(GOLDEN) as f:

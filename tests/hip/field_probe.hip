@@ -39,16 +39,22 @@ constexpr int N_IN = 8;      // operand slots per case
 constexpr int N_OUT = 4;     // result slots per case
 constexpr int FIRST_SAT_OP = OP_sat_mul;
 
-// pack ids: 0-4 the unsaturated base fields, 5-8 the 9 x 29 packs with CHAIN flipped, 10-19 the saturated packs
+// pack ids: 0-4 and 9 the unsaturated base fields, 5-8 the 9 x 29 packs with CHAIN flipped and 20 the 14 x 28 one (BLS12-377; BLS12-381
+// has no flipped pack), 10-19 and 21-22 the saturated packs
 struct PallasFqUOther : PallasFqU { static constexpr bool CHAIN = !PallasFqU::CHAIN; };
 struct VestaFqUOther : VestaFqU { static constexpr bool CHAIN = !VestaFqU::CHAIN; };
 struct Bn254FqUOther : Bn254FqU { static constexpr bool CHAIN = !Bn254FqU::CHAIN; };
 struct GrumpkinFqUOther : GrumpkinFqU { static constexpr bool CHAIN = !GrumpkinFqU::CHAIN; };
+struct Bls12377FqUOther : Bls12377FqU { static constexpr bool CHAIN = !Bls12377FqU::CHAIN; };
+namespace amsm {
+template <>
+struct HasTwoTorsion<Bls12377FqUOther> : HasTwoTorsion<Bls12377FqU> {};  // the same curve: the same guarded doublings
+}  // namespace amsm
 #define PROBE_PACKS(X)                                                                                                 \
   X(0, PallasFqU) X(1, Bls12381FqU) X(2, VestaFqU) X(3, Bn254FqU) X(4, GrumpkinFqU)                                   \
-  X(5, PallasFqUOther) X(6, VestaFqUOther) X(7, Bn254FqUOther) X(8, GrumpkinFqUOther)                                 \
+  X(5, PallasFqUOther) X(6, VestaFqUOther) X(7, Bn254FqUOther) X(8, GrumpkinFqUOther) X(9, Bls12377FqU)                \
   X(10, PallasFq) X(11, PallasFr) X(12, Bls12381Fq) X(13, Bls12381Fr) X(14, VestaFq) X(15, VestaFr) X(16, Bn254Fq)    \
-  X(17, Bn254Fr) X(18, GrumpkinFq) X(19, GrumpkinFr)
+  X(17, Bn254Fr) X(18, GrumpkinFq) X(19, GrumpkinFr) X(20, Bls12377FqUOther) X(21, Bls12377Fq) X(22, Bls12377Fr)
 
 #ifdef PROBE_PACK
 

@@ -3,8 +3,8 @@ code; the host scalar-field helpers, the GLV set-up, the 48 / 96 / 32-byte wire 
 subgroup among the rejections), the Poseidon sponge, host MSMs over the adversarial-point fixture, the key stream, the scalar stream
 with its reduced fallback (r has 253 bits), transparent keys (Tonelli-Shanks with 2-adicity 46 on a 12-word field, and an EVEN
 cofactor), point validation over the curve's small-order points ((p - 1, 0) of order 2, (0, 1) of order 3, (2, 3) of order 6), the four
-schemes on the library's host backend and the C++ drivers' dumps -- each against the big-int oracle with a BLS12-377 `Curve` built
-here (oracle/ knows curves 0 and 1 only and is curve-generic)."""
+schemes on the library's host backend and the C++ drivers' dumps -- each against the big-int oracle with the BLS12-377 `Curve` of
+tests/helpers.py (oracle/ knows curves 0 and 1 only and is curve-generic), checked here against the re-derived p, r and h."""
 import functools
 import json
 import math
@@ -28,8 +28,9 @@ H = (Z - 1) ** 2 // 3  # the cofactor
 GX = 81937999373150964239938255573465948239988671502647976594219695644855304257327692006745978603320413799295628339695
 GY = 241266749859715473739788878240585681733927191168601896383759122102112907357779751001206799952863815012735208165030
 BETA = 0x1AE3A4617C510EABC8756BA8F8C524EB8882A75CC9BC8E359064EE822FB5BFFD1E945779FFFFFFFFFFFFFFFFFFFFFFF
-BLS12_377 = o.Curve("bls12_377_g1", 8, P, R, b=1, gx=GX, gy=GY, limbs=6)
+BLS12_377 = h.BLS12_377  # the one definition (tests/helpers.py; tests/field_model.py takes it from there too)
 C = BLS12_377
+assert (C.name, C.curve_id, C.p, C.r, C.b, C.gx, C.gy, C.limbs) == ("bls12_377_g1", 8, P, R, 1, GX, GY, 6) and h.BLS12_377_H == H
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "accumulation_amd", "csrc")
 FIX = json.load(open(os.path.join(ROOT, "tests", "golden", "bls12_377_adversarial_points.json")))
@@ -531,9 +532,10 @@ def test_host_points_check(host_ctx):
     ck.free()
 
 
-def test_host_group_law_on_the_small_order_points(host_ctx):
-    """doubling the point of order 2 gives the identity and the identity plus P gives P: MSMs over a plain key of small-order points
-    on the host backend -- 2 (p - 1, 0) = O, 3 (2, 3) = (p - 1, 0), 6 (2, 3) = O, 3 (0, 1) = O, and O + G = G behind them"""
+@pytest.mark.parametrize("flags", [1, 2], ids=["precomp", "plain"])
+def test_host_group_law_on_the_small_order_points(host_ctx, flags):
+    """doubling the point of order 2 gives the identity and the identity plus P gives P: MSMs over a plain and over a precomputed key
+    of small-order points on the host backend -- 2 (p - 1, 0) = O, 3 (2, 3) = (p - 1, 0), 6 (2, 3) = O, 3 (0, 1) = O, and O + G = G behind them"""
     from tests.test_msm_gpu import run_msm
     g = o.generator(C)
     for pts, sc in (([(P - 1, 0)], [2]), ([(2, 3)], [3]), ([(2, 3)], [6]), ([(0, 1)], [3]), ([(P - 1, 0), g], [2, 1]),
@@ -541,7 +543,7 @@ def test_host_group_law_on_the_small_order_points(host_ctx):
         want = None
         for pt, s in zip(pts, sc):
             want = o.add(C, want, o.mul(C, s, pt))
-        xy, inf = run_msm(host_ctx, C, pts, sc, 2)
+        xy, inf = run_msm(host_ctx, C, pts, sc, flags)
         assert h.np_to_point(C, xy, inf) == want, (pts, sc)
 
 

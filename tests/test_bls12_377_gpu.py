@@ -410,9 +410,11 @@ def test_points_check_equals_the_host_backend(host, monkeypatch, ladder):
         c.close()
 
 
-def test_group_law_on_the_small_order_points(ctx):
+@pytest.mark.parametrize("flags", [1, 2], ids=["precomp", "plain"])
+def test_group_law_on_the_small_order_points(ctx, flags):
     """doubling the point of order 2 gives the identity and the identity plus P gives P, through the device's group law: MSMs over
-    plain keys of small-order points (tests/test_bls12_377_cpu.py runs the same cases on the host backend)"""
+    plain and precomputed keys of small-order points (the table of a precomputed key holds the doublings of (p - 1, 0) as (0, 0):
+    k_precompute_level / k_precompute_all_levels); tests/test_bls12_377_cpu.py runs the same cases on the host backend"""
     from tests.test_msm_gpu import run_msm
     g = o.generator(C)
     for pts, sc in (([(P - 1, 0)], [2]), ([(2, 3)], [3]), ([(2, 3)], [6]), ([(0, 1)], [3]), ([(P - 1, 0), g], [2, 1]),
@@ -420,7 +422,7 @@ def test_group_law_on_the_small_order_points(ctx):
         want = None
         for pt, s in zip(pts, sc):
             want = o.add(C, want, o.mul(C, s, pt))
-        xy, inf = run_msm(ctx, C, pts, sc, 2)
+        xy, inf = run_msm(ctx, C, pts, sc, flags)
         assert got(xy, inf) == want, (pts, sc)
 
 

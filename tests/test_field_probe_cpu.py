@@ -64,7 +64,8 @@ def test_every_field_case_is_inside_the_needs(pk, op):
 @pytest.mark.parametrize("pk", fm.UNSAT_PACKS, ids=_ids)
 def test_field_cases_reach_the_edges_the_issue_names(pk):
     """the value classes are there after clipping: the exact subtrahend limit and 0, all-ones lazy limbs in a column sum, m_k at 0
-    and at 2^B - 1, every k p below KMAX p and its neighbours"""
+    and at 2^B - 1 (in all columns at once, and in each column beside a neighbour of the other kind), every k p below KMAX p and
+    its neighbours"""
     p, wide = pk.p, (1 << (pk.B + 1)) - 1
     for op in fm.FIELD_OPS:
         base, K = fm.split_op(op)
@@ -83,6 +84,13 @@ def test_field_cases_reach_the_edges_the_issue_names(pk):
             assert all([1 << (pk.B * i), 1] in vals for i in range(pk.L)), op
             m0 = lambda v: ((v[0] * v[1]) % (1 << pk.B)) * pk.ninv % (1 << pk.B)  # noqa: E731
             assert {m0(v) for v in vals} >= {0, pk.M}, op
+        if base == "mul":  # the reduction column by column: m_k = 0 beside m_(k+1) != 0, and the other way round, at every column
+            ms = [fm.reduction_multipliers(pk, *ins) for ins in raw]
+            for k in range(pk.L - 1):
+                assert any(m[k] == 0 and m[k + 1] != 0 for m in ms) and any(m[k] != 0 and m[k + 1] == 0 for m in ms), (op, k)
+            assert [pk.M * (i & 1) for i in range(pk.L)] in ms and [pk.M * (1 - (i & 1)) for i in range(pk.L)] in ms and [1] * pk.L in ms
+            for k in range(pk.L):
+                assert [int(i == k) for i in range(pk.L)] in ms and [pk.M * int(i == k) for i in range(pk.L)] in ms, (op, k)
         if base == "is_zero_mod":
             flat = {v[0] for v in vals}
             assert flat >= {k * p for k in range(K)} | {k * p + 1 for k in range(K)} | {k * p - 1 for k in range(1, K)}, op
@@ -121,6 +129,79 @@ def test_group_cases_hold_the_tiny_y_class_and_the_bound_edges(pk):
     for op in ("xyzz_madd", "xyzz_add", "jac_madd"):
         tags = {tag.split(":")[0] for tag, _, _ in fm.group_cases(pk.pid, op)}
         assert tags >= {"generic", "q=acc", "q=-acc", "acc=inf", "q=inf"}, op
+
+
+def test_chosen_multipliers_are_what_the_reduction_computes():
+    """a = -m p mod R' against b = 1: a word-by-word Montgomery reduction in radix 2^B, written out here, multiplies p by exactly the
+    limbs of m -- on the p_0 = 1 branch (m_k = -lo) and on the general one (m_k = lo NINV mod 2^B) alike"""
+    for pk in fm.UNSAT_PACKS:
+        pats = dict(fm.chosen_m_patterns(pk))
+        assert len(pats) == 2 * pk.L + 4
+        present = [ins for _, ins in fm.field_cases(pk.pid, "mul")]  # (an operand pair an older case already holds keeps that tag)
+        for (tag, ins), m in zip(fm.chosen_m_cases(pk), pats.values()):
+            acc, got = pk.value(ins[0]) * pk.value(ins[1]), []
+            for _ in range(pk.L):
+                got.append((acc & pk.M) * pk.ninv & pk.M)
+                acc = (acc + got[-1] * pk.p) >> pk.B
+            assert got == m == fm.reduction_multipliers(pk, *ins), (pk.name, tag)
+            assert pk.is_tight(ins[0]) and fm.field_contract(pk, "mul", ins)[0] and ins in present, (pk.name, tag)
+    assert {pk.name for pk in fm.UNSAT_PACKS if pk.ninv == pk.M} == {"PallasFqU", "VestaFqU", "Bls12377FqU"}  # the p_0 = 1 branch
+
+
+def test_two_torsion_flag_is_the_headers():
+    """Pack.two_torsion <=> csrc/fp.h specialises HasTwoTorsion for the pack <=> the curve has a point with y = 0 (x^3 = -b has a
+    root: -b is a cube, p = 1 mod 3 for every curve here) -- and the flipped pack of the probe inherits the specialisation"""
+    src = open(os.path.join(ROOT, "accumulation_amd", "csrc", "fp.h")).read()
+    special = set(re.findall(r"struct HasTwoTorsion<(\w+)> \{\s*static constexpr bool value = true;", src))
+    for pk in fm.UNSAT_PACKS:
+        c = pk.curve
+        assert c.p % 3 == 1
+        even = pow(-c.b % c.p, (c.p - 1) // 3, c.p) == 1
+        assert pk.two_torsion == even == (pk.name in special), pk.name
+        if even:
+            so = fm.small_order_points(pk.pid)
+            assert so["T"][1] == 0 and o.add(c, so["T"], so["T"]) is None and o.add(c, so["S"], so["2S"]) == so["T"]
+            assert f"struct HasTwoTorsion<{pk.name}Other> : HasTwoTorsion<{pk.name}> {{}};" in open(PROBE_SRC).read()
+    assert special == {"Bls12377Fq", "Bls12377FqU"}
+
+
+@pytest.mark.parametrize("pk", [pk for pk in fm.UNSAT_PACKS if pk.two_torsion], ids=_ids)
+def test_group_cases_hold_the_two_torsion_class(pk):
+    """for a curve of even order: the point of order 2 with Y (y) written as a NON-ZERO multiple of p -- the representatives the
+    HasTwoTorsion guards exist for -- reaches each of the three guarded doublings, xyzz_dbl_affine, and the q = acc branch of both
+    mixed additions and of both full additions; every such case is inside the invariants and expects the identity"""
+    p = pk.p
+    T = fm.small_order_points(pk.pid)["T"]
+    xT = pk.to_m(T[0])
+
+    def kp(limbs):  # k if the limbs are k p with k != 0, else 0
+        v = pk.value(limbs)
+        return v // p if v and v % p == 0 else 0
+
+    for op, bound in (("xyzz_dbl", 3), ("xyzz_dbl_quad", 3), ("jac_dbl", 13)):
+        hit = [ins for _, ins, want in fm.group_cases(pk.pid, op) if kp(ins[1]) and pk.value(ins[0]) % p != 0 and want is None]
+        assert {kp(ins[1]) for ins in hit} == set(range(1, bound)) and all(fm.group_needs(pk, op, ins) for ins in hit), op
+        assert any(pk.value(ins[1]) == 0 and pk.value(ins[2]) != 0 and want is None for _, ins, want in fm.group_cases(pk.pid, op)), op
+    hit = [ins for _, ins, want in fm.group_cases(pk.pid, "xyzz_dbl_affine") if kp(ins[1]) and want is None]
+    assert {(pk.value(ins[0]), kp(ins[1])) for ins in hit} == {(xT + kx * p, ky) for kx in (0, 1) for ky in (1, 2)}
+    assert all(fm.group_needs(pk, "xyzz_dbl_affine", ins) for ins in hit)
+    for op, bound in (("xyzz_madd", 3), ("jac_madd", 13)):
+        cases = fm.group_cases(pk.pid, op)
+        hit = [ins for tag, ins, want in cases if tag.startswith("q=acc=T") and want is None]
+        assert all(pk.value(ins[4]) == xT and pk.value(ins[5]) % p == 0 and fm.group_needs(pk, op, ins) for ins in hit), op
+        assert {(kp(ins[1]), kp(ins[5]), pk.is_tight(ins[5])) for ins in hit} >= \
+            {(ky, kq, t) for ky in range(bound) for kq in (1, 2) for t in (False, True)}, op   # lazy and tight limbs of p and of 2p
+        assert {kp(ins[1]) for ins in hit if pk.value(ins[5]) == 0} == set(range(bound)), op    # and the plain y = 0
+        tags = {tag.split(":")[0] for tag, _, _ in cases}
+        assert tags >= {"acc=3S,q=T", "acc=S,q=T", "acc=inf,q=T"}, op
+    for op in ("xyzz_add", "xyzz_add_quad"):
+        cases = fm.group_cases(pk.pid, op)
+        hit = [ins for tag, ins, want in cases if tag.startswith("T+T") and want is None]
+        assert {(kp(ins[1]), kp(ins[5])) for ins in hit} == {(a, b) for a in range(3) for b in range(3)}, op
+        assert all(fm.group_needs(pk, op, ins) for ins in hit), op
+        want = {tag.split(":")[0]: w for tag, _, w in cases}
+        assert want["S+2S"] == T and want["T+U"] is not None and want["T+U"] == want["U+T"], op
+        assert len(cases) * (4 if op in fm.QUAD_OPS else 1) <= fm.MAX_CASES
 
 
 @pytest.mark.parametrize("pk", fm.SAT_PACKS, ids=_ids)
