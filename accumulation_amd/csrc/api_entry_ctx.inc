@@ -92,6 +92,10 @@ int amsm_ctx_create(amsm_ctx** out, int curve, int device_id, void* stream) {
   c->pool_cap_bytes = pool_cap_from_env(c->pool_cap_bytes);
   if (const char* e = getenv("AMSM_BPL")) c->bpl = atoi(e) != 0;
   if (const char* e = getenv("AMSM_BPL_PLAIN")) c->bpl_plain = atoi(e) != 0;
+  if (const char* e = getenv("AMSM_TOP_SETS")) {
+    const int t = atoi(e);
+    c->top_sets = (t == 2 || t == 4 || t == 8) ? t : 0;
+  }
   if (const char* e = getenv("AMSM_BPL_PROBE")) c->bpl_probe = atoi(e) != 0;
   if (const char* e = getenv("AMSM_BPS")) c->bps = std::max(0, std::min(2, atoi(e)));
   if (const char* e = getenv("AMSM_BPS_BATCH")) c->bps_batch = std::max(0, std::min((int)msel::BPS_BATCH, atoi(e)));
@@ -288,6 +292,9 @@ unsigned long long amsm_ctx_two_valued_msms(const amsm_ctx* c) { return c ? c->n
 unsigned long long amsm_ctx_unit_scalar_msms(const amsm_ctx* c) { return c ? c->n_ones_split : 0ull; }
 unsigned long long amsm_ctx_direct_sum_msms(const amsm_ctx* c) { return c ? c->n_direct : 0ull; }
 unsigned long long amsm_ctx_shared_bucket_msms(const amsm_ctx* c) { return c ? c->n_shared : 0ull; }
+unsigned long long amsm_ctx_top_sets_msms(const amsm_ctx* c, int sets) {
+  return (c && (sets == 2 || sets == 4 || sets == 8)) ? c->n_top_sets[sets / 4] : 0ull;
+}
 unsigned long long amsm_ctx_tables_denied(const amsm_ctx* c) {
   if (!c) return 0ull;
   unsigned long long n = c->n_tables_denied;

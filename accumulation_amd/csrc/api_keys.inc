@@ -119,41 +119,14 @@ int bases_direct_table(amsm_ctx* ctx, amsm_bases* b, unsigned flags) {
   return AMSM_OK;
 }
 
-// MsmGeom::top_shift for window width c over the scalar field Fr: the largest s for which every CANONICAL scalar's top digit,
-// shifted left by s (on top of the doubling of a narrow window), stays <= 2^(c - 1) (never negative, no carry out).  The top
-// window starts at bit lo: its raw value is at most top(r - 1), plus the recoding's carry from the window below -- which cannot
-// arrive when the scalars that reach the maximum have nothing in that window (Pallas: r = 2^254 + 2^125.1, so the maximal top
-// value forces bits 126..253 to zero).  Round 3's 20-bit keys: Pallas 5 (digits at every 32nd bucket), BLS12-381 4; round 4's
-// (widths adding up to 256 bits): Pallas 1, BLS12-381 0.  Non-canonical scalars whose shifted digit would leave the bucket range
-// are reported as AMSM_E_SCALAR_RANGE by the digit walk.  *raw_max_out: the largest raw top digit.
+// MsmGeom::top_shift of a walk over the scalar field Fr (msm_types.h: top_window_shift_of has the arithmetic).  Round 3's 20-bit keys:
+// Pallas 5 (digits at every 32nd bucket), BLS12-381 4; round 4's (widths adding up to 256 bits): Pallas 1, BLS12-381 0.
+// Non-canonical scalars whose shifted digit would leave the bucket range are reported as AMSM_E_SCALAR_RANGE by the digit walk.
 template <class Fr>
 int top_window_shift(int c, int W, int n_narrow = 0, unsigned long long* raw_max_out = nullptr) {
-  const int lo = (int)window_position_of((u32)c, (u32)W, (u32)n_narrow, (u32)W - 1u);
-  const int narrow = n_narrow > 0 ? 1 : 0;  // (the narrow windows are the top ones)
-  if (raw_max_out) *raw_max_out = 0;
-  if (lo >= 255 || c < 2 || W < 2) return 0;
-  u32 r1[8];  // r - 1
-  for (int i = 0; i < 8; i++) r1[i] = Fr::mod(i);
-  r1[0] -= 1u;  // r is odd
-  auto bits = [&](int from, int n) -> unsigned long long {  // n <= 32 bits of r - 1 starting at bit `from`
-    unsigned long long v = 0;
-    for (int k = 0; k < n; k++) {
-      int bit = from + k;
-      if (bit >= 0 && bit < 256 && ((r1[bit >> 5] >> (bit & 31)) & 1u)) v |= 1ull << k;
-    }
-    return v;
-  };
-  const unsigned long long top = bits(lo, std::min(32, 256 - lo));
-  // can a scalar with the maximal top value receive a carry?  Only if its window below can exceed half its range (a carry into
-  // THAT window included): its raw value there is at most the field of r - 1
-  const int cb = (int)window_bits_of((u32)c, (u32)W, (u32)n_narrow, (u32)W - 2u);
-  const unsigned long long below = bits(lo - cb, cb);
-  const unsigned long long raw_max = top + (below + 1ull > (1ull << (cb - 1)) ? 1ull : 0ull);
-  if (raw_max_out) *raw_max_out = raw_max;
-  const unsigned long long half = 1ull << (c - 1);
-  int s = 0;
-  while (s + 1 < c && (raw_max << (narrow + s + 1)) <= half) s++;
-  return raw_max == 0 ? 0 : s;
+  u32 mod[8];
+  for (int i = 0; i < 8; i++) mod[i] = Fr::mod(i);
+  return top_window_shift_of(mod, c, W, n_narrow, raw_max_out);
 }
 inline int top_window_shift_curve(int curve, int c, int W, int n_narrow, unsigned long long* raw_max_out) {
   return with_curve(curve, [&](auto cv) { return top_window_shift<typename decltype(cv)::Fr>(c, W, n_narrow, raw_max_out); });

@@ -110,6 +110,7 @@ inline msel::Switches switches_of(const amsm_ctx* c) {
   s.direct = c->direct_max_log2 > 0;
   s.window_override = c->window_override != 0;
   s.bps_batch = c->bps_batch;
+  s.top_sets = c->top_sets;
   return s;
 }
 inline msel::Choice choose_pipeline(const amsm_ctx* ctx, const amsm_bases* bases, size_t n, int group_shift, bool skewed) {
@@ -136,9 +137,10 @@ struct RunInfo {
 
 // (api_keys.inc) MsmGeom::top_shift of a walk over the curve's scalar field; *raw_max_out = the largest raw top digit
 inline int top_window_shift_curve(int curve, int c, int W, int n_narrow, unsigned long long* raw_max_out = nullptr);
-// c_plain > 0 (plain keys, the bucket-per-lane pipeline): that window width, its widths adding up to 256 bits (n_narrow)
+// c_plain > 0 (plain keys, the bucket-per-lane pipeline): that window width, its widths adding up to 256 bits (n_narrow), the top
+// window over top_sets = 2, 4 or 8 bucket sets (MsmGeom::top_split)
 int make_geom(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, size_t n, MsmGeom* out, int group_shift = -1,
-              int c_plain = 0) {
+              int c_plain = 0, u32 top_sets = 2) {
   MsmGeom g;
   memset(&g, 0, sizeof(g));
   int c, W;
@@ -153,7 +155,8 @@ int make_geom(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, size_t n,
     if (nn == ~0u) return AMSM_E_INVALID_ARG;
     g.n_narrow = nn;
     g.top_shift = (u32)top_window_shift_curve(ctx->curve, c, W, (int)nn);  // (precomputed keys: set from the key below)
-    g.top_split = 1;
+    if (top_sets != 2u && top_sets != 4u && top_sets != 8u) return AMSM_E_INVALID_ARG;
+    g.top_split = top_sets - 1u;
   } else {
     c = ctx->window_override ? ctx->window_override : msel::key_window(n, false, false);
     W = windows_for(c);
@@ -269,9 +272,10 @@ inline size_t bpl_min_pairs(const amsm_bases*) { return msel::P2(18) + 1; }
 
 // The geometry of an MSM on the bucket-per-lane pipeline (msm_select.h chose it; c_plain = the window of a plain key, 0 for a
 // 20-bit table) -- false when the prep cannot take it (prep_bpl_supported: the caller falls back to the chunked pipeline).
-inline bool bpl_geom(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, size_t n, int group_shift, int c_plain, MsmGeom* out) {
+inline bool bpl_geom_sets(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, size_t n, int group_shift, int c_plain, u32 top_sets,
+                          MsmGeom* out) {
   MsmGeom g;
-  if (make_geom(ctx, bases, base_off, n, &g, group_shift, c_plain) != AMSM_OK) return false;
+  if (make_geom(ctx, bases, base_off, n, &g, group_shift, c_plain, top_sets) != AMSM_OK) return false;
   if (g.groups == 1u && g.precomp) {  // window-relative indices (MsmGeom::idx_rel_bits)
     u32 b = 1;
     while ((1ull << b) < n) b++;
@@ -285,19 +289,36 @@ inline bool bpl_geom(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, si
     // over the part of it its raw values reach (r / 2^256 of the range: no sign to fold, and only as far as top_shift spreads it)
     unsigned long long raw_max = 0;
     (void)top_window_shift_curve(ctx->curve, (int)g.c, (int)g.W, (int)g.n_narrow, &raw_max);
-    unsigned long long top_reach = std::min<unsigned long long>(g.nb, raw_max << (g.top_shift + (g.n_narrow ? 1u : 0u)));
-    top_reach = std::max<unsigned long long>(1024ull, top_reach);
-    const unsigned long long per_win = ((unsigned long long)n * 1024ull + g.nb - 1) / g.nb;  // a regular window's, per partition
-    const unsigned long long per_top = ((unsigned long long)n * 1024ull + top_reach - 1) / top_reach;
-    const unsigned long long wins = g.precomp ? g.W : 1ull;  // windows sharing a bucket set
-    // (a plain key's top window is split over two sets, MsmGeom::top_split; what is sized for is TWICE the uniform load:
-    // scalars a bit short of the field's width -- the 254-bit stream of rng.h on BLS12-381 -- fill half the reach)
-    g.part_max = (u32)std::min<unsigned long long>(0xffffffffull, g.precomp ? (wins - 1ull) * per_win + per_top : std::max(per_win, per_top));
-    if (g.groups > 1u) g.part_max = (g.part_max + 1u) / 2u;  // (a group sees half the scalars)
+    const unsigned long long top_reach = top_window_reach(g.nb, raw_max, g.top_shift, g.n_narrow);
+    if (g.precomp) {  // W windows share one bucket set
+      const unsigned long long per_win = ((unsigned long long)n * 1024ull + g.nb - 1) / g.nb;  // a regular window's, per partition
+      const unsigned long long per_top = ((unsigned long long)n * 1024ull + top_reach - 1) / top_reach;
+      g.part_max = (u32)std::min<unsigned long long>(0xffffffffull, (g.W - 1ull) * per_win + per_top);
+      if (g.groups > 1u) g.part_max = (g.part_max + 1u) / 2u;  // (a group sees half the scalars)
+    } else {
+      // (a plain key's top window is split over T sets, MsmGeom::top_split; what is sized for is TWICE the uniform load of one:
+      // msm_select.h: plain_part_max)
+      g.part_max = (u32)std::min<unsigned long long>(0xffffffffull, msel::plain_part_max(n, g.nb, top_reach, top_sets, g.groups));
+    }
   }
   if (!prep_bpl_supported(g)) return false;
   *out = g;
   return true;
+}
+inline bool bpl_geom(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, size_t n, int group_shift, int c_plain, MsmGeom* out) {
+  if (c_plain <= 0 || bases->precomp) return bpl_geom_sets(ctx, bases, base_off, n, group_shift, c_plain, 2, out);
+  // a plain key: the sets of its top window (msm_select.h: plain_top_sets) -- AMSM_TOP_SETS = 4 / 8 where the prep takes that geometry,
+  // else the smallest count that fits its stage (AMSM_TOP_SETS=2: two or none)
+  if (ctx->top_sets > 2 && bpl_geom_sets(ctx, bases, base_off, n, group_shift, c_plain, (u32)ctx->top_sets, out)) return true;
+  const int W = windows_for(c_plain);
+  const u32 nn = narrow_windows_for((u32)c_plain);
+  if (nn == ~0u) return false;
+  unsigned long long raw_max = 0;
+  const int shift = top_window_shift_curve(ctx->curve, c_plain, W, (int)nn, &raw_max);
+  const u32 nb = 1u << (c_plain - 1);
+  const u32 T = msel::plain_top_sets(n, nb, top_window_reach(nb, raw_max, (u32)shift, nn), (u32)W, group_shift >= 0 ? 2u : 1u,
+                                     msel::BPL_STAGE_CAP, msel::plain_top_sets_cap(ctx->top_sets));
+  return T != 0u && bpl_geom_sets(ctx, bases, base_off, n, group_shift, c_plain, T, out);
 }
 
 // The geometry of an MSM on the bucket-split pipeline (precomputed key, one or two bucket sets, 2^16 .. 2^17 pairs: msm_select.h) --
@@ -583,6 +604,7 @@ int msm_enqueue(amsm_ctx* ctx, Slot* sl, const MsmJob& job, Place place) {
       stage_mark(ctx, sl, ST_BOUNDS, st);
       if (g.bpl != 2) ctx->n_bpl++;
       else if (!job.counted) ctx->n_bps++;  // (a unit's MSM run again on its own was counted with its unit)
+      if (g.bpl == 1u && g.top_split) ctx->n_top_sets[(g.top_split + 1u) / 4u]++;  // (a plain key: amsm_ctx_top_sets_msms)
     } else if (short_prep) {
       // short prep chain (prep_kernels.h: 5 dispatches + 2 for skewed inputs); the stage marks keep their names: "sort" = scatter + local sort
       PrepBuffers pb;
@@ -894,11 +916,12 @@ int msm_collect(amsm_ctx* ctx, Slot* sl, host::HXYZZ<Fq>* out) {
     return msm_collect<Fq>(ctx, sl, out);  // the re-run is chunked: no second fallback
   }
   // one result per group: Horner over the group's window sums (plain key) or its single record (precomputed key)
-  const u32 sets = g.n_sets / g.groups, per = sets - g.top_split;  // per = windows with a sum of their own
+  const u32 sets = g.n_sets / g.groups, per = sets - g.top_split;  // per = windows (the top one owns 1 + top_split sets)
   auto horner = [&](size_t grp) {
     const u32* base = h + grp * sets * (rec / 4);
     host::HXYZZ<Fq> acc = host::hx_from_device<Fq>(base + (size_t)(per - 1) * (rec / 4));
-    if (g.top_split) acc = host::hx_add<Fq>(acc, host::hx_from_device<Fq>(base + (size_t)per * (rec / 4)));  // the top window's second set
+    // the top window's other sets (an empty set's record is the identity)
+    for (u32 k = 0; k < g.top_split; k++) acc = host::hx_add<Fq>(acc, host::hx_from_device<Fq>(base + (size_t)(per + k) * (rec / 4)));
     for (int w = (int)per - 2; w >= 0; w--) {
       // window w's sum counts 2^(e_w): c doublings between equal windows, c - 1 where a narrow one is involved (n_narrow)
       const u32 dbl = per > 1u ? window_exponent(g, (u32)w + 1u) - window_exponent(g, (u32)w) : 0u;

@@ -204,6 +204,8 @@ struct amsm_ctx {
   // environment knob is a measured constant now (namespace tune below; the A/Bs are in profiles/ and DESIGN.md) ----
   bool bpl = true;        // AMSM_BPL=0: no 20-bit tables, no bucket-per-lane pipeline (17-bit windows + the chunked pipeline)
   bool bpl_plain = true;  // AMSM_BPL_PLAIN=0: plain keys stay on the chunked pipeline
+  int top_sets = 0;       // AMSM_TOP_SETS=2|4|8: bucket sets of a plain key's top window on the bucket-per-lane pipeline (unset / 0: the
+                          // rule, msm_select.h: plain_top_sets; 2: never more than two, the behaviour before the rule; A/B and tests)
   int bps = 2;            // AMSM_BPS: bucket-split pipeline 0 never, 1 grouped MSMs only, 2 every candidate of 2^16 .. 2^17 pairs
   int split_log2 = 21;    // AMSM_SPLIT_LOG2: MSMs of 2^22 pairs and more over a key without a 20-bit table run as ranges of 2^this (0: whole)
   unsigned long long n_bps = 0, n_bps_fallbacks = 0;
@@ -217,6 +219,7 @@ struct amsm_ctx {
   bool host_halves = true;  // AMSM_HOST_HALVES=0: a lone host slice over a 20-bit key as ONE range (upload, then the MSM: rounds 1-5; A/B)
   bool bpl_probe = true;  // sample every candidate vector's digits first and send skewed ones straight to the chunked pipeline
                           // (AMSM_BPL_PROBE=0: find out from the prep's overflow flag only -- the safety net either way)
+  unsigned long long n_top_sets[3] = {0, 0, 0};  // plain-key MSMs enqueued there with 2 / 4 / 8 sets for the top window (index sets / 4)
   unsigned long long n_bpl = 0, n_bpl_fallbacks = 0;  // MSMs that took it / that were re-run chunked (skewed digits)
   // MSMs longer than the key's window: one bucket set for all their ranges (struct Share; AMSM_SHARE_BUCKETS=0: independent ranges, A/B)
   bool share_buckets = true;

@@ -100,6 +100,7 @@ constexpr u32 BPL_LOCAL_FIXED_WORDS = 3u * BPL_NB + 2u * BPL_BINS + 2u * BPL_GRO
 constexpr u32 BPL_LOCAL_BUDGET_WORDS = 40960u;
 static_assert(BPL_LOCAL_BUDGET_WORDS - BPL_LOCAL_FIXED_WORDS <= BPL_LOCAL_SLOTS * BPL_NB,
               "k_prep_local_t keeps a partition of CAP entries in BPL_LOCAL_SLOTS registers per lane");
+static_assert(BPL_LOCAL_BUDGET_WORDS - BPL_LOCAL_FIXED_WORDS == msel::BPL_STAGE_CAP, "msm_select.h plans for k_prep_local_t's stage");
 static PrepGeom prep_bpl_geom(const MsmGeom& g) {
   PrepGeom pg;
   pg.SH = 10;
@@ -145,8 +146,8 @@ bool prep_bpl_supported(const MsmGeom& g) {
   if (pg.IB > 30u) return false;
   // the expected partition -- the fullest one -- must fit the LDS stage with room for the digits' spread (sigma ~ 180 entries at
   // 30 k: 1024 on the average partition, 5 sigma on the fullest)
-  if ((unsigned long long)g.E / pg.P + 1024ull > pg.CAP) return false;
-  if (g.part_max && (unsigned long long)g.part_max + 5ull * (unsigned long long)std::sqrt((double)g.part_max) > pg.CAP) return false;
+  // (msm_select.h: bpl_stage_fits states the two inequalities -- the rule that picks a plain key's top sets asks the same question)
+  if (!msel::bpl_stage_fits(g.E, pg.P, g.part_max, pg.CAP)) return false;
   return prep_bpl_scatter_lds(g, pg) <= PREP_LDS_LIMIT && prep_bpl_local_lds(pg) <= PREP_LDS_LIMIT &&
          (unsigned long long)pg.P * prep_bpl_stride(g) < (1ull << 31);
 }

@@ -9,7 +9,8 @@
 //                    table points, no buckets (msm_kernels.h k_direct_sum)
 //   BUCKET_SPLIT     2^16 .. 2^17 pairs over a precomputed key: every bucket on 2 .. 64 adjacent lanes (k_prep_local_s + k_accum_bps)
 //   BUCKET_PER_LANE  (2^18, 2^20] pairs: a lane sums one whole bucket; 20-bit windows over a precomputed key of >= 2^20 generators,
-//                    one bucket set per 16- / 15-bit window over a plain key (k_prep_local_t + k_accum_bpl)
+//                    one bucket set per 16- / 15-bit window over a plain key, 2, 4 or 8 for the top one: plain_top_sets
+//                    (k_prep_local_t + k_accum_bpl)
 //   CHUNKED          everything else, and every vector whose digits are skewed: equal-sized work items whatever the digit
 //                    distribution (k_accum_l0 + k_accum_l1)
 // Longer MSMs are cut into ranges first (`range`), each range is chosen again; the ranges of one vector over a bucket-per-lane key
@@ -17,7 +18,10 @@
 // Table 3, `tail_plan`: the bucket reduction, fold and export behind any of them -- form, grids and what the slot must hold.
 // Beside the tables: `classify`, what a call makes of its vectors' two-valued probes (two-valued, all zero, unit scalars summed apart).
 #pragma once
+#include <math.h>
 #include <stddef.h>
+
+#include <initializer_list>
 
 namespace amsm {
 namespace msel {
@@ -88,6 +92,7 @@ struct Switches {              // the context's documented switches (include/ams
   bool direct = true;          // AMSM_DIRECT_SUM_MAX_LOG2=0: no direct sums
   bool window_override = false;  // amsm_ctx_set_window: everything chunked with that width
   int bps_batch = 8;           // AMSM_BPS_BATCH: bucket-split MSMs per launch (batch_units below); 0 or 1: every MSM a chain of its own
+  int top_sets = 0;            // AMSM_TOP_SETS: bucket sets of a plain key's top window -- 0 the rule (plain_top_sets), 2, 4 or 8
 };
 struct Row {
   KeyKind kind;
@@ -282,6 +287,44 @@ inline void classify(const VecProbe* vec, size_t k, bool mont, const KeyDesc& ke
     }
   }
 }
+
+// ---- plain keys on the bucket-per-lane pipeline: how many bucket sets the TOP window owns --------------------------------------------
+// The prep sorts one 1024-bucket partition per workgroup in an LDS stage of BPL_STAGE_CAP entries (kern_fr.hip asserts the figure
+// against k_prep_local_t's layout).  bpl_stage_fits: the two inequalities every bucket-per-lane geometry must meet (kern_fr.hip:
+// prep_bpl_supported calls it) -- E entries over P partitions, the average one with 1024 to spare, and the fullest one expected on
+// uniform scalars (part_max; 0: not known) with 5 sigma of the digits' spread to spare (sigma = sqrt(part_max): ~180 at 30 k).
+constexpr unsigned BPL_STAGE_CAP = 37340;
+inline bool bpl_stage_fits(unsigned long long E, unsigned long long P, unsigned long long part_max, unsigned cap) {
+  if (P == 0 || E / P + 1024ull > cap) return false;
+  return !(part_max && part_max + 5ull * (unsigned long long)sqrt((double)part_max) > cap);
+}
+// A plain key's top window starts at bit 240 (16-bit windows) or 242 (15-bit): its raw digits reach only (r - 1) >> lo, carry no sign
+// to fold, and top_shift spreads them by a power of two only -- they cover `reach` of the set's nb buckets (msm_types.h:
+// top_window_reach), so a partition of the top window expects n * 1024 / reach entries where the others expect n * 1024 / nb.  The
+// top window therefore owns T bucket sets, picked by index bits (MsmGeom::top_split, window_set), and the stage is sized for TWICE
+// the uniform load of one of them: scalars a bit short of the field's width -- the 254-bit stream of rng.h on BLS12-381 -- fill half
+// the reach.  groups == 2: a group sees half the scalars.
+inline unsigned long long plain_part_max(size_t n, unsigned nb, unsigned long long reach, unsigned T, unsigned groups) {
+  const unsigned long long per_win = ((unsigned long long)n * 1024ull + nb - 1) / nb;  // a regular window's, per partition
+  const unsigned long long per_top = ((unsigned long long)n * 1024ull + reach - 1) / reach;
+  const unsigned long long top = (2ull * per_top + T - 1) / T;
+  const unsigned long long pm = per_win > top ? per_win : top;
+  return groups > 1u ? (pm + 1ull) / 2ull : pm;
+}
+// T: the smallest of 2, 4, 8 (<= max_sets) with which n pairs over W windows of nb buckets fit the stage; 0: none does -- the MSM
+// stays chunked.  T = 2 is what every plain key had before the rule: a shape that fitted then keeps its geometry bit for bit.
+inline unsigned plain_top_sets(size_t n, unsigned nb, unsigned long long reach, unsigned W, unsigned groups, unsigned cap = BPL_STAGE_CAP,
+                               unsigned max_sets = 8) {
+  if (n == 0 || nb < 1024u || reach == 0 || W == 0) return 0;
+  for (unsigned T = 2; T <= max_sets && T <= 8u; T *= 2u) {
+    const unsigned long long P = ((unsigned long long)groups * (W + T) * nb) >> 10;
+    if (bpl_stage_fits((unsigned long long)n * W, P, plain_part_max(n, nb, reach, T, groups), cap)) return T;
+  }
+  return 0;
+}
+// AMSM_TOP_SETS (Switches::top_sets): 0 the rule decides, 2 never more than two sets (the behaviour before the rule), 4 / 8 that
+// many wherever the prep takes the geometry (api_pipeline.inc: bpl_geom falls back to the rule where it does not)
+inline unsigned plain_top_sets_cap(int top_sets) { return top_sets == 2 ? 2u : 8u; }
 
 // ---- table 3: the tail of an MSM -- the bucket reduction (per set sum_j (j + 1) bucket_j), the fold of its partial records, the export ----
 // Where an MSM stands in its call (msm_enqueue): whether anybody waits for its tail, and whether anything can overlap with it

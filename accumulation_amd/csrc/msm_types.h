@@ -65,11 +65,13 @@ struct MsmGeom {
   u32 T0;            // entries covered by phase A = nA * K0
   u32 n_chunks;      // work items of accumulate L0 (upper bound: sized for E entries)
   u32 K1;            // max partials folded by one L1 lane
-  u32 top_split;     // plain keys on the bucket-per-lane pipeline (round 4): the TOP window owns two bucket sets, the scalars with an
-                     // even index feed the first, the odd ones the second (the host adds the two sums) -- its digits reach only
-                     // r / 2^256 of their range and carry no sign to fold, so its partitions run 10 % fuller than the others' on
-                     // uniform BLS12-381 scalars and twice as full on 254-bit ones (the synthetic stream of rng.h); sets per group
-                     // = W + top_split
+  u32 top_split;     // plain keys on the bucket-per-lane pipeline: the TOP window owns T = top_split + 1 = 2, 4 or 8 bucket sets (a mask:
+                     // 1, 3 or 7), picked by log2 T low bits of the scalar's index that leave the group's bit out (window_set); the
+                     // host adds the T sums (msm_collect) -- its digits reach only (r - 1) >> lo of their range and carry no sign to
+                     // fold, so its partitions run 10 % fuller than the others' on uniform BLS12-381 scalars, 1.3 times on BN254 /
+                     // Grumpkin and 1.7 times on BLS12-377, and twice that on scalars a bit short of the field's width (the
+                     // synthetic stream of rng.h).  T is the smallest that fits the prep's stage (msm_select.h: plain_top_sets;
+                     // 2 wherever 2 fits); sets per group = W + top_split
   u32 part_max;      // host only (bucket-per-lane prep): entries the fullest partition is expected to hold on uniform scalars -- the
                      // top window's digits cover only r / 2^256 of its range (no sign to fold), 10 % denser than the others'
                      // on BLS12-381; a plain key gives that window a bucket set of its own
@@ -129,12 +131,54 @@ AMSM_GEOM_FN u32 narrow_windows_for(u32 c) {
   const u32 W = 255u / c + 1u, nn = W * c - 256u;
   return nn < W ? nn : ~0u;
 }
+// MsmGeom::top_shift for window width c over the scalar field of modulus `mod` (8 little-endian words, odd): the largest s for which
+// every CANONICAL scalar's top digit, shifted left by s (on top of the doubling of a narrow window), stays <= 2^(c - 1) (never
+// negative, no carry out).  The top window starts at bit lo: its raw value is at most top(r - 1), plus the recoding's carry from the
+// window below -- which cannot arrive when the scalars that reach the maximum have nothing in that window (Pallas: r = 2^254 +
+// 2^125.1, so the maximal top value forces bits 126..253 to zero).  *raw_max_out: the largest raw top digit.  Host only, no HIP:
+// tests/cpp_host/top_sets_check.cpp pins it for every curve.
+inline int top_window_shift_of(const u32 mod[8], int c, int W, int n_narrow = 0, unsigned long long* raw_max_out = nullptr) {
+  const int lo = (int)window_position_of((u32)c, (u32)W, (u32)n_narrow, (u32)W - 1u);
+  const int narrow = n_narrow > 0 ? 1 : 0;  // (the narrow windows are the top ones)
+  if (raw_max_out) *raw_max_out = 0;
+  if (lo >= 255 || c < 2 || W < 2) return 0;
+  u32 r1[8];  // r - 1
+  for (int i = 0; i < 8; i++) r1[i] = mod[i];
+  r1[0] -= 1u;  // r is odd
+  auto bits = [&](int from, int n) -> unsigned long long {  // n <= 32 bits of r - 1 starting at bit `from`
+    unsigned long long v = 0;
+    for (int k = 0; k < n; k++) {
+      int bit = from + k;
+      if (bit >= 0 && bit < 256 && ((r1[bit >> 5] >> (bit & 31)) & 1u)) v |= 1ull << k;
+    }
+    return v;
+  };
+  const unsigned long long top = bits(lo, 256 - lo < 32 ? 256 - lo : 32);
+  // can a scalar with the maximal top value receive a carry?  Only if its window below can exceed half its range (a carry into
+  // THAT window included): its raw value there is at most the field of r - 1
+  const int cb = (int)window_bits_of((u32)c, (u32)W, (u32)n_narrow, (u32)W - 2u);
+  const unsigned long long below = bits(lo - cb, cb);
+  const unsigned long long raw_max = top + (below + 1ull > (1ull << (cb - 1)) ? 1ull : 0ull);
+  if (raw_max_out) *raw_max_out = raw_max;
+  const unsigned long long half = 1ull << (c - 1);
+  int s = 0;
+  while (s + 1 < c && (raw_max << (narrow + s + 1)) <= half) s++;
+  return raw_max == 0 ? 0 : s;
+}
+// buckets of its set's nb that the top window's digits reach (at least one partition of 1024): what its n entries spread over
+inline unsigned long long top_window_reach(u32 nb, unsigned long long raw_max, u32 top_shift, u32 n_narrow) {
+  unsigned long long reach = raw_max << (top_shift + (n_narrow ? 1u : 0u));
+  if (reach > nb) reach = nb;
+  return reach < 1024ull ? 1024ull : reach;
+}
 // bucket sets per group / the set window w of scalar i feeds, relative to its group's first
 AMSM_GEOM_FN u32 sets_per_group(const MsmGeom& g) { return g.precomp ? 1u : g.W + g.top_split; }
 AMSM_GEOM_FN u32 window_set(const MsmGeom& g, u32 w, u32 i) {
-  // (the bit that splits the top window must not be the bit that picks the group: a group would feed ONE of its two top sets)
-  const u32 sb = (g.groups > 1u && g.group_shift == 0u) ? 1u : 0u;
-  return g.precomp ? 0u : w + ((g.top_split && w == g.W - 1u) ? ((i >> sb) & 1u) : 0u);
+  // the top window's set: the low bits of i under the mask top_split -- with the bit that picks the group squeezed out first (a
+  // group would feed half, a quarter or one of its top sets otherwise); a group bit above the mask changes nothing
+  const u32 gs = g.group_shift;
+  const u32 j = (g.groups > 1u && gs < 3u) ? ((i & ((1u << gs) - 1u)) | ((i >> (gs + 1u)) << gs)) : i;
+  return g.precomp ? 0u : w + ((w == g.W - 1u) ? (j & g.top_split) : 0u);
 }
 // interchange index -> table index (see idx_rel_bits)
 AMSM_GEOM_FN u32 entry_abs_index(const MsmGeom& g, u32 v) {

@@ -125,6 +125,11 @@ class Context:
                 "shared_bucket_sets": int(self._lib.amsm_ctx_shared_bucket_msms(self._h)),
                 "unit_scalar_sums": int(self._lib.amsm_ctx_unit_scalar_msms(self._h))}
 
+    def top_sets_stats(self) -> dict:
+        """plain-key MSMs on the bucket-per-lane pipeline by the bucket sets their top window owned: {2: .., 4: .., 8: ..}
+        (amsm_ctx_top_sets_msms; AMSM_TOP_SETS forces a count)"""
+        return {t: int(self._lib.amsm_ctx_top_sets_msms(self._h, t)) for t in (2, 4, 8)}
+
     def trim(self):
         """Release the MSM workspace and every cached buffer (amsm_ctx_trim); live vectors and keys stay."""
         self.empty_cache()

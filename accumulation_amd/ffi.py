@@ -61,6 +61,7 @@ SIGNATURES = {
     "amsm_ctx_unit_scalar_msms": (C.c_ulonglong, [_vp]),
     "amsm_ctx_direct_sum_msms": (C.c_ulonglong, [_vp]),
     "amsm_ctx_shared_bucket_msms": (C.c_ulonglong, [_vp]),
+    "amsm_ctx_top_sets_msms": (C.c_ulonglong, [_vp, C.c_int]),
     "amsm_ctx_pipeline_stats": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "amsm_ctx_pipeline_stats_small": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "amsm_ctx_batched_split_stats": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),

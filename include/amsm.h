@@ -174,6 +174,12 @@ unsigned long long amsm_ctx_direct_sum_msms(const amsm_ctx* ctx);
  * one bucket reduction and one fold per MSM instead of one per range (round 5).  A range whose digits turn out skewed sends the
  * whole MSM back to independent ranges; results do not depend on the path. */
 unsigned long long amsm_ctx_shared_bucket_msms(const amsm_ctx* ctx);
+/* MSMs over a PLAIN key that took the bucket-per-lane pipeline with `sets` = 2, 4 or 8 bucket sets for their TOP window (0 for any other
+ * `sets`).  A plain key's top window starts at bit 240 / 242: its digits reach only (r - 1) >> that of their range, so its partitions of
+ * the bucket range run fuller than the other windows' -- 1.3 times on BN254 / Grumpkin, 1.7 times on BLS12-377 -- and the window is
+ * split over as many sets, picked by index bits, as the prep's stage needs (2 wherever 2 fit; AMSM_TOP_SETS forces a count).  Results
+ * do not depend on it. */
+unsigned long long amsm_ctx_top_sets_msms(const amsm_ctx* ctx, int sets);
 /* Which accumulation pipeline the context's MSMs took so far: *n_bucket_per_lane = MSMs enqueued on the bucket-per-lane
  * pipeline (keys of >= 2^20 generators, MSMs of (2^19, 2^20] pairs -- longer ones as windows of 2^20; 20-bit windows, 13
  * gathered additions per pair), *n_fallbacks = those whose scalars turned out skewed (a digit value shared by a large part of
