@@ -42,6 +42,7 @@ using namespace amsm;
 
 namespace {
 
+#include "api_gate.inc"
 #include "api_pipeline.inc"
 #include "api_keys.inc"
 #include "api_host.inc"

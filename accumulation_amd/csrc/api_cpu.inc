@@ -8,11 +8,6 @@
 // still fails with AMSM_E_NO_DEVICE.  Results are the same canonical affine points / field elements the HIP path produces.
 namespace cpu {
 
-inline void* h_alloc(size_t bytes) {
-  void* p = nullptr;
-  if (posix_memalign(&p, 64, std::max<size_t>(bytes, 64)) != 0) return nullptr;
-  return p;
-}
 template <class Fq>
 constexpr size_t pt_words() {  // u64 words of one affine point
   return 2 * host::HFe<Fq>::N;
@@ -43,15 +38,14 @@ inline void st(void* p, size_t i, const host::HFe<Fr>& x) {
 
 // ---- keys ----------------------------------------------------------------------------------------------------------
 template <class Fq>
-amsm_bases* bases_new(const amsm_ctx* c, size_t n) {
+amsm_bases* bases_new(amsm_ctx* c, size_t n) {
   amsm_bases* b = new (std::nothrow) amsm_bases();
   if (!b) return nullptr;
   b->curve = c->curve;
   b->device = c->device;
   b->host = true;
   b->n = n;
-  b->d_table = (u32*)h_alloc(std::max<size_t>(n, 1) * affine_bytes<Fq>());
-  if (!b->d_table) {
+  if (gate_alloc(c, GATE_HOST, std::max<size_t>(n, 1) * affine_bytes<Fq>(), false, (void**)&b->d_table) != AMSM_OK) {
     delete b;
     return nullptr;
   }

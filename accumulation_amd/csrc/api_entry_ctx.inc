@@ -28,6 +28,10 @@ static size_t pool_cap_from_env(size_t dflt) {
   const char* e = getenv("AMSM_POOL_MAX_MB");
   return e ? (size_t)std::max(0, atoi(e)) << 20 : dflt;
 }
+static size_t mem_limit_from_env() {  // AMSM_MEM_LIMIT_MB: amsm_ctx_set_memory_limit at creation (unset, 0 or not a number: no limit)
+  const char* e = getenv("AMSM_MEM_LIMIT_MB");
+  return e ? (size_t)std::max(0ll, atoll(e)) << 20 : 0;
+}
 int amsm_ctx_create(amsm_ctx** out, int curve, int device_id, void* stream) {
   if (!out) return AMSM_E_INVALID_ARG;
   *out = nullptr;
@@ -40,6 +44,8 @@ int amsm_ctx_create(amsm_ctx** out, int curve, int device_id, void* stream) {
     c->device = AMSM_DEVICE_HOST;
     c->host_only = true;
     c->pool_cap_bytes = pool_cap_from_env(c->pool_cap_bytes);
+    c->gate.limit = mem_limit_from_env();
+    ctx_bind_bufs(c);
     *out = c;
     return AMSM_OK;
   }
@@ -51,6 +57,7 @@ int amsm_ctx_create(amsm_ctx** out, int curve, int device_id, void* stream) {
   if (!c) return AMSM_E_OOM;
   c->curve = curve;
   c->device = device_id;
+  ctx_bind_bufs(c);
   bool ok = true;
   if (stream) {
     c->stream = (hipStream_t)stream;
@@ -90,6 +97,7 @@ int amsm_ctx_create(amsm_ctx** out, int curve, int device_id, void* stream) {
   }
   // the documented switches (include/amsm.h "Environment")
   c->pool_cap_bytes = pool_cap_from_env(c->pool_cap_bytes);
+  c->gate.limit = mem_limit_from_env();
   if (const char* e = getenv("AMSM_BPL")) c->bpl = atoi(e) != 0;
   if (const char* e = getenv("AMSM_BPL_PLAIN")) c->bpl_plain = atoi(e) != 0;
   if (const char* e = getenv("AMSM_TOP_SETS")) {
@@ -110,8 +118,6 @@ int amsm_ctx_create(amsm_ctx** out, int curve, int device_id, void* stream) {
   return AMSM_OK;
 }
 
-static void pool_release_all(amsm_ctx* c);
-static void pool_forget_ctx(amsm_ctx* c);
 void amsm_ctx_destroy(amsm_ctx* c) {
   if (!c) return;
   if (c->parent) return;  // a shard context is borrowed: it goes with its parent
@@ -132,6 +138,7 @@ void amsm_ctx_destroy(amsm_ctx* c) {
   if (c->host_only) {
     pool_release_all(c);
     pool_forget_ctx(c);
+    gate_forget_ctx(c);
     delete c;
     return;
   }
@@ -141,14 +148,12 @@ void amsm_ctx_destroy(amsm_ctx* c) {
   if (c->s_tail) (void)hipStreamSynchronize(c->s_tail);
   if (c->s_copy) (void)hipStreamSynchronize(c->s_copy);
   if (c->s_tv) (void)hipStreamSynchronize(c->s_tv);
-  auto free_buf = [](DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-  };
+  auto free_buf = [](DevBuf& b) { b.release(); };
   for_each_ctx_buf(c, free_buf);
   for (int k = 0; k < N_SLOTS; k++) {
     Slot* sl = &c->slot[k];
     for_each_slot_buf(sl, free_buf);
-    if (sl->h_pinned) (void)hipHostFree(sl->h_pinned);
+    (void)gate_free(sl->h_pinned);
     for (int i = 0; i <= ST_COUNT; i++)
       if (sl->ev[i]) (void)hipEventDestroy(sl->ev[i]);
     if (sl->ev_prep_end) (void)hipEventDestroy(sl->ev_prep_end);
@@ -167,11 +172,12 @@ void amsm_ctx_destroy(amsm_ctx* c) {
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->shared_free)
     if (e) (void)hipEventDestroy(e);
-  if (c->tv_pinned) (void)hipHostFree(c->tv_pinned);
+  (void)gate_free(c->tv_pinned);
   if (c->s_tv) (void)hipStreamDestroy(c->s_tv);
   if (c->tv_done) (void)hipEventDestroy(c->tv_done);
   pool_release_all(c);
   pool_forget_ctx(c);
+  gate_forget_ctx(c);
   if (c->multi_fork) (void)hipEventDestroy(c->multi_fork);
   delete c;
 }
@@ -197,6 +203,10 @@ static int ctx_create_multi_impl(amsm_ctx*& c, amsm_ctx** out, int curve, const 
     c = nullptr;
     return AMSM_E_HIP;
   }
+  // A memory limit over several devices' books is not defined yet (include/amsm.h: the setters refuse such a context), so the
+  // environment's limit, which amsm_ctx_create gave every shard, does not apply either: it could not be changed or read afterwards
+  if (n_dev > 1)
+    for (amsm_ctx* cg : c->shard_ctx) cg->gate.limit = 0;
   (void)hipSetDevice(c->device);
   const char* want = getenv("AMSM_COLLECTIVE");  // "rccl" (fail if unavailable) | "peer" | unset (RCCL when possible)
   const bool force_rccl = want && strcmp(want, "rccl") == 0, force_peer = want && strcmp(want, "peer") == 0;
@@ -305,6 +315,41 @@ int amsm_ctx_set_table_budget(amsm_ctx* c, size_t bytes) {
   if (!c) return AMSM_E_INVALID_ARG;
   c->table_budget = bytes;
   for (size_t g = 1; g < c->shard_ctx.size(); g++) c->shard_ctx[g]->table_budget = bytes;
+  return AMSM_OK;
+}
+
+// ---- the allocation gate (api_gate.inc) ----
+int amsm_ctx_set_memory_limit(amsm_ctx* c, size_t bytes) {
+  if (!c) return AMSM_E_INVALID_ARG;
+  if (c->shard_ctx.size() > 1 || c->parent) return AMSM_E_UNSUPPORTED;  // (one limit over several devices' books: not defined yet)
+  std::lock_guard<std::mutex> lk(gate_mu());
+  c->gate.limit = bytes;
+  c->gate.peak = c->gate.held;  // the peak is counted anew: what was held at most BEFORE the limit says nothing about the limit
+  return AMSM_OK;
+}
+int amsm_ctx_memory_held(const amsm_ctx* c, size_t out[4]) {
+  if (!c || !out) return AMSM_E_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(gate_mu());
+  out[0] = c->gate.held;
+  out[1] = c->gate.peak;
+  out[2] = c->gate.limit;
+  out[3] = c->gate.pinned;
+  return AMSM_OK;
+}
+int amsm_ctx_fail_alloc_after(amsm_ctx* c, long n) {
+  if (!c) return AMSM_E_INVALID_ARG;
+  if (c->shard_ctx.size() > 1 || c->parent) return AMSM_E_UNSUPPORTED;
+  std::lock_guard<std::mutex> lk(gate_mu());
+  c->gate.fail_after = n < 0 ? -1 : n;
+  return AMSM_OK;
+}
+int amsm_ctx_alloc_stats(const amsm_ctx* c, unsigned long long out[4]) {
+  if (!c || !out) return AMSM_E_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(gate_mu());
+  out[0] = c->gate.requests;
+  out[1] = c->gate.refused_limit;
+  out[2] = c->gate.refused_hook;
+  out[3] = c->gate.failed_driver;
   return AMSM_OK;
 }
 

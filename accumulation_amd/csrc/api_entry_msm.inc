@@ -181,7 +181,7 @@ void amsm_bases_free(amsm_bases* b) {
   if (b->alt) amsm_bases_free(b->alt);
   b->alt = nullptr;
   if (b->host) {
-    free(b->d_table);
+    (void)gate_free(b->d_table);
     delete b;
     return;
   }
@@ -190,9 +190,9 @@ void amsm_bases_free(amsm_bases* b) {
     (void)hipEventSynchronize(b->ready);
     (void)hipEventDestroy(b->ready);
   }
-  if (b->d_table) (void)hipFree(b->d_table);
-  if (b->d_small) (void)hipFree(b->d_small);
-  if (b->d_abi) (void)hipFree(b->d_abi);
+  (void)gate_free(b->d_table);
+  (void)gate_free(b->d_small);
+  (void)gate_free(b->d_abi);
   delete b;
 }
 

@@ -15,45 +15,14 @@ int amsm_vec_fill(amsm_ctx* c, const uint64_t* value_mont, size_t n, void* d_out
   return AMSM_OK;
 }
 
-static size_t pool_round(size_t bytes) {  // 256-byte granules up to 1 MiB, 64-KiB granules above
-  bytes = std::max<size_t>(bytes, 16);
-  const size_t g = bytes <= ((size_t)1 << 20) ? 256 : 65536;
-  return (bytes + g - 1) / g * g;
-}
-// Which context's bookkeeping a buffer belongs to.  Two contexts can share a GPU (a multi-device context that lists a device
-// twice, two callers) and a wrapper may free a vector through the other one: the owner's `pool_size` entry and live-byte
-// count must follow, and the buffer must not enter a free list whose stream-order argument (api_types.h) does not cover
-// the consumer.  Every allocator operation takes this one lock (they are rare next to kernel launches).
-static std::mutex g_pool_mu;
-static std::unordered_map<void*, amsm_ctx*>& pool_owner() {
-  static std::unordered_map<void*, amsm_ctx*> m;
-  return m;
-}
-static void pool_release_all(amsm_ctx* c) {
-  std::lock_guard<std::mutex> lk(g_pool_mu);
-  for (auto& kv : c->pool)
-    for (void* p : kv.second) {
-      (void)hipFree(p);
-      c->pool_size.erase(p);
-      pool_owner().erase(p);
-    }
-  c->pool.clear();
-  c->pool_free_bytes = 0;
-}
-// the context goes away: buffers it handed out and never got back stay allocated (the caller still holds them) but no
-// longer point at it
-static void pool_forget_ctx(amsm_ctx* c) {
-  std::lock_guard<std::mutex> lk(g_pool_mu);
-  for (auto& kv : c->pool_size) pool_owner().erase(kv.first);
-  c->pool_size.clear();
-  c->pool_live_bytes = 0;
-}
+// (the pool's books -- pool_round, g_pool_mu, pool_owner, pool_release_all, pool_forget_ctx -- are in api_gate.inc)
 int amsm_dev_alloc(amsm_ctx* c, size_t bytes, void** d_ptr) {
   if (!c || !d_ptr) return AMSM_E_INVALID_ARG;
   if (c->host_only) {  // host memory, no free lists (malloc does not synchronise anything)
     const size_t hsz = pool_round(bytes);
-    *d_ptr = cpu::h_alloc(hsz);
-    if (!*d_ptr) return AMSM_E_OOM;
+    void* hp = nullptr;  // (*d_ptr is written on success only: the contract after AMSM_E_OOM, include/amsm.h)
+    TRY(gate_alloc(c, GATE_HOST, hsz, false, &hp));
+    *d_ptr = hp;
     std::lock_guard<std::mutex> lk(g_pool_mu);
     c->pool_size[*d_ptr] = hsz;
     c->pool_live_bytes += hsz;
@@ -72,17 +41,21 @@ int amsm_dev_alloc(amsm_ctx* c, size_t bytes, void** d_ptr) {
       return AMSM_OK;
     }
   }
-  hipError_t e = hipMalloc(d_ptr, sz);
-  if (e != hipSuccess) {  // give the free lists back to the driver and try once more
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(c->stream);
+  int why = GATE_GRANTED;
+  void* p = nullptr;  // (*d_ptr is written on success only: the contract after AMSM_E_OOM, include/amsm.h)
+  int rc = gate_alloc(c, GATE_DEVICE, sz, true, &p, &why);
+  if (rc != AMSM_OK && why == GATE_BY_DRIVER) {  // give the free lists back to the driver and try once more (a refusal by the
+    (void)hipStreamSynchronize(c->stream);       // limit has done so already; one by the test hook stands)
     pool_release_all(c);
-    e = hipMalloc(d_ptr, sz);
+    rc = gate_alloc(c, GATE_DEVICE, sz, true, &p);
   }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
+  if (rc != AMSM_OK) {
+    // (asked for as tolerated because of the second try above; for the caller -- the library's own scratch vectors included, which may
+    // have queued work before they asked: t_vecs_impl -- the vector was required: nothing stays in flight)
+    gate_drain(c);
     return AMSM_E_OOM;
   }
+  *d_ptr = p;
   std::lock_guard<std::mutex> lk(g_pool_mu);
   c->pool_size[*d_ptr] = sz;
   c->pool_live_bytes += sz;
@@ -100,7 +73,7 @@ int amsm_dev_free(amsm_ctx* c, void* d_ptr) {
       c->pool_live_bytes -= it->second;
       c->pool_size.erase(it);
     }
-    free(d_ptr);
+    (void)gate_free(d_ptr);
     return AMSM_OK;
   }
   TRY(bind_device(c));
@@ -122,7 +95,7 @@ int amsm_dev_free(amsm_ctx* c, void* d_ptr) {
       pool_owner().erase(ow);
     }
     lk.unlock();
-    HIP_TRY(hipFree(d_ptr));
+    HIP_TRY(gate_free(d_ptr));
     return AMSM_OK;
   }
   const size_t sz = it->second;
@@ -131,7 +104,7 @@ int amsm_dev_free(amsm_ctx* c, void* d_ptr) {
     c->pool_size.erase(it);
     pool_owner().erase(d_ptr);
     lk.unlock();
-    HIP_TRY(hipFree(d_ptr));
+    HIP_TRY(gate_free(d_ptr));
     return AMSM_OK;
   }
   c->pool[sz].push_back(d_ptr);
@@ -156,10 +129,7 @@ int amsm_ctx_trim(amsm_ctx* c) {
   TRY(amsm_ctx_synchronize(c));
   pool_release_all(c);
   if (c->s_copy) (void)hipStreamSynchronize(c->s_copy);
-  auto release = [](DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b = DevBuf();
-  };
+  auto release = [](DevBuf& b) { b.release(); };
   for_each_ctx_buf(c, release);
   for (Slot& sl : c->slot) for_each_slot_buf(&sl, release);
   return AMSM_OK;
@@ -240,8 +210,7 @@ int amsm_bases_from_device(amsm_ctx* c, const void* d_xy, size_t n, unsigned fla
   b->device = c->device;
   b->n = n;
   size_t pb = DISPATCH(c, affine_bytes<Fq>());
-  if (hipMalloc((void**)&b->d_table, std::max<size_t>(n, 1) * pb) != hipSuccess) {
-    (void)hipGetLastError();
+  if (gate_alloc(c, GATE_DEVICE, std::max<size_t>(n, 1) * pb, false, (void**)&b->d_table) != AMSM_OK) {
     delete b;
     return AMSM_E_OOM;
   }
@@ -257,8 +226,9 @@ int amsm_bases_from_device(amsm_ctx* c, const void* d_xy, size_t n, unsigned fla
       s = DISPATCH(c, bases_finish<Fq, Fr>(c, b, (flags & ~(unsigned)AMSM_BASES_CHECK) ? flags : AMSM_BASES_NO_PRECOMPUTE));
   }
   if (s != AMSM_OK) {
-    (void)hipFree(b->d_table);
-    delete b;
+    (void)hipStreamSynchronize(c->stream);  // (the copy into the table may still run)
+    (void)hipGetLastError();
+    bases_discard(b);
     return s;
   }
   *out = b;
@@ -278,13 +248,12 @@ const void* amsm_bases_device_ptr(const amsm_bases* b) {
     int prev = 0;
     if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(b->device) != hipSuccess) return nullptr;
     u32* p = nullptr;
-    bool ok = hipMalloc((void**)&p, b->n * pb) == hipSuccess;
+    // on the books of the context that holds the key's table (if it still lives).  Tolerated: the caller gets a null pointer
+    bool ok = gate_alloc(gate_owner_of(b->d_table), GATE_DEVICE, b->n * pb, true, (void**)&p) == AMSM_OK;
     if (ok) {
       DISPATCH_DO(b, launch_points_export<Fq>(nullptr, b->d_table, p, (u32)b->n));
       ok = hipStreamSynchronize(nullptr) == hipSuccess && hipGetLastError() == hipSuccess;
-      if (!ok) (void)hipFree(p);
-    } else {
-      (void)hipGetLastError();
+      if (!ok) (void)gate_free(p);
     }
     (void)hipSetDevice(prev);
     if (ok) b->d_abi = p;
@@ -351,8 +320,7 @@ int amsm_bases_fold(amsm_ctx* c, const amsm_bases* key, size_t n_half, const uin
   b->curve = c->curve;
   b->device = c->device;
   b->n = n_half;
-  if (hipMalloc((void**)&b->d_table, n_half * pb) != hipSuccess) {
-    (void)hipGetLastError();
+  if (gate_alloc(c, GATE_DEVICE, n_half * pb, false, (void**)&b->d_table) != AMSM_OK) {
     delete b;
     return AMSM_E_OOM;
   }
@@ -374,7 +342,8 @@ int amsm_bases_fold(amsm_ctx* c, const amsm_bases* key, size_t n_half, const uin
       hipEventRecord(b->ready, c->stream) != hipSuccess) {
     (void)hipGetLastError();
     if (b->ready) (void)hipEventDestroy(b->ready);
-    (void)hipFree(b->d_table);
+    (void)hipStreamSynchronize(c->stream);
+    (void)gate_free(b->d_table);
     delete b;
     return AMSM_E_HIP;
   }
@@ -541,10 +510,9 @@ int amsm_matrix_load(amsm_ctx* c, const uint32_t* row_ptr, const uint32_t* col_i
   m->nnz = nnz;
   if (c->host_only) {
     m->host = true;
-    m->d_row_ptr = (u32*)cpu::h_alloc((n_rows + 1) * 4);
-    m->d_col = (u32*)cpu::h_alloc(std::max<size_t>(nnz, 1) * 4);
-    m->d_val = (u32*)cpu::h_alloc(std::max<size_t>(nnz, 1) * 32);
-    if (!m->d_row_ptr || !m->d_col || !m->d_val) {
+    if (gate_alloc(c, GATE_HOST, (n_rows + 1) * 4, false, (void**)&m->d_row_ptr) != AMSM_OK ||
+        gate_alloc(c, GATE_HOST, std::max<size_t>(nnz, 1) * 4, false, (void**)&m->d_col) != AMSM_OK ||
+        gate_alloc(c, GATE_HOST, std::max<size_t>(nnz, 1) * 32, false, (void**)&m->d_val) != AMSM_OK) {
       amsm_matrix_free(m);
       return AMSM_E_OOM;
     }
@@ -556,15 +524,19 @@ int amsm_matrix_load(amsm_ctx* c, const uint32_t* row_ptr, const uint32_t* col_i
     *out = m;
     return AMSM_OK;
   }
-  bool ok = hipMalloc((void**)&m->d_row_ptr, (n_rows + 1) * 4) == hipSuccess &&
-            hipMalloc((void**)&m->d_col, std::max<size_t>(nnz, 1) * 4) == hipSuccess &&
-            hipMalloc((void**)&m->d_val, std::max<size_t>(nnz, 1) * 32) == hipSuccess;
-  ok = ok && hipMemcpyAsync(m->d_row_ptr, row_ptr, (n_rows + 1) * 4, hipMemcpyHostToDevice, c->stream) == hipSuccess;
+  // (the three arrays: a refusal of the second or third leaves the earlier ones to amsm_matrix_free below)
+  if (gate_alloc(c, GATE_DEVICE, (n_rows + 1) * 4, false, (void**)&m->d_row_ptr) != AMSM_OK ||
+      gate_alloc(c, GATE_DEVICE, std::max<size_t>(nnz, 1) * 4, false, (void**)&m->d_col) != AMSM_OK ||
+      gate_alloc(c, GATE_DEVICE, std::max<size_t>(nnz, 1) * 32, false, (void**)&m->d_val) != AMSM_OK) {
+    amsm_matrix_free(m);
+    return AMSM_E_OOM;
+  }
+  bool ok = hipMemcpyAsync(m->d_row_ptr, row_ptr, (n_rows + 1) * 4, hipMemcpyHostToDevice, c->stream) == hipSuccess;
   if (ok && nnz) {
     ok = hipMemcpyAsync(m->d_col, col_idx, nnz * 4, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
          hipMemcpyAsync(m->d_val, vals, nnz * 32, hipMemcpyHostToDevice, c->stream) == hipSuccess;
   }
-  ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
+  ok = hipStreamSynchronize(c->stream) == hipSuccess && ok;  // (synchronised either way: the arrays are freed below)
   if (!ok) {
     (void)hipGetLastError();
     amsm_matrix_free(m);
@@ -577,16 +549,16 @@ size_t amsm_matrix_rows(const amsm_matrix* m) { return m ? m->n_rows : 0; }
 void amsm_matrix_free(amsm_matrix* m) {
   if (!m) return;
   if (m->host) {
-    free(m->d_row_ptr);
-    free(m->d_col);
-    free(m->d_val);
+    (void)gate_free(m->d_row_ptr);
+    (void)gate_free(m->d_col);
+    (void)gate_free(m->d_val);
     delete m;
     return;
   }
   (void)hipSetDevice(m->device);
-  if (m->d_row_ptr) (void)hipFree(m->d_row_ptr);
-  if (m->d_col) (void)hipFree(m->d_col);
-  if (m->d_val) (void)hipFree(m->d_val);
+  (void)gate_free(m->d_row_ptr);
+  (void)gate_free(m->d_col);
+  (void)gate_free(m->d_val);
   delete m;
 }
 int amsm_matrix_vec_mul(amsm_ctx* c, const amsm_matrix* m, const void* d_input, size_t n_input, const void* d_witness,

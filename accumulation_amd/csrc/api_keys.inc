@@ -43,12 +43,17 @@ int bases_precompute(amsm_ctx* ctx, amsm_bases* b, int c, bool requested, int to
   if ((unsigned long long)b->n * W >= (1ull << 30))  // entry words carry a 30-bit table index
     return requested ? AMSM_E_UNSUPPORTED : AMSM_OK;
   u32* table = nullptr;
-  hipError_t e = hipMalloc((void**)&table, (size_t)b->n * W * affine_bytes<Fq>());
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
+  if (gate_alloc(ctx, GATE_DEVICE, (size_t)b->n * W * affine_bytes<Fq>(), !requested, (void**)&table) != AMSM_OK)
     return requested ? AMSM_E_OOM : AMSM_OK;  // not enough HBM for W copies
-  }
-  HIP_TRY(hipMemcpyAsync(table, b->d_table, b->n * affine_bytes<Fq>(), hipMemcpyDeviceToDevice, ctx->stream));
+  // (from here on the table is this function's: every way out without it gives it back)
+  auto fail = [&](hipError_t e) {
+    fprintf(stderr, "[amsm] HIP error %s (%d) in bases_precompute\n", hipGetErrorName(e), (int)e);
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipGetLastError();
+    (void)gate_free(table);
+    return e == hipErrorOutOfMemory ? AMSM_E_OOM : AMSM_E_HIP;
+  };
+  if (hipError_t e = hipMemcpyAsync(table, b->d_table, b->n * affine_bytes<Fq>(), hipMemcpyDeviceToDevice, ctx->stream)) return fail(e);
   u32* scratch = nullptr;
   // small keys with plain power-of-two levels (round 4): every level in ONE pass and one batched conversion (2^12 generators:
   // 31 launches of 150 us -> 2 launches)
@@ -64,13 +69,11 @@ int bases_precompute(amsm_ctx* ctx, amsm_bases* b, int c, bool requested, int to
                     window_exponent_of((u32)c, (u32)W, (u32)n_narrow, (u32)top_shift, (u32)w - 1u);
     launch_precompute_level<Fq>(ctx->stream, table, (u32)b->n, (u32)w, dbl, scratch);
   }
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  HIP_TRY(hipGetLastError());
-  if (scratch || (all_at_once && ctx->xyzz_scratch.bytes > ((size_t)256 << 20))) {  // a key-sized buffer: not worth keeping between the rare key loads
-    (void)hipFree(ctx->xyzz_scratch.p);
-    ctx->xyzz_scratch = DevBuf();
-  }
-  HIP_TRY(hipFree(b->d_table));
+  if (hipError_t e = hipStreamSynchronize(ctx->stream)) return fail(e);
+  if (hipError_t e = hipGetLastError()) return fail(e);
+  if (scratch || (all_at_once && ctx->xyzz_scratch.bytes > ((size_t)256 << 20)))  // a key-sized buffer: not worth keeping between the rare key loads
+    ctx->xyzz_scratch.release();
+  (void)gate_free(b->d_table);
   b->d_table = table;
   b->precomp = 1;
   b->c = c;
@@ -100,21 +103,23 @@ int bases_direct_table(amsm_ctx* ctx, amsm_bases* b, unsigned flags) {
   if (flags & AMSM_BASES_NO_DIRECT_TABLE) return deny(DENIED_BY_FLAG);
   if (pts * affine_bytes<Fq>() > ctx->table_budget) return deny(DENIED_BY_BUDGET);
   u32* t = nullptr;
-  if (hipMalloc((void**)&t, pts * affine_bytes<Fq>()) != hipSuccess) {
-    (void)hipGetLastError();
-    return deny(DENIED_BY_OOM);
-  }
+  if (gate_alloc(ctx, GATE_DEVICE, pts * affine_bytes<Fq>(), true, (void**)&t) != AMSM_OK) return deny(DENIED_BY_OOM);
   // slabs of the 64 four-bit windows so that the XYZZ scratch stays at or below 256 MiB (the whole table at once needed 2-3 GiB for a
   // 2^15-generator key)
   u32 slab = DS_W;
   while (slab > 1u && (size_t)DS_MULT * slab * b->n * xyzz_bytes<Fq>() > ((size_t)256 << 20)) slab >>= 1;
   if (!try_ensure(ctx->xyzz_scratch, (size_t)DS_MULT * slab * b->n * xyzz_bytes<Fq>())) {
-    (void)hipFree(t);
+    (void)gate_free(t);
     return deny(DENIED_BY_OOM);
   }
   launch_ds_table<Fq>(ctx->stream, b->d_table, (u32)b->n, (u32)b->c, (u32)b->W, (u32*)ctx->xyzz_scratch.p, slab, t);
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  HIP_TRY(hipGetLastError());
+  hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) {  // (the table is not the key's yet: give it back)
+    (void)hipGetLastError();
+    (void)gate_free(t);
+    return AMSM_E_HIP;
+  }
   b->d_small = t;
   return AMSM_OK;
 }
@@ -177,8 +182,7 @@ int bases_alt(amsm_ctx* ctx, const amsm_bases* b, const amsm_bases** out) {
     a->curve = b->curve;
     a->device = b->device;
     a->n = b->n;
-    if (hipMalloc((void**)&a->d_table, std::max<size_t>(b->n, 1) * affine_bytes<Fq>()) != hipSuccess) {
-      (void)hipGetLastError();
+    if (gate_alloc(ctx, GATE_DEVICE, std::max<size_t>(b->n, 1) * affine_bytes<Fq>(), false, (void**)&a->d_table) != AMSM_OK) {
       delete a;
       return AMSM_E_OOM;
     }
@@ -190,7 +194,8 @@ int bases_alt(amsm_ctx* ctx, const amsm_bases* b, const amsm_bases** out) {
     if (rc == AMSM_OK)
       rc = bases_precompute<Fq>(ctx, a, msel::key_window(b->n, true, false), true);
     if (rc != AMSM_OK) {
-      (void)hipFree(a->d_table);
+      (void)hipStreamSynchronize(ctx->stream);  // (the copy into the table may still run)
+      (void)gate_free(a->d_table);
       delete a;
       return rc;
     }
@@ -266,15 +271,20 @@ template <class Fq>
 int points_check_for_key(amsm_ctx* ctx, const u32* d_xy, const uint8_t* d_inf, size_t n) {
   if (!n) return AMSM_OK;
   char* tmp = nullptr;
-  if (hipMalloc((void**)&tmp, PCHK_HEAD + n) != hipSuccess) {
-    (void)hipGetLastError();
-    return AMSM_E_OOM;
-  }
+  TRY(gate_alloc(ctx, GATE_DEVICE, PCHK_HEAD + n, false, (void**)&tmp));
   u32 cnt[PCHK_WORDS] = {0, 0, 0, 0};
   int s = points_check_run<Fq>(ctx, d_xy, d_inf, n, (uint8_t*)tmp + PCHK_HEAD, (u32*)tmp, cnt);
-  (void)hipFree(tmp);
+  if (s != AMSM_OK) (void)hipStreamSynchronize(ctx->stream);
+  (void)gate_free(tmp);
   if (s == AMSM_OK && (cnt[0] | cnt[1] | cnt[2])) s = AMSM_E_INVALID_POINT;
   return s;
+}
+
+// A key that did not come to be: every table it got so far (the window table, a direct-sum table built before a later step failed)
+inline void bases_discard(amsm_bases* b) {
+  (void)gate_free(b->d_table);
+  (void)gate_free(b->d_small);
+  delete b;
 }
 
 template <class Fq, class Fr>
@@ -286,8 +296,7 @@ int bases_load_impl(amsm_ctx* ctx, const uint64_t* xy, const uint8_t* is_inf, si
   b->device = ctx->device;
   b->n = n;
   size_t bytes = std::max<size_t>(n, 1) * affine_bytes<Fq>();
-  hipError_t e = hipMalloc((void**)&b->d_table, bytes);
-  if (e != hipSuccess) {
+  if (gate_alloc(ctx, GATE_DEVICE, bytes, false, (void**)&b->d_table) != AMSM_OK) {
     delete b;
     return AMSM_E_OOM;
   }
@@ -320,8 +329,9 @@ int bases_load_impl(amsm_ctx* ctx, const uint64_t* xy, const uint8_t* is_inf, si
     }
   } while (0);
   if (s != AMSM_OK) {
-    (void)hipFree(b->d_table);
-    delete b;
+    (void)hipStreamSynchronize(ctx->stream);  // (the upload into the table may still run)
+    (void)hipGetLastError();
+    bases_discard(b);
     return s;
   }
   *out = b;
@@ -335,8 +345,7 @@ int bases_generate_impl(amsm_ctx* ctx, uint64_t seed, size_t n, unsigned flags, 
   b->curve = ctx->curve;
   b->device = ctx->device;
   b->n = n;
-  hipError_t e = hipMalloc((void**)&b->d_table, std::max<size_t>(n, 1) * affine_bytes<Fq>());
-  if (e != hipSuccess) {
+  if (gate_alloc(ctx, GATE_DEVICE, std::max<size_t>(n, 1) * affine_bytes<Fq>(), false, (void**)&b->d_table) != AMSM_OK) {
     delete b;
     return AMSM_E_OOM;
   }
@@ -348,8 +357,7 @@ int bases_generate_impl(amsm_ctx* ctx, uint64_t seed, size_t n, unsigned flags, 
     if (s == AMSM_OK) s = bases_finish<Fq, Fr>(ctx, b, flags);
   }
   if (s != AMSM_OK) {
-    (void)hipFree(b->d_table);
-    delete b;
+    bases_discard(b);
     return s;
   }
   *out = b;
@@ -374,27 +382,22 @@ int bases_sample_impl(amsm_ctx* ctx, const uint8_t* domain, size_t domain_len, u
   u64* pend[2] = {nullptr, nullptr};
   u32* counters = nullptr;
   auto release = [&](int rc) {
-    if (jwin) (void)hipFree(jwin);
-    if (pend[0]) (void)hipFree(pend[0]);
-    if (pend[1]) (void)hipFree(pend[1]);
-    if (counters) (void)hipFree(counters);
-    if (rc != AMSM_OK) {
-      if (b->d_table) (void)hipFree(b->d_table);
-      delete b;
-    }
+    if (rc != AMSM_OK) (void)hipStreamSynchronize(ctx->stream);  // (a search pass may still write the lists)
+    (void)gate_free(jwin);
+    (void)gate_free(pend[0]);
+    (void)gate_free(pend[1]);
+    (void)gate_free(counters);
+    if (rc != AMSM_OK) bases_discard(b);
     return rc;
   };
-  if (hipMalloc((void**)&b->d_table, std::max<size_t>(n, 1) * affine_bytes<Fq>()) != hipSuccess) {
-    (void)hipGetLastError();
-    b->d_table = nullptr;
+  if (gate_alloc(ctx, GATE_DEVICE, std::max<size_t>(n, 1) * affine_bytes<Fq>(), false, (void**)&b->d_table) != AMSM_OK)
     return release(AMSM_E_OOM);
-  }
   if (n) {
-    if (hipMalloc((void**)&jwin, n * 4) != hipSuccess || hipMalloc((void**)&pend[0], n * 8) != hipSuccess ||
-        hipMalloc((void**)&pend[1], n * 8) != hipSuccess || hipMalloc((void**)&counters, SAMPLE_CNT_WORDS * 4) != hipSuccess) {
-      (void)hipGetLastError();
+    if (gate_alloc(ctx, GATE_DEVICE, n * 4, false, (void**)&jwin) != AMSM_OK ||
+        gate_alloc(ctx, GATE_DEVICE, n * 8, false, (void**)&pend[0]) != AMSM_OK ||
+        gate_alloc(ctx, GATE_DEVICE, n * 8, false, (void**)&pend[1]) != AMSM_OK ||
+        gate_alloc(ctx, GATE_DEVICE, SAMPLE_CNT_WORDS * 4, false, (void**)&counters) != AMSM_OK)
       return release(AMSM_E_OOM);
-    }
     const SampleConsts k = host::sample_consts<Fq>(domain, domain_len);
     hipStream_t st = ctx->stream;
     u32 cnt[SAMPLE_CNT_WORDS] = {0};

@@ -17,39 +17,43 @@
     if (_s != AMSM_OK) return _s; \
   } while (0)
 
+// Grow-only workspace: the old buffer goes back BEFORE the new one is asked for (the peak stays at the larger of the two), so a
+// refusal leaves the buffer empty: p null and bytes 0, and the next use asks again
 int ensure(DevBuf& b, size_t bytes) {
   if (b.bytes >= bytes && b.p) return AMSM_OK;
-  if (b.p) HIP_TRY(hipFree(b.p));
+  if (b.p) HIP_TRY(gate_free(b.p));
   b.p = nullptr;
   b.bytes = 0;
   size_t want = bytes + bytes / 8 + 256;
-  HIP_TRY(hipMalloc(&b.p, want));
+  TRY(gate_alloc(b.owner, GATE_DEVICE, want, false, &b.p));
   b.bytes = want;
   return AMSM_OK;
 }
+void DevBuf::release() {
+  if (p) (void)gate_free(p);
+  p = nullptr;
+  bytes = 0;
+}
 
-// ensure() for an allocation the caller can do without: no message, and HIP's sticky last error is cleared -- a tolerated failure
-// must not surface as AMSM_E_OOM at the next HIP_TRY(hipGetLastError()) of an unrelated call (ADVICE r4)
+// ensure() for an allocation the caller can do without: no message, and HIP's sticky last error is cleared (the gate does) -- a
+// tolerated failure must not surface as AMSM_E_OOM at the next HIP_TRY(hipGetLastError()) of an unrelated call (ADVICE r4)
 bool try_ensure(DevBuf& b, size_t bytes) {
   if (b.bytes >= bytes && b.p) return true;
-  if (b.p) (void)hipFree(b.p);
+  if (b.p) (void)gate_free(b.p);
   b.p = nullptr;
   b.bytes = 0;
   const size_t want = bytes + bytes / 8 + 256;
-  if (hipMalloc(&b.p, want) != hipSuccess) {
-    (void)hipGetLastError();
-    b.p = nullptr;
-    return false;
-  }
+  if (gate_alloc(b.owner, GATE_DEVICE, want, true, &b.p) != AMSM_OK) return false;
   b.bytes = want;
   return true;
 }
 
 int ensure_pinned(Slot* sl, size_t bytes) {
   if (sl->h_pinned_bytes >= bytes) return AMSM_OK;
-  if (sl->h_pinned) HIP_TRY(hipHostFree(sl->h_pinned));
+  if (sl->h_pinned) HIP_TRY(gate_free(sl->h_pinned));
   sl->h_pinned = nullptr;
-  HIP_TRY(hipHostMalloc(&sl->h_pinned, bytes + 4096, hipHostMallocDefault));
+  sl->h_pinned_bytes = 0;
+  TRY(gate_alloc(sl->owner, GATE_PINNED, bytes + 4096, false, &sl->h_pinned));
   sl->h_pinned_bytes = bytes + 4096;
   return AMSM_OK;
 }
@@ -1363,13 +1367,10 @@ int tv_probe(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, const std::vector<s
   TRY(ensure(ctx->tv_flags, 2 * p->cap_vecs * TV_PB));  // (second half: the synthetic probe blocks of the unit-scalar sums)
   const size_t pin_need = 2 * p->cap_vecs * (TV_PB + rec + tv_exc_bytes<Fq>()) + 64;
   if (ctx->tv_pinned_bytes < pin_need) {
-    if (ctx->tv_pinned) (void)hipHostFree(ctx->tv_pinned);
+    if (ctx->tv_pinned) (void)gate_free(ctx->tv_pinned);
     ctx->tv_pinned = nullptr;
     ctx->tv_pinned_bytes = 0;
-    if (hipHostMalloc(&ctx->tv_pinned, pin_need * 2) != hipSuccess) {
-      (void)hipGetLastError();
-      return AMSM_E_OOM;
-    }
+    TRY(gate_alloc(ctx, GATE_PINNED, pin_need * 2, false, &ctx->tv_pinned));
     ctx->tv_pinned_bytes = pin_need * 2;
   }
   HIP_TRY(hipMemsetAsync(ctx->tv_flags.p, 0, cand.size() * TV_PB, ctx->stream));

@@ -476,6 +476,10 @@ int ipa_jump_fold_impl(amsm_ctx* ctx, const amsm_bases* key, size_t log_key, con
   if (!key->precomp || key->bpl || key->top_shift || key->n_narrow || n > key->n || (m0 & 63u) || c < 2 || c > 16 || (size_t)c * W < 256 ||
       (size_t)W * key->n >= ((size_t)1 << 31) || T * W * 2 >= ((size_t)1 << 26))
     return AMSM_E_UNSUPPORTED;
+  // n_sets = 2 n_rep m0 (below) is the gridDim.y of the reduction launch: HIP takes at most 65535.  With n_rep >= 1 a small j is
+  // out before any work; the callers keep such rounds on the device (amsm_ipa_round_fused)
+  constexpr size_t MAX_GRID_Y = 65535;
+  if (2 * m0 > MAX_GRID_Y) return AMSM_E_UNSUPPORTED;
   std::vector<std::array<u64, 4>> S;
   jump_fold_scalars<Fr>(xs_mont, j, &S);
   // signed c-bit digits (|d| <= 2^(c-1) <= 2^15), each split into two bytes; one list per (half, value) with entries
@@ -540,6 +544,7 @@ int ipa_jump_fold_impl(amsm_ctx* ctx, const amsm_bases* key, size_t log_key, con
   MsmGeom g;
   memset(&g, 0, sizeof(g));
   g.nb = JUMP_NB;
+  if ((size_t)2 * n_rep * m0 > MAX_GRID_Y) return AMSM_E_UNSUPPORTED;  // (decided before anything is allocated)
   g.n_sets = (u32)(2 * n_rep * m0);
   const msel::TailPlan tp = tail_plan_of(g, Place::LONE);  // (the caller waits: the fused quad tail, two buckets per logical lane)
   Slot* sl = &ctx->slot[0];

@@ -1,5 +1,6 @@
 // Private to api.hip (one translation unit): the context, key, slot and host-thread types of the C ABI implementation.
 #pragma once
+struct amsm_ctx;
 namespace {
 
 enum Stage { ST_DIGITS = 0, ST_SORT, ST_BOUNDS, ST_ACCUM_L0, ST_ACCUM_L12, ST_REDUCE, ST_COUNT };
@@ -13,6 +14,17 @@ const char* kStageNames[ST_COUNT] = {"prep_chain", "prep_sort_rocprim", "prep_bo
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  amsm_ctx* owner = nullptr;  // the context whose gate this buffer is asked from (api_gate.inc; set once at creation: ctx_bind_bufs)
+  void release();             // back through the gate; p and bytes cleared, the owner stays
+};
+
+// The books of a context's allocation gate (api_gate.inc), under the gate's lock
+struct MemGate {
+  size_t held = 0, peak = 0;  // device (host backend: host) bytes held through the gate now / at most so far
+  size_t limit = 0;           // amsm_ctx_set_memory_limit; 0: none
+  size_t pinned = 0;          // page-locked host bytes: they pass the gate, counted apart and not against the limit
+  unsigned long long requests = 0, refused_limit = 0, refused_hook = 0, failed_driver = 0;
+  long fail_after = -1;       // amsm_ctx_fail_alloc_after: requests still granted before one is refused; < 0: disarmed
 };
 
 }  // namespace
@@ -79,6 +91,7 @@ struct Slot {  // buffers and events of one MSM in flight (the streams belong to
   int (*rerun_unit)(amsm_ctx*, Slot*, void* out) = nullptr;
   void* h_pinned = nullptr;
   size_t h_pinned_bytes = 0;
+  amsm_ctx* owner = nullptr;  // the slot's context (its page-locked buffer passes that gate; ctx_bind_bufs)
   MsmGeom geom = {};
   bool busy = false;
   bool share_overflow = false;  // set by msm_collect: a range of a shared MSM found skewed digits -- the whole MSM is re-run unshared
@@ -288,6 +301,7 @@ struct amsm_ctx {
   std::unordered_map<void*, size_t> pool_size;            // every live or pooled buffer -> its rounded size
   size_t pool_free_bytes = 0, pool_live_bytes = 0;
   size_t pool_cap_bytes = (size_t)16 << 30;               // free-list budget (AMSM_POOL_MAX_MB); beyond it frees are real
+  MemGate gate;  // every allocation of this context, its keys and its matrices passes it (api_gate.inc)
 };
 
 // Every device buffer of a slot, and every one the context owns beside its slots: the one list amsm_ctx_destroy, amsm_ctx_memory and
@@ -305,6 +319,14 @@ void for_each_ctx_buf(C* c, F&& f) {
                   &c->shared_buckets[1], &c->oneshot_table, &c->oneshot_inf, &c->rec_send, &c->rec_recv, &c->stage, &c->check_ws})
     f(*b);
   for (auto& b : c->stage_ring) f(b);
+}
+inline void ctx_bind_bufs(amsm_ctx* c) {  // every workspace buffer knows its context's gate
+  auto bind = [c](DevBuf& b) { b.owner = c; };
+  for_each_ctx_buf(c, bind);
+  for (Slot& sl : c->slot) {
+    sl.owner = c;
+    for_each_slot_buf(&sl, bind);
+  }
 }
 
 struct amsm_bases {

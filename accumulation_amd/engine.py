@@ -106,6 +106,28 @@ class Context:
     def tables_denied(self) -> int:
         return int(self._lib.amsm_ctx_tables_denied(self._h))
 
+    def set_memory_limit(self, nbytes: int) -> None:
+        """device bytes this context may hold through the library (workspace, vectors, its keys' tables, its matrices); 0: no
+        limit.  A request past it is refused: AmsmError with status AMSM_E_OOM, or the call's documented fallback
+        (amsm_ctx_set_memory_limit)"""
+        ffi.check(self._lib.amsm_ctx_set_memory_limit(self._h, nbytes), "amsm_ctx_set_memory_limit")
+
+    def memory_held(self) -> tuple:
+        """(held now, peak, limit, page-locked host bytes): amsm_ctx_memory_held"""
+        out = (C.c_size_t * 4)()
+        ffi.check(self._lib.amsm_ctx_memory_held(self._h, out), "amsm_ctx_memory_held")
+        return tuple(int(v) for v in out)
+
+    def fail_alloc_after(self, n: int) -> None:
+        """TESTING: refuse, once, the (n + 1)-th allocation request from now on; n < 0 disarms (amsm_ctx_fail_alloc_after)"""
+        ffi.check(self._lib.amsm_ctx_fail_alloc_after(self._h, n), "amsm_ctx_fail_alloc_after")
+
+    def alloc_stats(self) -> tuple:
+        """(requests, refused by the limit, refused by the hook, failed in the driver): amsm_ctx_alloc_stats"""
+        out = (C.c_ulonglong * 4)()
+        ffi.check(self._lib.amsm_ctx_alloc_stats(self._h, out), "amsm_ctx_alloc_stats")
+        return tuple(int(v) for v in out)
+
     def two_valued_msms(self) -> int:
         """MSMs of device vectors that took the two-valued form (every scalar 0 or one value v) so far"""
         return int(self._lib.amsm_ctx_two_valued_msms(self._h))

@@ -46,6 +46,14 @@ _u64p = C.POINTER(C.c_uint64)
 _u8p = C.POINTER(C.c_uint8)
 _sz = C.c_size_t
 
+class _Long(C.c_long):
+    """`long` as an argument type that also takes None (as zero), the way the pointer types do"""
+
+    @classmethod
+    def from_param(cls, value):
+        return C.c_long(0 if value is None else value)
+
+
 # name -> (restype, argtypes); must list every symbol include/amsm.h declares (tests check this)
 SIGNATURES = {
     "amsm_strerror": (C.c_char_p, [C.c_int]),
@@ -117,6 +125,10 @@ SIGNATURES = {
     "amsm_bases_tables": (C.c_int, [_vp, _vp]),
     "amsm_ctx_set_table_budget": (C.c_int, [_vp, _sz]),
     "amsm_ctx_tables_denied": (C.c_ulonglong, [_vp]),
+    "amsm_ctx_set_memory_limit": (C.c_int, [_vp, _sz]),
+    "amsm_ctx_memory_held": (C.c_int, [_vp, _vp]),
+    "amsm_ctx_fail_alloc_after": (C.c_int, [_vp, _Long]),
+    "amsm_ctx_alloc_stats": (C.c_int, [_vp, _vp]),
     "amsm_host_register": (C.c_int, [_vp, _sz]),
     "amsm_host_unregister": (C.c_int, [_vp]),
     "amsm_host_is_pinned": (C.c_int, [_vp]),

@@ -247,7 +247,8 @@ class InnerProductArgPC:
             # (JUMP_M generators) comes from ONE pass over the key's window table (amsm_ipa_jump_fold) and the remaining
             # log2(JUMP_M) rounds -- ~0.36 ms each on the device whatever their logical size -- run on the host over those few
             # generators; the final folded key falls out of the last fold instead of one more full-size MSM.  Keys that do not
-            # qualify (AMSM_E_UNSUPPORTED: folded / plain keys, 20-bit tables, sharded keys) keep their rounds on the device.
+            # qualify (AMSM_E_UNSUPPORTED: folded / plain keys, 20-bit tables, sharded keys) keep their rounds on the device, and so
+            # does a jump whose bucket table was refused (AMSM_E_OOM leaves the context reusable: include/amsm.h).
             if n == cls._jump_m() and j >= 1 and key.num_shards == 1:
                 jumped = cls._host_rounds(ctx, fr, cur_key, log_key, xs, j, n, coeffs, z, h_prime, round_challenge, l_vec, r_vec)
                 if jumped is not None:
@@ -313,7 +314,7 @@ class InnerProductArgPC:
         inf = np.zeros((n,), dtype=np.uint8)
         xi = fr.to_limbs_many(xs[len(xs) - j:])
         rc = ctx._lib.amsm_ipa_jump_fold(ctx._h, cur_key._h, log_key, _ptr(xi), j, _ptr(xy), _ptr(inf))
-        if rc == ffi.AMSM_E_UNSUPPORTED:
+        if rc in (ffi.AMSM_E_UNSUPPORTED, ffi.AMSM_E_OOM):
             return None
         ffi.check(rc, "amsm_ipa_jump_fold")
         B = [(xy[k].copy(), bool(inf[k])) for k in range(n)]

@@ -60,6 +60,18 @@ enum amsm_curve {
                             0x170b5d44300000000000000000000000 (even: the curve has points of order 2); extension */
 };
 
+/* THE CONTRACT AFTER AMSM_E_OOM -- it holds for every entry point below.  AMSM_E_OOM means that an allocation the call could not
+ * do without was refused: by the driver, by the context's memory limit (amsm_ctx_set_memory_limit) or by the test hook
+ * (amsm_ctx_fail_alloc_after).  Allocations a call CAN do without (a key's optional tables, scratch that only makes a step faster,
+ * the buffers that let several MSMs share launches) are never reported: the call takes its slower path and returns AMSM_OK.
+ *  1. No handle is produced and *out is untouched.  Everything the failing call itself allocated is returned.  Grow-only workspace
+ *     buffers that grew before the failing request may stay: they show in amsm_ctx_memory and go with amsm_ctx_trim.
+ *  2. The context is reusable: no pipeline slot stays busy, no MSM stays in flight, every stream of the context is drained before
+ *     the call returns, the arrival counters of the fused tail are zero (a counter buffer that was refused is zeroed when it is next
+ *     allocated), and the next call inherits no error.
+ *  3. Caller-visible inputs are untouched wherever an entry point says so (amsm_ipa_round_fused: d_coeffs / d_z); everywhere else
+ *     the caller's vectors are read-only anyway, and documented outputs hold nothing to rely on.
+ *  4. The same call repeated after the hook is disarmed, the limit raised or memory freed gives the bit-exact result. */
 enum amsm_status {
   AMSM_OK = 0,
   AMSM_E_INVALID_ARG = -1,
@@ -213,6 +225,31 @@ int amsm_ctx_synchronize(amsm_ctx* ctx);
  * amsm_ctx_trim synchronises and releases the workspace and the free lists (live buffers and keys stay). */
 int amsm_ctx_memory(const amsm_ctx* ctx, size_t* workspace_bytes, size_t* vectors_live_bytes, size_t* vectors_pooled_bytes);
 int amsm_ctx_trim(amsm_ctx* ctx);
+/* THE ALLOCATION GATE.  Every device allocation of a context passes one gate: the MSM workspace, live and pooled amsm_dev_alloc
+ * vectors, the tables of the keys made through the context (window table, direct-sum table, twin, C-ABI copy) and its matrices --
+ * that sum is what the context HOLDS.  Keys and matrices stay on the books of the context that made them until they are freed (a
+ * context destroyed first is forgotten).  Page-locked host memory passes the gate too, counted apart and not against the limit.  On
+ * the host backend the gate covers the host memory behind keys, vectors and matrices (not the calls' internal scratch).
+ * amsm_ctx_set_memory_limit: device bytes this context may hold through the library.  0: no limit (the default; the environment
+ *   variable AMSM_MEM_LIMIT_MB sets one, in MiB, at creation).  Applies to later requests only: nothing held is given back, and the
+ *   peak of amsm_ctx_memory_held starts again at what is held now (so that under a limit the peak never exceeds it).  A request
+ *   that would pass the limit gives the vector pool's free lists back once and is then REFUSED before it reaches the driver: the call
+ *   returns AMSM_E_OOM where it needs the memory (see the contract above the status enum) and takes its documented fallback where it
+ *   does not (no direct-sum table -- amsm_ctx_tables_denied, reason code 3 --, a plain key under AMSM_BASES_DEFAULT, ...).  The library
+ *   does not cut an MSM into smaller pieces to fit: the limit refuses, the caller decides.
+ * amsm_ctx_memory_held: out[0] held now, out[1] peak, out[2] limit, out[3] page-locked host bytes.
+ * amsm_ctx_fail_alloc_after (TESTING): refuse, once, the (n+1)-th request that would reach the driver from now on (a vector handed
+ *   out from the pool's free lists is no request); n < 0 disarms.  This is how every out-of-memory path of the library is exercised
+ *   without exhausting a device.
+ * amsm_ctx_alloc_stats: out[0] requests, out[1] refused by the limit, out[2] refused by the hook, out[3] failed in the driver.
+ * A multi-device context (amsm_ctx_create_multi with n_dev >= 2) and its shard contexts return AMSM_E_UNSUPPORTED from the two
+ * setters and ignores AMSM_MEM_LIMIT_MB (no limit on any of its devices); the two readers report the primary device's books.
+ * The books are kept under one lock, and a request's bytes are reserved in the critical section that checks them against the limit:
+ * keys made or freed on other threads cannot take a context past its limit. */
+int amsm_ctx_set_memory_limit(amsm_ctx* ctx, size_t bytes);
+int amsm_ctx_memory_held(const amsm_ctx* ctx, size_t out[4]);
+int amsm_ctx_fail_alloc_after(amsm_ctx* ctx, long n);
+int amsm_ctx_alloc_stats(const amsm_ctx* ctx, unsigned long long out[4]);
 /* Device memory a key holds: its table (W levels of affine points when precomputed -- plus 512 points per generator for a key of up
  * to 2^15 generators, the direct-sum table -- the generators otherwise), the C-ABI-radix
  * copy amsm_bases_device_ptr made (0 if never asked), and the 17-bit-window TWIN of a 20-bit key -- built lazily, inside the

@@ -81,6 +81,31 @@ class Context {
   amsm_ctx* get() const { return h_; }
   int fq_limbs() const { return amsm_ctx_fq_limbs(h_); }
   void synchronize() { check(amsm_ctx_synchronize(h_), "amsm_ctx_synchronize"); }
+  // The allocation gate (amsm.h): device bytes the context may hold through the library (0: no limit); a request past it is refused
+  // and the call throws Error{AMSM_E_OOM} -- or takes its documented fallback where it can do without the memory
+  void set_memory_limit(size_t bytes) { check(amsm_ctx_set_memory_limit(h_, bytes), "amsm_ctx_set_memory_limit"); }
+  struct MemoryHeld {
+    size_t held = 0, peak = 0, limit = 0, pinned_host = 0;
+  };
+  MemoryHeld memory_held() const {
+    size_t o[4];
+    check(amsm_ctx_memory_held(h_, o), "amsm_ctx_memory_held");
+    MemoryHeld m;
+    m.held = o[0], m.peak = o[1], m.limit = o[2], m.pinned_host = o[3];
+    return m;
+  }
+  // TESTING: refuse, once, the (n + 1)-th allocation request from now on; n < 0 disarms
+  void fail_alloc_after(long n) { check(amsm_ctx_fail_alloc_after(h_, n), "amsm_ctx_fail_alloc_after"); }
+  struct AllocStats {
+    unsigned long long requests = 0, refused_by_limit = 0, refused_by_hook = 0, failed_in_driver = 0;
+  };
+  AllocStats alloc_stats() const {
+    unsigned long long o[4];
+    check(amsm_ctx_alloc_stats(h_, o), "amsm_ctx_alloc_stats");
+    AllocStats s;
+    s.requests = o[0], s.refused_by_limit = o[1], s.refused_by_hook = o[2], s.failed_in_driver = o[3];
+    return s;
+  }
   // amsm_points_check: may these points become a key?  Counts by status and the first bad index (n: none); status (optional): one
   // byte per point -- 0 valid, 1 non-canonical, 2 not on the curve, 3 outside the prime-order subgroup.  CommitterKey::load with
   // AMSM_BASES_CHECK runs the same check and throws Error{AMSM_E_INVALID_POINT} on a bad point.

@@ -362,7 +362,8 @@ struct InnerProductArgPC {
       // from ONE pass over the key's window table (amsm_ipa_jump_fold) and the remaining rounds -- ~0.36 ms each on the device
       // whatever their logical size -- run on the host over those few generators (host_rounds below); the final folded key falls
       // out of the last fold instead of one more full-size MSM.  A key that does not qualify (AMSM_E_UNSUPPORTED: folded / plain
-      // keys, 20-bit tables, sharded keys) keeps its rounds on the device.  The proof does not depend on the choice.
+      // keys, 20-bit tables, sharded keys, a jump whose bucket sets pass the launch limit) keeps its rounds on the device, and so
+      // does one whose bucket table was refused (AMSM_E_OOM: the context is reusable, amsm.h).  The proof does not depend on the choice.
       if (cur == jump_m() && j >= 1 && amsm_bases_num_shards(cur_key->get()) == 1) {
         std::vector<uint64_t> bxy(cur * w);
         std::vector<uint8_t> binf(cur);
@@ -373,7 +374,7 @@ struct InnerProductArgPC {
           jumped = true;
           break;
         }
-        if (rc != AMSM_E_UNSUPPORTED) amsm::check(rc, "amsm_ipa_jump_fold");
+        if (rc != AMSM_E_UNSUPPORTED && rc != AMSM_E_OOM) amsm::check(rc, "amsm_ipa_jump_fold");
       }
       std::vector<uint64_t> lr_xy(2 * w);
       uint8_t lr_inf[2] = {0, 0};
