@@ -371,6 +371,18 @@ int amsm_ctx_set_window(amsm_ctx* c, int bits) {
   c->window_override = bits;
   return AMSM_OK;
 }
+int amsm_ctx_set_vec_grid_max(amsm_ctx* c, unsigned max_workgroups) {
+  if (!c) return AMSM_E_INVALID_ARG;
+  c->vec_grid_max = max_workgroups;
+  for (size_t g = 1; g < c->shard_ctx.size(); g++) c->shard_ctx[g]->vec_grid_max = max_workgroups;
+  return AMSM_OK;
+}
+int amsm_ctx_vec_grid(const amsm_ctx* c, size_t n, unsigned* stream_workgroups, unsigned* reduce_workgroups) {
+  if (!c || n >= (1ull << 32)) return AMSM_E_INVALID_ARG;
+  if (stream_workgroups) *stream_workgroups = vec_stream_grid((u32)n, vec_grid_of(c));
+  if (reduce_workgroups) *reduce_workgroups = vec_reduce_grid((u32)n, vec_grid_of(c));
+  return AMSM_OK;
+}
 int amsm_ctx_synchronize(amsm_ctx* c) {
   if (!c) return AMSM_E_INVALID_ARG;
   if (c->host_only) return AMSM_OK;  // every host-backend call is synchronous

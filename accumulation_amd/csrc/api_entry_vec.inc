@@ -187,7 +187,7 @@ int amsm_vec_hadamard(amsm_ctx* c, const void* d_a, const void* d_b, void* d_out
   if (c->host_only) return CPU_CALL(c, vec_hadamard, d_a, d_b, d_out, n);
   TRY(bind_device(c));
   if (!n) return AMSM_OK;
-  DISPATCH_DO(c, launch_vec_hadamard<Fr>(c->stream, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, (u32)n));
+  DISPATCH_DO(c, launch_vec_hadamard<Fr>(c->stream, vec_grid_of(c), (const u32*)d_a, (const u32*)d_b, (u32*)d_out, (u32)n));
   HIP_TRY(hipGetLastError());
   return AMSM_OK;
 }
@@ -357,7 +357,7 @@ int amsm_vec_inner_product(amsm_ctx* c, const void* d_a, const void* d_b, size_t
   TRY(bind_device(c));
   memset(out_mont, 0, 32);
   if (!n) return AMSM_OK;
-  u32 blocks = std::min<u32>(1024u, cdiv((u32)n, 256));
+  const u32 blocks = vec_reduce_grid((u32)n, vec_grid_of(c));
   Slot* sl = &c->slot[0];
   TRY(ensure(sl->red_out, (size_t)blocks * 32 + 4096));
   TRY(ensure_pinned(sl, (size_t)blocks * 32));

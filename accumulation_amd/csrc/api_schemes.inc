@@ -43,7 +43,7 @@ int msm_grouped_impl(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, co
 template <class Fr>
 int ipa_round_vectors(amsm_ctx* ctx, const uint64_t* xi_mont, size_t j, size_t log_key, const void* d_coeffs, const void* d_z, size_t half,
                       void* d_u, const uint64_t* fold_x_mont, u32* blocks_out) {
-  const u32 blocks = std::min<u32>(1024u, cdiv((u32)half, 256));
+  const u32 blocks = vec_reduce_grid((u32)half, vec_grid_of(ctx));
   *blocks_out = blocks;
   Slot* aux = &ctx->slot[1];  // only its pinned buffer: slot 1 carries no MSM during a single-MSM call
   TRY(ensure_pinned(aux, (size_t)2 * blocks * 32));
@@ -225,7 +225,7 @@ int vec_combine_impl(amsm_ctx* ctx, const void* const* d_vecs, const size_t* len
     a.hiding_len = done ? (u32)n : (u32)hiding_len;
     a.n_vecs = (u32)k;
     a.n = (u32)n;
-    launch_vec_combine<Fr>(ctx->stream, a, (u32*)d_out);
+    launch_vec_combine<Fr>(ctx->stream, vec_grid_of(ctx), a, (u32*)d_out);
     HIP_TRY(hipGetLastError());
     done += k;
   } while (done < n_vecs);
@@ -354,7 +354,7 @@ int t_vecs_impl(amsm_ctx* ctx, const void* const* d_a, const size_t* a_lens, con
   a.hiding_b_len = (u32)hb_len;
   for (size_t k = 0; k < 2 * n_in - 1; k++) a.t[k] = (u32*)d_t[k];
   a.len = (u32)len;
-  launch_hp_t_vecs<Fr>(ctx->stream, a, (int)n_in);
+  launch_hp_t_vecs<Fr>(ctx->stream, vec_grid_of(ctx), a, (int)n_in);
   HIP_TRY(hipGetLastError());
   return AMSM_OK;
 }
@@ -426,7 +426,7 @@ int t_vecs_blocked(amsm_ctx* ctx, const void* const* d_a, const size_t* a_lens, 
           if (i >= n_t || !d_t[i]) continue;
           const size_t l = std::min(std::min(a_lens ? a_lens[i] : len, hb_len), len);
           launch_vec_fill(ctx->stream, (u32*)scratch[2 * M - 1], zero, (u32)len);
-          if (l) launch_vec_hadamard<Fr>(ctx->stream, (const u32*)d_a[i], (const u32*)d_hb, (u32*)scratch[2 * M - 1], (u32)l);
+          if (l) launch_vec_hadamard<Fr>(ctx->stream, vec_grid_of(ctx), (const u32*)d_a[i], (const u32*)d_hb, (u32*)scratch[2 * M - 1], (u32)l);
           H mi;
           memcpy(mi.v, mu + 4 * i, 32);
           H cf = host::h_mul<Fr>(mi, mu1);

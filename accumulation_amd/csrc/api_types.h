@@ -212,6 +212,7 @@ struct amsm_ctx {
   bool own_stream = false;
   int window_override = 0;  // amsm_ctx_set_window: every MSM chunked with this width (tests, sweeps)
   int cu_count = 256;
+  unsigned vec_grid_max = 0;  // amsm_ctx_set_vec_grid_max: upper bound on the workgroups of every grid-stride Fr kernel (0: none; tests)
   int wave_slots = 4096;  // resident accumulate-L0 waves: CUs x resident 256-lane blocks per CU x 4
   // ---- the documented switches (include/amsm.h "Environment"; msm_select.h: Switches) -- everything else that used to be an
   // environment knob is a measured constant now (namespace tune below; the A/Bs are in profiles/ and DESIGN.md) ----
@@ -303,6 +304,9 @@ struct amsm_ctx {
   size_t pool_cap_bytes = (size_t)16 << 30;               // free-list budget (AMSM_POOL_MAX_MB); beyond it frees are real
   MemGate gate;  // every allocation of this context, its keys and its matrices passes it (api_gate.inc)
 };
+
+// what the grid-stride Fr kernels of this context are launched over (launch.h: vec_stream_grid / vec_reduce_grid)
+inline VecGrid vec_grid_of(const amsm_ctx* c) { return VecGrid{(u32)std::max(1, c->cu_count), c->vec_grid_max}; }
 
 // Every device buffer of a slot, and every one the context owns beside its slots: the one list amsm_ctx_destroy, amsm_ctx_memory and
 // amsm_ctx_trim walk (a buffer added to a struct above goes here too)

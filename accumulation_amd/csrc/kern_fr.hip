@@ -13,20 +13,6 @@
 namespace amsm {
 
 static inline u32 cdiv_(u32 a, u32 b) { return (a + b - 1) / b; }
-// grid of a streaming (grid-stride) kernel: enough 256-lane workgroups to fill the wave slots a few times over, not one
-// per 256 elements beyond that (64 per CU: one element per lane up to 2^22 elements; round 2, 2^22 elements: 64 -> 0.57-0.79 of
-// 8 TB/s, 8 -> 0.52-0.75)
-static u32 stream_grid(u32 n) {
-  constexpr u32 per_cu = 64;
-  static const u32 cus = [] {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256u;
-    return (u32)std::max(1, prop.multiProcessorCount);
-  }();
-  return std::max(1u, std::min(cdiv_(n, 256), cus * per_cu));
-}
-
 void launch_bounds(hipStream_t st, const void* keys_sorted, bool keys16, u32* vals_sorted, MsmGeom g, u32* start,
                    u32* items) {
   if (keys16)
@@ -461,12 +447,12 @@ void launch_tv_probe(hipStream_t st, const u32* scalars, u32 n, u32* out16, cons
                          stream, first, n, mont);                                                                    \
   }                                                                                                                  \
   template <>                                                                                                        \
-  void launch_vec_hadamard<FR>(hipStream_t st, const u32* a, const u32* b, u32* out, u32 n) {                        \
-    hipLaunchKernelGGL((k_vec_hadamard<FR>), dim3(stream_grid(n)), dim3(256), 0, st, a, b, out, n);                  \
+  void launch_vec_hadamard<FR>(hipStream_t st, VecGrid vg, const u32* a, const u32* b, u32* out, u32 n) {            \
+    hipLaunchKernelGGL((k_vec_hadamard<FR>), dim3(vec_stream_grid(n, vg)), dim3(256), 0, st, a, b, out, n);          \
   }                                                                                                                  \
   template <>                                                                                                        \
-  void launch_vec_combine<FR>(hipStream_t st, const CombineArgs& a_in, u32* out) {                                   \
-    dim3 grid(stream_grid(a_in.n)), block(256);                                                                      \
+  void launch_vec_combine<FR>(hipStream_t st, VecGrid vg, const CombineArgs& a_in, u32* out) {                       \
+    dim3 grid(vec_stream_grid(a_in.n, vg)), block(256);                                                              \
     const CombineArgs& a = a_in;                                                                                     \
     switch (a.n_vecs) {                                                                                              \
       case 0: /* only the hiding addend */                                                                          \
@@ -543,8 +529,8 @@ void launch_tv_probe(hipStream_t st, const u32* scalars, u32 n, u32* out16, cons
                        witness, n_witness, out, n_rows);                                                             \
   }                                                                                                                  \
   template <>                                                                                                        \
-  void launch_hp_t_vecs<FR>(hipStream_t st, const TVecArgs& a_in, int n_inputs) {                                    \
-    dim3 grid(stream_grid(a_in.len)), block(256);                                                                    \
+  void launch_hp_t_vecs<FR>(hipStream_t st, VecGrid vg, const TVecArgs& a_in, int n_inputs) {                        \
+    dim3 grid(vec_stream_grid(a_in.len, vg)), block(256);                                                            \
     const TVecArgs& a = a_in;                                                                                        \
     switch (n_inputs) {                                                                                              \
       case 1: hipLaunchKernelGGL((k_hp_t_vecs<FR, 1>), grid, block, 0, st, a); break;                                \

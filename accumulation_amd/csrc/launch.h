@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "blind.h"
 #include "msm_select.h"
 #include "msm_types.h"
@@ -201,12 +203,32 @@ void launch_vec_random(hipStream_t st, u32* out, u64 seed, u32 n, int mont);
 constexpr u32 VEC_SAMPLE_TILE = 1024;
 template <class Fr>
 void launch_vec_sample(hipStream_t st, u32* out, const blind::Key& key, u32 curve_id, u32 stream, u64 first, u32 n, int mont, int form);
+// Grids of the grid-stride Fr kernels (256-lane workgroups), the ONE place they are computed: the launchers below, the callers that
+// size partial-sum buffers by `blocks`, and amsm_ctx_vec_grid all call these two.  cus: the CUs of the context's device; max_wg:
+// amsm_ctx_set_vec_grid_max (0: none) -- a further upper bound, so that a test reaches the loops' second pass at a small n.
+struct VecGrid {
+  u32 cus;
+  u32 max_wg;
+};
+// streaming kernels (k_vec_hadamard, k_vec_combine, k_hp_t_vecs): enough workgroups to fill the wave slots a few times over, not one
+// per 256 elements beyond that (64 per CU: one element per lane up to 2^22 elements on 256 CUs; round 2, 2^22 elements: 64 -> 0.57-0.79
+// of 8 TB/s, 8 -> 0.52-0.75)
+inline u32 vec_stream_grid(u32 n, VecGrid vg) {
+  constexpr u32 per_cu = 64;
+  u32 g = std::max(1u, std::min((n + 255u) / 256u, std::max(1u, vg.cus) * per_cu));
+  return vg.max_wg ? std::min(g, vg.max_wg) : g;
+}
+// block-reduction kernels (k_vec_inner_product, k_vec_inner_product_pair, k_ipa_fold_ip): one partial sum per workgroup, folded on the host
+inline u32 vec_reduce_grid(u32 n, VecGrid vg) {
+  u32 g = std::min<u32>(1024u, (n + 255u) / 256u);
+  return vg.max_wg ? std::min(g, vg.max_wg) : g;
+}
 template <class Fr>
-void launch_vec_hadamard(hipStream_t st, const u32* a, const u32* b, u32* out, u32 n);
+void launch_vec_hadamard(hipStream_t st, VecGrid vg, const u32* a, const u32* b, u32* out, u32 n);
 template <class Fr>
-void launch_vec_combine(hipStream_t st, const CombineArgs& a, u32* out);
+void launch_vec_combine(hipStream_t st, VecGrid vg, const CombineArgs& a, u32* out);
 template <class Fr>
-void launch_hp_t_vecs(hipStream_t st, const TVecArgs& a, int n_inputs);
+void launch_hp_t_vecs(hipStream_t st, VecGrid vg, const TVecArgs& a, int n_inputs);
 
 template <class Fr>
 void launch_spmv(hipStream_t st, const u32* row_ptr, const u32* col, const u32* val, const u32* input, u32 n_input,

@@ -160,6 +160,17 @@ class Context:
     def set_window(self, c_bits: int):
         ffi.check(self._lib.amsm_ctx_set_window(self._h, c_bits), "amsm_ctx_set_window")
 
+    def set_vec_grid_max(self, max_workgroups: int) -> None:
+        """TESTING: at most this many 256-lane workgroups for every grid-stride Fr kernel; 0: the built-in bounds
+        (amsm_ctx_set_vec_grid_max)"""
+        ffi.check(self._lib.amsm_ctx_set_vec_grid_max(self._h, max_workgroups), "amsm_ctx_set_vec_grid_max")
+
+    def vec_grid(self, n: int) -> tuple:
+        """(workgroups of an n-element streaming launch, workgroups of an n-element reduction) now: amsm_ctx_vec_grid"""
+        s, r = C.c_uint(), C.c_uint()
+        ffi.check(self._lib.amsm_ctx_vec_grid(self._h, n, C.byref(s), C.byref(r)), "amsm_ctx_vec_grid")
+        return s.value, r.value
+
     def set_profiling(self, on: bool):
         ffi.check(self._lib.amsm_ctx_set_profiling(self._h, 1 if on else 0), "amsm_ctx_set_profiling")
 

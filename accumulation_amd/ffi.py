@@ -77,6 +77,8 @@ SIGNATURES = {
     "amsm_ctx_curve": (C.c_int, [_vp]),
     "amsm_ctx_fq_limbs": (C.c_int, [_vp]),
     "amsm_ctx_set_window": (C.c_int, [_vp, C.c_int]),
+    "amsm_ctx_set_vec_grid_max": (C.c_int, [_vp, C.c_uint]),
+    "amsm_ctx_vec_grid": (C.c_int, [_vp, _sz, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "amsm_ctx_synchronize": (C.c_int, [_vp]),
     "amsm_ctx_memory": (C.c_int, [_vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     "amsm_ctx_trim": (C.c_int, [_vp]),

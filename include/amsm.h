@@ -217,6 +217,18 @@ int amsm_ctx_curve(const amsm_ctx* ctx);
 int amsm_ctx_fq_limbs(const amsm_ctx* ctx);
 /* Override the Pippenger window width c (bits); 0 restores the automatic choice. */
 int amsm_ctx_set_window(amsm_ctx* ctx, int c_bits);
+/* TESTING: the grids of the grid-stride scalar-field kernels.  The streaming kernels (amsm_vec_hadamard, amsm_vec_combine,
+ * amsm_hp_t_vecs) run over min(ceil(n / 256), 64 * CUs) workgroups of 256 lanes, the block reductions (amsm_vec_inner_product, the
+ * inner products and the fold of amsm_ipa_round / amsm_ipa_round_fused) over min(ceil(n / 256), 1024): a lane takes a second
+ * element only from n > 2^22 (on 256 CUs) and n > 2^18 on.
+ * amsm_ctx_set_vec_grid_max: a further upper bound on the workgroup count of every one of these launches, so that a small vector
+ *   goes through the same loops; 0 (the default) leaves the built-in bounds alone.  Results do not depend on it.  The shard contexts
+ *   of a multi-device context take their parent's value; a host-backend context keeps the value and has no use for it.
+ * amsm_ctx_vec_grid: the workgroups an n-element streaming launch (*stream_workgroups) and an n-element reduction
+ *   (*reduce_workgroups) of this context would get now, computed by the functions the launches themselves call; n < 2^32, either
+ *   pointer may be NULL. */
+int amsm_ctx_set_vec_grid_max(amsm_ctx* ctx, unsigned max_workgroups);
+int amsm_ctx_vec_grid(const amsm_ctx* ctx, size_t n, unsigned* stream_workgroups, unsigned* reduce_workgroups);
 int amsm_ctx_synchronize(amsm_ctx* ctx);
 
 /* Device memory the context holds: the MSM workspace (grow-only: sized by the largest MSM so far, three pipeline slots), the

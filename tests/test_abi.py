@@ -96,6 +96,32 @@ def test_invalid_arguments_rejected(built_lib):
     assert built_lib.amsm_ctx_set_window(None, 8) == ffi.AMSM_E_INVALID_ARG
 
 
+def test_vec_grid_cap_on_a_host_context(built_lib):
+    """amsm_ctx_set_vec_grid_max / amsm_ctx_vec_grid: 0 leaves min(ceil(n / 256), 64 CUs) and min(ceil(n / 256), 1024) in force (a
+    host context keeps the 256 CUs a context starts with), a positive value is a further bound, and like amsm_ctx_set_window the
+    host backend keeps the value and computes what it computed before."""
+    import numpy as np
+    from accumulation_amd import Context
+    from accumulation_amd.hp_as import compute_hp
+    assert built_lib.amsm_ctx_set_vec_grid_max(None, 4) == ffi.AMSM_E_INVALID_ARG
+    assert built_lib.amsm_ctx_vec_grid(None, 1, None, None) == ffi.AMSM_E_INVALID_ARG
+    ctx = Context(ffi.AMSM_PALLAS, device=ffi.AMSM_DEVICE_HOST)
+    sizes = [0, 1, 256, 257, 1025, (1 << 18) + 1, (1 << 22) + 1, (1 << 32) - 256]
+    for n in sizes:
+        assert ctx.vec_grid(n) == (max(1, min(-(-n // 256), 256 * 64)), min(-(-n // 256), 1024)), n
+    a, b = ctx.random_vector(1, 1500, mont=True), ctx.random_vector(2, 1500, mont=True)
+    before = compute_hp(ctx, a, b).download()
+    ctx.set_vec_grid_max(4)
+    for n in sizes:
+        assert ctx.vec_grid(n) == (max(1, min(-(-n // 256), 4)), min(-(-n // 256), 4)), n
+    assert np.array_equal(compute_hp(ctx, a, b).download(), before)
+    assert built_lib.amsm_ctx_vec_grid(ctx._h, 1 << 32, None, None) == ffi.AMSM_E_INVALID_ARG
+    assert built_lib.amsm_ctx_vec_grid(ctx._h, 5, None, None) == ffi.AMSM_OK  # either pointer may be NULL
+    ctx.set_vec_grid_max(0)
+    assert ctx.vec_grid(1025) == (5, 5)
+    ctx.close()
+
+
 def test_product_does_not_import_oracle():
     """The shipped package must never route through oracle/ (it is test infrastructure)."""
     pkg = os.path.join(ROOT, "accumulation_amd")

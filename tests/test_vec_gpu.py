@@ -9,7 +9,8 @@ from tests import helpers as h
 
 pytestmark = pytest.mark.gpu
 CURVES = [o.PALLAS, o.BLS12_381_G1]  # the C oracle's curves
-EDGE_CURVES = CURVES + [h.VESTA]  # the edge-value test compares with Python integers only
+# the edge-value test compares with Python integers only: every curve of the library
+EDGE_CURVES = CURVES + [h.VESTA, h.BN254, h.GRUMPKIN, h.BLS12_377]
 
 
 @pytest.fixture(scope="module")
@@ -159,17 +160,13 @@ def test_hp_accumulation_decider_identity(ctxs):
     assert got[0] == C1 and got[1] == C2 and got[2] == C3
 
 
-@pytest.mark.parametrize("c", EDGE_CURVES, ids=lambda c: c.name)
-def test_scalar_field_kernels_on_edge_values(ctxs, c):
+def edge_value_pass(ctx, c):
     """The scalar-field kernels take Montgomery limbs as they are, so the limb patterns a carry chain cares about can be fed
     directly: 0, 1, r - 1, r - 2, all-ones words, single high bits, 2^k - 1, values just below the modulus in every limb.
     Every pair goes through the Hadamard product, a two-vector combination with edge coefficients, the inner product and
     compute_t_vecs, against Python integers (Montgomery product = a b R^-1 mod r)."""
     from accumulation_amd.hp_as import combine_vectors, compute_hp, compute_t_vecs
     from accumulation_amd.ipa_pc import InnerProductArgPC as IpaPC
-    from accumulation_amd.scalar_field import Fr
-    ctx = ctxs[c.name]
-    fr = Fr(ctx.curve)
     r = c.r
     R = 1 << 256
     Rinv = pow(R, -1, r)
@@ -212,3 +209,11 @@ def test_scalar_field_kernels_on_edge_values(ctxs, c):
                            [[x * Rinv % r for x in B], [x * Rinv % r for x in A]], [x * Rinv % r for x in mu], len(A), None)
     for k, tv in enumerate(t):
         assert h.np_to_ints(tv.download()) == [x * R % r for x in exp[k]], k
+    return len(A)
+
+
+@pytest.mark.parametrize("c", EDGE_CURVES, ids=lambda c: c.name)
+def test_scalar_field_kernels_on_edge_values(ctxs, c):
+    """edge_value_pass on the grids that ship (one element per lane at this size; tests/test_vec_stride_gpu.py runs the same
+    pass with the grids capped, where the edge operands also go through the loops' second iteration)"""
+    edge_value_pass(ctxs[c.name], c)
