@@ -6,10 +6,10 @@ import struct
 
 from oracle import pyref as o
 from oracle import pyref_ser as ser
+from tests.helpers import VESTA
 
 PALLAS = o.PALLAS
 BLS = o.BLS12_381_G1
-VESTA = o.Curve("vesta", 2, p=PALLAS.r, r=PALLAS.p, b=5, gx=PALLAS.r - 1, gy=2, limbs=4)
 CURVES = {"pallas": PALLAS, "bls12_381": BLS, "vesta": VESTA}
 BLS_COFACTOR = 0x396C8C005555E1568C00AAAB0000AAAB
 MAX_ATTEMPTS = 256

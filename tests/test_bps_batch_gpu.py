@@ -75,11 +75,11 @@ def test_units_of_uniform_vectors_vs_c_oracle_and_single_calls(cref, V):
 
 def _bn254_case(ctx, n, seeds, cref):
     from accumulation_amd import CommitterKey
-    from tests.test_bn254_gpu import BN254, expect, ints, mults
+    from tests.curve_rows import expect, ints, mults
     ck = CommitterKey.generate(ctx, KEY_SEED, n)
     mult = mults(KEY_SEED, n)
     scs = [cref.rng_scalars(s, n) for s in seeds]
-    return ck, scs, [expect(mult, ints(sc)) for sc in scs], lambda xy, inf: h.np_to_point(BN254, xy, inf)
+    return ck, scs, [expect(h.BN254, mult, ints(sc)) for sc in scs], lambda xy, inf: h.np_to_point(h.BN254, xy, inf)
 
 
 @pytest.mark.parametrize("curve,n", [("pallas", N16 + 12345), ("bls12_381_g1", N16 + 12345), ("bn254_g1", N16 + 12345), ("pallas", 1 << 17)])

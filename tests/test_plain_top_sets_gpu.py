@@ -4,24 +4,20 @@ Grumpkin and BLS12-377, 786 432 on BLS12-377 --, every forced count at the small
 group bit lies inside, at the edge of and above the bits that pick the top set, empty and lopsided top sets, and one MSM cut into a
 range with four sets and one with two.
 
-No big oracle: a generated key has G_i = k_i G with k_i = rng_scalar(seed, i) (restated with numpy in tests/test_bn254_gpu.py), so
+No big oracle: a generated key has G_i = k_i G with k_i = rng_scalar(seed, i) (restated with numpy in tests/curve_rows.py), so
 sum s_i G_i = (sum s_i k_i mod r) G, one scalar multiplication in Python.  tests/test_top_sets_cpu.py pins the rule without a GPU."""
 import numpy as np
 import pytest
 
 from oracle import pyref as o
 from tests import helpers as h
-from tests import test_bls12_377_gpu as t377
-from tests import test_bn254_gpu as tbn
-from tests import test_grumpkin_gpu as tgr
+from tests.curve_rows import edge_scalars, ints, mults  # (the multiplier stream of generated keys is the same on every curve)
 
 pytestmark = pytest.mark.gpu
 
 SEED = 0x5EED70B5
 PLAIN = 2  # AMSM_BASES_NO_PRECOMPUTE
-CURVES = {"pallas": o.PALLAS, "bls12_381_g1": o.BLS12_381_G1, "bn254_g1": tbn.BN254, "grumpkin": tgr.GRUMPKIN, "bls12_377_g1": t377.C}
-EDGE = {"bn254_g1": tbn.edge_scalars, "grumpkin": tgr.edge_scalars, "bls12_377_g1": t377.edge_scalars}
-ints, mults = tbn.ints, tbn.mults  # (the multiplier stream of generated keys is the same on every curve)
+CURVES = {c.name: c for c in (o.PALLAS, o.BLS12_381_G1, h.BN254, h.GRUMPKIN, h.BLS12_377)}
 
 
 def expect(c, mult, scalars):
@@ -70,7 +66,7 @@ def test_long_plain_keys_take_the_bucket_per_lane_pipeline(built_lib, monkeypatc
     try:
         ck = CommitterKey.generate(ctx, SEED, n, PLAIN)
         assert not ck.precomputed
-        sc, edge = uniform(ctx, 31, n), EDGE[name]()
+        sc, edge = uniform(ctx, 31, n), edge_scalars(c)
         sc[:len(edge)] = edge
         sc[n - len(edge):] = edge
         res, moved, tops = msm(ctx, ck, sc)
@@ -130,7 +126,7 @@ def test_grouped_msm_with_eight_top_sets(built_lib, monkeypatch):
     """multi_scalar_mul_grouped over a plain key of 2^18 + 2 pairs, AMSM_TOP_SETS=8: group bit 0, 1, 2 (inside the three bits that
     pick the top set: squeezed out of them) and 17 (above them) -- both sums against the oracle and the two-set context's"""
     from accumulation_amd import CommitterKey, VariableBaseMSM
-    c, n = t377.C, (1 << 18) + 2
+    c, n = h.BLS12_377, (1 << 18) + 2
     mult, out = mults(SEED, n), {}
     for top_sets in (2, 8):
         ctx = make_ctx(c, monkeypatch, top_sets)
@@ -170,7 +166,7 @@ def test_empty_and_lopsided_top_sets(built_lib, monkeypatch):
     Scalars non-zero only at indices that are 1 mod 4: ONE top set carries the whole top window -- it fits, or the overflow flag sends
     the MSM to the chunked re-run (at most one fallback); the sum is exact either way."""
     from accumulation_amd import CommitterKey
-    c, n = tbn.BN254, (1 << 18) + 1
+    c, n = h.BN254, (1 << 18) + 1
     mult = mults(SEED, n)
     ctx = make_ctx(c, monkeypatch, 4)
     try:
@@ -195,7 +191,7 @@ def test_empty_and_lopsided_top_sets(built_lib, monkeypatch):
 def test_msm_cut_into_a_range_with_four_sets_and_one_with_two(built_lib, monkeypatch):
     """BN254, 2^20 + 2^18 + 1 pairs over a plain key: a range of 2^20 pairs (four top sets) and one of 2^18 + 1 (two)"""
     from accumulation_amd import CommitterKey
-    c, n = tbn.BN254, (1 << 20) + (1 << 18) + 1
+    c, n = h.BN254, (1 << 20) + (1 << 18) + 1
     ctx = make_ctx(c, monkeypatch)
     try:
         ck = CommitterKey.generate(ctx, SEED, n, PLAIN)

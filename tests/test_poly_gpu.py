@@ -14,12 +14,12 @@ import numpy as np
 import pytest
 
 from oracle import pyref as o
+from tests.helpers import VESTA
 
 pytestmark = pytest.mark.gpu
 
 TILE = 1024  # coefficients per workgroup (accumulation_amd/csrc/msm_types.h: POLY_T)
 HOST_MAX_LOG = 18
-VESTA = o.Curve("vesta", 2, p=o.PALLAS.r, r=o.PALLAS.p, b=5, gx=o.PALLAS.r - 1, gy=2, limbs=4)
 CURVES = {c.name: c for c in (o.PALLAS, o.BLS12_381_G1, VESTA)}
 SIZES = [0, 1, 2, 3, 255, 256, 257, TILE - 1, TILE, TILE + 1, 2 * TILE + 1, (1 << 16) + 3, 1 << 20, 1 << 22]
 AMSM_E_INVALID_ARG = -1
