@@ -436,15 +436,18 @@ int msm_plan(amsm_ctx* ctx, Slot* sl, const MsmJob& job, bool* short_prep_out, c
     TRY(ensure(sl->buckets, (size_t)g.B * rec));  // MSM will stand in its call (msm_enqueue knows, callers that reserve first do not)
     return reserve_tail<Fq>(ctx, sl, g.n_sets, msel::tail_plan_any_place(g.nb, g.n_sets, g.B, g.E, g.bpl == 1u));
   };
+  auto prep_reserve = [&](const PrepNeeds& nd) -> int {  // a bucket-per-lane / bucket-split MSM (prep_geom.h: what its prep chain needs)
+    TRY(ensure(sl->vals_a, nd.vals_a));
+    TRY(ensure(sl->vals_b, nd.vals_b));
+    TRY(ensure(sl->bpl_grp, nd.bpl_grp));
+    TRY(ensure(sl->bpl_order, nd.bpl_order));
+    TRY(common());
+    return ensure(sl->prep_small, nd.prep_small);
+  };
   if (ch.pipeline == msel::BUCKET_PER_LANE && bpl_geom(ctx, bases, base_off, n, group_shift, ch.plain_window, &g)) {
     sl->geom = g;
     if (eff) *eff = bases;
-    TRY(ensure(sl->vals_a, prep_bpl_part_entries(g) * 8 + 64));                                     // 64-bit interchange entries
-    TRY(ensure(sl->vals_b, (size_t)prep_bpl_partitions(g) * prep_bpl_stride(g) * 4 + 64));          // transposed blocks
-    TRY(ensure(sl->bpl_grp, (size_t)prep_bpl_partitions(g) * prep_bpl_groups_per_partition() * 8 + 64));
-    TRY(ensure(sl->bpl_order, (size_t)prep_bpl_partitions(g) * prep_bpl_groups_per_partition() * 64 * 4 + 64));
-    TRY(common());
-    TRY(ensure(sl->prep_small, 64 + prep_small_words(g) * sizeof(u32) + 256));
+    TRY(prep_reserve(prep_bpl_needs(g)));
     *short_prep_out = true;
     return AMSM_OK;
   }
@@ -453,13 +456,7 @@ int msm_plan(amsm_ctx* ctx, Slot* sl, const MsmJob& job, bool* short_prep_out, c
   if (eff) *eff = bases;
   if (ch.pipeline == msel::BUCKET_SPLIT && bps_geom(ctx, bases, base_off, n, group_shift, &g)) {
     sl->geom = g;
-    const u32 P = prep_bps_partitions(g, g.bps_log2_l);
-    TRY(ensure(sl->vals_a, prep_bps_part_entries(g, g.bps_log2_l) * 4 + 64));
-    TRY(ensure(sl->vals_b, (size_t)P * prep_bps_stride(g, g.bps_log2_l) * 4 + 64));
-    TRY(ensure(sl->bpl_grp, (size_t)P * 16 * 8 + 64));
-    TRY(ensure(sl->bpl_order, (size_t)g.B * 4 + 64));  // position in a partition's size order -> bucket
-    TRY(common());
-    TRY(ensure(sl->prep_small, 64 + prep_small_words(g) * sizeof(u32) + 256));
+    TRY(prep_reserve(prep_bps_needs(g)));
     *short_prep_out = true;
     return AMSM_OK;
   }
@@ -496,7 +493,7 @@ int msm_plan(amsm_ctx* ctx, Slot* sl, const MsmJob& job, bool* short_prep_out, c
   // arrays, so that ONE fill clears both
   const bool short_prep = prep_supported(g);
   if (short_prep) {
-    TRY(ensure(sl->prep_small, 64 + prep_small_words(g) * sizeof(u32) + 256));
+    TRY(ensure(sl->prep_small, prep_small_bytes(g)));
   } else {  // only the rocPRIM chain sorts (key, value) pairs
     TRY(ensure(sl->misc, 64));
     TRY(ensure(sl->keys_a, (size_t)g.E * 4));
@@ -752,13 +749,12 @@ int msm_enqueue(amsm_ctx* ctx, Slot* sl, const MsmJob& job, Place place) {
 }
 
 // ---- a unit of bucket-split MSMs: one launch per pipeline stage (msm_select.h: batch_units; DESIGN.md 4.2h) ----
-// What ONE bucket-split MSM of geometry g takes of a slot: msm_plan's expressions for vals_a, vals_b, bpl_grp, bpl_order, buckets and
-// prep_small.  batch_units keeps a unit's V of them below msel::BPS_BATCH_MAX_BYTES.
+// What ONE bucket-split MSM of geometry g takes of a slot: what msm_plan reserves for its prep (prep_geom.h: prep_bps_needs) and its
+// buckets.  batch_units keeps a unit's V of them below msel::BPS_BATCH_MAX_BYTES.
 template <class Fq>
 size_t bps_slot_bytes(const MsmGeom& g) {
-  const u32 P = prep_bps_partitions(g, g.bps_log2_l);
-  return (prep_bps_part_entries(g, g.bps_log2_l) * 4 + 64) + ((size_t)P * prep_bps_stride(g, g.bps_log2_l) * 4 + 64) + ((size_t)P * 16 * 8 + 64) +
-         ((size_t)g.B * 4 + 64) + (size_t)g.B * xyzz_bytes<Fq>() + (64 + prep_small_words(g) * sizeof(u32) + 256);
+  const PrepNeeds nd = prep_bps_needs(g);
+  return nd.vals_a + nd.vals_b + nd.bpl_grp + nd.bpl_order + (size_t)g.B * xyzz_bytes<Fq>() + nd.prep_small;
 }
 // The unit as its tail sees it: nv * n_sets bucket sets in one table, one result ("group") per MSM -- what msm_collect's horner hands out
 inline MsmGeom bps_unit_geom(const MsmGeom& g, u32 nv) {
@@ -792,15 +788,15 @@ template <class Fq>
 int bps_batch_plan(amsm_ctx* ctx, Slot* sl, const MsmGeom& g, size_t nv, BpsBatchPlan* out) {
   if (nv < 2 || nv > (size_t)msel::BPS_BATCH || g.bpl != 2u || g.n_sets != 1u || g.S > 16u) return AMSM_E_INVALID_ARG;
   const size_t rec = xyzz_bytes<Fq>();
-  const u32 P = prep_bps_partitions(g, g.bps_log2_l);
+  const PrepNeeds nd = prep_bps_needs(g);
   BpsBatchBuffers& b = out->buf;
   // MSM v's share of every buffer: what msm_plan gives a single MSM (the 64 bytes of slack included), v strides in
   b.small_stride = prep_bps_small_block_words();
-  b.part_stride = (u32)(prep_bps_part_entries(g, g.bps_log2_l) + 16);
-  b.ents_stride = (u32)((size_t)P * prep_bps_stride(g, g.bps_log2_l) + 16);
-  b.grp_stride = P * 16u + 8u;
-  b.order_stride = g.B + 16u;
-  if ((unsigned long long)P * prep_bps_stride(g, g.bps_log2_l) + 16ull >= (1ull << 31)) return AMSM_E_INVALID_ARG;
+  b.part_stride = (u32)(nd.vals_a / 4);    // words
+  b.ents_stride = (u32)(nd.vals_b / 4);    // words
+  b.grp_stride = (u32)(nd.bpl_grp / 8);    // headers
+  b.order_stride = (u32)(nd.bpl_order / 4);  // words
+  if (nd.vals_b / 4 >= ((size_t)1 << 31)) return AMSM_E_INVALID_ARG;
   TRY(ensure(sl->vals_a, nv * (size_t)b.part_stride * 4));
   TRY(ensure(sl->vals_b, nv * (size_t)b.ents_stride * 4));
   TRY(ensure(sl->bpl_grp, nv * (size_t)b.grp_stride * 8));

@@ -36,14 +36,11 @@ void launch_accum_bpl<AMSM_FQ>(hipStream_t st, const u32* table, const u32* ents
   if (wg_per_cu == 1u) pad = 82u * 1024u > STATIC_LDS ? 82u * 1024u - STATIC_LDS : 0u;
   else if (wg_per_cu == 2u) pad = 54u * 1024u > STATIC_LDS ? 54u * 1024u - STATIC_LDS : 0u;
   if (STATIC_LDS + pad > 64u * 1024u) {  // opt in, once per device
-    static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
-    if (dev == 63 || !(done.load(std::memory_order_acquire) & (1ull << dev))) {
+    static DeviceOnce once;
+    once.run([] {
       (void)hipFuncSetAttribute((const void*)k_accum_bpl<FQD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
       (void)hipFuncSetAttribute((const void*)k_accum_bpl<FQD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-      done.fetch_or(1ull << dev, std::memory_order_release);
-    }
+    });
   }
   if (accumulate)
     hipLaunchKernelGGL((k_accum_bpl<FQD, true>), dim3(cdiv_(n_groups, 4)), dim3(256), pad, st, table, ents_t,

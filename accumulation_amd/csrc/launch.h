@@ -5,12 +5,30 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 
 #include "blind.h"
 #include "msm_select.h"
 #include "msm_types.h"
+#include "prep_geom.h"
 
 namespace amsm {
+
+// What a launcher must do once per DEVICE before its kernel runs there -- opting in to more than 64 KiB of dynamic LDS: the attribute
+// is per device, a second context on another GPU of the same process needs its own.  One bit per device; a device the runtime does
+// not name (or beyond 62) takes bit 63, which never counts as done: there the work is repeated on every call.
+struct DeviceOnce {
+  std::atomic<unsigned long long> done{0};
+  template <class F>
+  void run(F&& f) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
+    const unsigned long long bit = 1ull << dev;
+    if (dev != 63 && (done.load(std::memory_order_acquire) & bit)) return;
+    f();
+    done.fetch_or(bit, std::memory_order_release);
+  }
+};
 
 // ---- per-curve (Fq) launchers ------------------------------------------------------------------
 template <class Fq>
@@ -128,8 +146,8 @@ template <class Fr>
 void launch_digits(hipStream_t st, const u32* scalars, int mont, MsmGeom g, void* keys, bool keys16, u32* vals, u32* err);
 // Custom prep chain (prep_kernels.h): scalars -> sorted entry list + bucket table in 7 dispatches.  d_small holds
 // prep_small_words(g) words (partition totals, starts, cursors, partial counts, the heavy-partition tables); the launcher
-// zeroes what needs it.
-size_t prep_small_words(const MsmGeom& g);
+// zeroes what needs it.  The geometry of the three chains -- what they support, their partitions, strides and buffer needs -- is
+// prep_geom.h's.
 struct PrepBuffers {
   u32* d_small;       // >= prep_small_words(g) words (+ 256 bytes of slack), directly behind the 16 words at `err`
   u32* part;          // E words: entries grouped by partition
@@ -139,29 +157,19 @@ struct PrepBuffers {
   u32* item_off;      // B + 2 words
   u32* err;           // == d_small - 16: the MSM's flag words, cleared by the same fill
 };
-bool prep_supported(const MsmGeom& g);
 // Bucket-per-lane prep (prep_kernels.h: hist, scan, wide scatter, k_prep_local_t): 4 dispatches + the fill
 struct PrepBplBuffers {
   u32* d_small;   // as PrepBuffers
   u32* part;      // 2 * E words: 64-bit interchange entries
-  u32* ents_t;    // P * stride words: the transposed entry blocks
+  u32* ents_t;    // P * stride words: the transposed entry blocks (prep_bpl_stride / prep_bps_stride entries per partition)
   void* grp;      // partitions x prep_bpl_groups_per_partition() group headers (8 bytes each)
   u32* order;     // 64 words per group: the bucket every lane slot sums
   u32* err;       // == d_small - 16; err[1] = overflow (the host falls back to the chunked pipeline)
 };
-bool prep_bpl_supported(const MsmGeom& g);
-u32 prep_bpl_stride(const MsmGeom& g);  // entries per partition block of ents_t
-u32 prep_bpl_partitions(const MsmGeom& g);
-size_t prep_bpl_part_entries(const MsmGeom& g);
-size_t prep_bps_part_entries(const MsmGeom& g, u32 log2_l);  // 4-byte interchange entries of the bucket-split prep  // 8-byte interchange entries the partition pass may write
-u32 prep_bpl_groups_per_partition();  // group headers (and 64-lane blocks of `order`) per partition
 template <class Fr>
 int launch_prep_bpl(hipStream_t st, const u32* scalars, int mont, MsmGeom g, const PrepBplBuffers& b);
 // Bucket-split prep for small / medium MSMs (prep_kernels.h: k_prep_local_s): every bucket on 2^log2_l adjacent lanes.
-// prep_bps_choose: log2 of the lanes per bucket for this geometry, or -1 when it does not take this pipeline.
-int prep_bps_choose(const MsmGeom& g);
-u32 prep_bps_partitions(const MsmGeom& g, u32 log2_l);
-u32 prep_bps_stride(const MsmGeom& g, u32 log2_l);
+// log2_l: prep_bps_choose(g).
 template <class Fr>
 int launch_prep_bps(hipStream_t st, const u32* scalars, int mont, MsmGeom g, u32 log2_l, const PrepBplBuffers& b);
 template <class Fq>
@@ -181,7 +189,6 @@ struct BpsBatchBuffers {
   u32* order;        // bucket order
   u32 order_stride;  // words
 };
-u32 prep_bps_small_block_words();  // the words of a block that must start at zero, rounded up to a whole number of 256-byte lines
 // the fill, the scatter and the local sort of the whole unit: three commands
 template <class Fr>
 int launch_prep_bps_batch(hipStream_t st, const u32* const* scalars, u32 nv, int mont, MsmGeom g, u32 log2_l, const BpsBatchBuffers& b);

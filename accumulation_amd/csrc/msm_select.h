@@ -289,8 +289,8 @@ inline void classify(const VecProbe* vec, size_t k, bool mont, const KeyDesc& ke
 }
 
 // ---- plain keys on the bucket-per-lane pipeline: how many bucket sets the TOP window owns --------------------------------------------
-// The prep sorts one 1024-bucket partition per workgroup in an LDS stage of BPL_STAGE_CAP entries (kern_fr.hip asserts the figure
-// against k_prep_local_t's layout).  bpl_stage_fits: the two inequalities every bucket-per-lane geometry must meet (kern_fr.hip:
+// The prep sorts one 1024-bucket partition per workgroup in an LDS stage of BPL_STAGE_CAP entries (prep_geom.h asserts the figure
+// against k_prep_local_t's layout).  bpl_stage_fits: the two inequalities every bucket-per-lane geometry must meet (prep_geom.h:
 // prep_bpl_supported calls it) -- E entries over P partitions, the average one with 1024 to spare, and the fullest one expected on
 // uniform scalars (part_max; 0: not known) with 5 sigma of the digits' spread to spare (sigma = sqrt(part_max): ~180 at 30 k).
 constexpr unsigned BPL_STAGE_CAP = 37340;

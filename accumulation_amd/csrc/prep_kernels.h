@@ -25,37 +25,17 @@
 #include "fp.h"
 #include "msm_select.h"  // BPS_BATCH
 #include "msm_types.h"
+#include "prep_geom.h"  // PrepGeom, PrepHeavy and the constants the host sizes the launches by
 #include "vec_kernels.h"  // digit_step
 
 namespace amsm {
-
-struct PrepGeom {
-  u32 SH;   // log2(buckets per partition)
-  u32 P;    // partitions = ceil(B / 2^SH)
-  u32 SPB;  // scalars per workgroup of k_prep_hist / k_prep_scatter (256 lanes x 2)
-  u32 IB;   // bits of a table index (entry word: negate | bucket id low bits << IB | index)
-  u32 CAP;  // entries k_prep_local can assemble in LDS (larger partitions scatter straight to memory)
-  u32 HEAVY;  // partitions with more entries than this are split over PREP_HEAVY_SLICES workgroups (k_prep_heavy_*)
-  // FIX != 0 (bucket-per-lane prep, round 3): partition p owns entries [p * FIX, (p + 1) * FIX) of the interchange buffer --
-  // no histogram, no scan: uniform digits fill a partition to E / P +- a few hundred entries, and FIX = CAP, what
-  // k_prep_local_t can stage anyway; a partition that would overflow drops the excess and its count (the cursor) trips the
-  // overflow flag there, i.e. the skew fallback that a partition above CAP takes in any case
-  u32 FIX;
-};
 
 // A skewed digit distribution (the all-equal vectors the reference's harness commits to put a whole
 // window into ONE bucket) makes a few partitions hold millions of entries.  One workgroup streams at one CU's share of
 // the memory system (~30 GB/s: 0.45 ms per million entries for the two passes), so such partitions are listed by
 // k_prep_scan and processed by PREP_HEAVY_SLICES workgroups each: k_prep_heavy_count (per-bucket totals), k_prep_local
 // (offsets only) and k_prep_heavy_place (slices reserve runs in their buckets with one global atomicAdd per bucket).
-constexpr u32 PREP_HEAVY_SLICES = 64, PREP_HEAVY_GRID = 1024, PREP_MAX_HEAVY = 4096;
-struct PrepHeavy {
-  u32* n;      // number of heavy partitions (k_prep_scan)
-  u32* ids;    // their ids
-  u32* cnt;    // B words, zeroed by the launcher: entries per bucket (heavy partitions only)
-  u32* cur;    // B words: running cursor of every bucket of a heavy partition (offset inside the partition)
-  u32* end;    // B words: end offset of the bucket inside the partition
-};
+constexpr u32 PREP_HEAVY_SLICES = 64, PREP_HEAVY_GRID = 1024;  // (PREP_MAX_HEAVY, PrepHeavy: prep_geom.h)
 
 constexpr u32 PREP_ENTRY_LAST = 0x40000000u;  // == ENTRY_LAST of msm_kernels.h
 
@@ -589,19 +569,8 @@ __global__ void __launch_bounds__(256)
 // stride) raise the overflow flag: every later kernel of the chain returns at once and the host reruns the MSM over the
 // key's 17-bit-window table through the chunked pipeline above, which is built for exactly those inputs.
 // ---------------------------------------------------------------------------------------------
-constexpr u32 BPL_GROUP = 64;            // lanes per accumulate wave
 constexpr u32 BPL_ENTRY_PAD = 0x40000000u;  // padding entry (bit 30; the last-of-bucket flag is not used in this pipeline)
-constexpr u32 BPL_BINS = 256;            // size classes of the bucket ordering (sizes >= 255 share the last one)
-// The 64 LARGEST buckets of a partition are split in two halves, one lane each, whose sums the accumulate kernel adds with one
-// lane exchange.  On uniform scalars the largest are the buckets the spread top window feeds (MsmGeom::top_shift: every 32nd
-// bucket holds ~88 entries against ~24; Pallas has 32 of them per partition, BLS12-381 64): unsplit, the group holding them
-// ran 108 rows with half its lanes idle after 35 (rows per MSM 242 k -> 225 k, 88 % -> 94 % of the lane-iterations useful).
-// Lane slots of a partition: [0, 64) halves of the buckets at positions 0..31 of the size order | [64, 1024) the buckets at
-// positions 64..1023, one lane each | [1024, 1088) halves of positions 32..63 -- 17 groups of 64 lanes, rows nearly descending.
-constexpr u32 BPL_SPLIT = 64;
-constexpr u32 BPL_NB = 1024;                                   // buckets per partition
-constexpr u32 BPL_LANES = BPL_NB + BPL_SPLIT;                  // 1088 lane slots per partition
-constexpr u32 BPL_GROUPS = BPL_LANES / BPL_GROUP;              // 17
+// (BPL_GROUP, BPL_BINS, BPL_SPLIT, BPL_NB, BPL_LANES, BPL_GROUPS -- the lane slots of a partition -- and BPS_LANES, BPS_GROUPS: prep_geom.h)
 struct BplGroup {
   u32 base;  // first entry of the group's transposed block in ents_t
   u32 m;     // rows = entries of its largest lane
@@ -638,9 +607,11 @@ AMSM_DEV u32 block_scan_inclusive(u32 v, u32* wt) {
 }
 
 // k_prep_local_t keeps its partition in REGISTERS between the count and the placement pass: entry i * 1024 + t in slot i of
-// lane t, BPL_LOCAL_SLOTS slots (kern_fr.hip asserts that they hold CAP entries), loaded and walked in blocks of
+// lane t, BPL_LOCAL_SLOTS slots, loaded and walked in blocks of
 // BPL_SLOT_BLOCK that a short partition skips whole.  f(b): slots [b, b + BPL_SLOT_BLOCK), b a constant after unrolling.
 constexpr u32 BPL_LOCAL_SLOTS = 37, BPL_SLOT_BLOCK = 8;
+static_assert(BPL_LOCAL_BUDGET_WORDS - BPL_LOCAL_FIXED_WORDS <= BPL_LOCAL_SLOTS * BPL_NB,
+              "k_prep_local_t keeps a partition of CAP entries in BPL_LOCAL_SLOTS registers per lane");
 template <class F>
 AMSM_DEV void bpl_slot_blocks(u32 n, F&& f) {
 #pragma unroll
@@ -648,7 +619,7 @@ AMSM_DEV void bpl_slot_blocks(u32 n, F&& f) {
     if (b * BPL_NB < n) f(b);  // (the same in every lane of the workgroup)
 }
 
-// dynamic LDS: (3 * NB + 2 * BPL_BINS + 2 * BPL_GROUPS + 2 + CAP) words, NB = 2^SH = 1024 (kern_fr.hip: BPL_LOCAL_FIXED_WORDS).
+// dynamic LDS: (3 * NB + 2 * BPL_BINS + 2 * BPL_GROUPS + 2 + CAP) words, NB = 2^SH = 1024 (prep_geom.h: BPL_LOCAL_FIXED_WORDS).
 // The partition is read from memory ONCE, every load of a lane in flight before the first is used (the earlier two passes
 // of one dependent 8-byte load per trip were latency chains on a CU this workgroup holds alone); the prefix sums are
 // wave-level; the transposed write gives whole rows to waves, so that a lane looks its slot's bucket up once per group and the
@@ -799,7 +770,6 @@ __global__ void __launch_bounds__(1024)
 // 32-bit interchange entries as in k_prep_local (negate | bucket low bits << IB | index).
 // dynamic LDS: see k_prep_local_s; NBP = 2^SH = 1024 / L buckets per partition.
 // ---------------------------------------------------------------------------------------------
-constexpr u32 BPS_LANES = 1024, BPS_GROUPS = BPS_LANES / BPL_GROUP;  // lane slots / 64-lane groups per partition
 // Round 3, late: the partition's buckets are ORDERED BY SIZE (descending, counting sort over BPL_BINS size classes, as in
 // k_prep_local_t) before they are laid on the lanes: a group's rows are its largest part, and 32 neighbouring buckets of a
 // uniform 2^16-pair MSM spread over 8 +- 2 entries per part -- 12.4 rows for 8.3 of work; sorted, a group's parts differ by
