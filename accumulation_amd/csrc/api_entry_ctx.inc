@@ -299,6 +299,7 @@ int amsm_ctx_batched_split_stats(const amsm_ctx* c, unsigned long long* n_units,
 }
 
 unsigned long long amsm_ctx_two_valued_msms(const amsm_ctx* c) { return c ? c->n_two_valued : 0ull; }
+unsigned long long amsm_ctx_heavy_buckets(const amsm_ctx* c) { return c ? c->n_heavy_buckets : 0ull; }
 unsigned long long amsm_ctx_unit_scalar_msms(const amsm_ctx* c) { return c ? c->n_ones_split : 0ull; }
 unsigned long long amsm_ctx_direct_sum_msms(const amsm_ctx* c) { return c ? c->n_direct : 0ull; }
 unsigned long long amsm_ctx_shared_bucket_msms(const amsm_ctx* c) { return c ? c->n_shared : 0ull; }

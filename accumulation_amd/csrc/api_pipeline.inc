@@ -914,6 +914,9 @@ int msm_collect(amsm_ctx* ctx, Slot* sl, host::HXYZZ<Fq>* out) {
     else ctx->n_bpl_fallbacks++;
     TRY(sl->rerun(ctx, sl));
     return msm_collect<Fq>(ctx, sl, out);  // the re-run is chunked: no second fallback
+  } else if (!g.bpl) {
+    // the chunked pipeline's second flag word is k_accum_l1's count of heavy buckets (a direct sum leaves it zero): amsm_ctx_heavy_buckets
+    ctx->n_heavy_buckets += *(u32*)((char*)h + g.n_sets * rec + 4);
   }
   // one result per group: Horner over the group's window sums (plain key) or its single record (precomputed key)
   const u32 sets = g.n_sets / g.groups, per = sets - g.top_split;  // per = windows (the top one owns 1 + top_split sets)

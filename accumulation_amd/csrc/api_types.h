@@ -278,6 +278,7 @@ struct amsm_ctx {
   hipStream_t s_tv = nullptr;
   hipEvent_t tv_done = nullptr;
   unsigned long long n_two_valued = 0;
+  unsigned long long n_heavy_buckets = 0;  // buckets of more than tune::K1 partial records over the chunked MSMs collected so far (msm_collect)
   // ---- multi-device (amsm_ctx_create_multi) ----
   // shard_ctx[0] == this (the primary); shard_ctx[g >= 1] are owned single-device contexts, each served by one host
   // worker thread so that the blocking single-device pipeline runs on all devices at once.

@@ -132,6 +132,11 @@ class Context:
         """MSMs of device vectors that took the two-valued form (every scalar 0 or one value v) so far"""
         return int(self._lib.amsm_ctx_two_valued_msms(self._h))
 
+    def heavy_buckets(self) -> int:
+        """buckets of more than 1024 partial records over the chunked MSMs collected so far: the ones that took the heavy path of
+        the accumulation (amsm_ctx_heavy_buckets)"""
+        return int(self._lib.amsm_ctx_heavy_buckets(self._h))
+
     def pipeline_stats(self) -> dict:
         """MSMs that took the bucket-per-lane pipeline / that fell back to the chunked one (amsm_ctx_pipeline_stats)"""
         a, b = C.c_ulonglong(), C.c_ulonglong()

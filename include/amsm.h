@@ -168,6 +168,11 @@ unsigned long long amsm_ctx_collectives(const amsm_ctx* ctx);
  * with a non-zero scalar).  ark-ec's multi_scalar_mul special-cases the scalars 0 and 1 the same way (ark-ec ^0.2.0 msm, not
  * in /root/reference: Cargo.toml:15); the reference's hp_as inputs are `vec![rand; n]` (src/hp_as/mod.rs:189-190). */
 unsigned long long amsm_ctx_two_valued_msms(const amsm_ctx* ctx);
+/* Heavy buckets over all MSMs of the chunked pipeline this context has collected so far: buckets that received more than 1024
+ * partial records (skewed digit distributions: constant vectors) and were therefore summed by the two-step heavy
+ * path (32 workgroups per bucket, then one folding wave) instead of one lane group.  The count rides to the host with the MSM's
+ * result, so reading it costs nothing; a host-backend context reports 0.  Results do not depend on the path. */
+unsigned long long amsm_ctx_heavy_buckets(const amsm_ctx* ctx);
 /* MSMs of device vectors whose UNIT scalars were summed apart (round 5): a vector that is not two-valued but holds a share of
  * ones -- the boolean wires of an R1CS witness -- would put all of them into bucket 1 of the lowest window (2.2x slower than a
  * uniform vector at 2^18 pairs with 10 % booleans).  The same exact pass that tests for two-valued vectors counts the ones among

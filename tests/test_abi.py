@@ -83,6 +83,7 @@ def test_host_backend_computes_results_where_there_is_no_gpu(built_lib, cref):
                                           hid.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), C.byref(inf)) == ffi.AMSM_OK
     both, both_inf = cref.msm(ffi.AMSM_PALLAS, xy, np.concatenate([sc, cref.rng_scalars(5, 1)]))
     assert inf.value == both_inf and np.array_equal(out, both)
+    assert built_lib.amsm_ctx_heavy_buckets(h) == 0 and built_lib.amsm_ctx_heavy_buckets(None) == 0  # (no pipelines on the host backend)
     built_lib.amsm_bases_free(ck)
     built_lib.amsm_ctx_destroy(h)
 

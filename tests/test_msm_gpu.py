@@ -549,10 +549,13 @@ def test_large_key_precompute_and_fold_batched_affine(ctxs, cref, c):
 
 @pytest.mark.parametrize("mode", ["precomp", "plain"])
 def test_skewed_scalars_heavy_partitions_vs_c_oracle(ctxs, cref, mode):
-    """Constant vectors at a size where one bucket holds more than 2^17 entries: the prep stage then splits the partition
-    over 64 workgroups (k_prep_heavy_count / k_prep_heavy_place).  All-equal, all-one, two values, and a constant vector
-    with a uniform tenth mixed in (giant and ordinary buckets inside one partition), bit-exact against the CPU oracle;
-    the grouped form as well."""
+    """Skewed vectors at a size where one bucket holds more than 2^17 entries, bit-exact against the CPU oracle; which path each takes
+    today is asserted by the context's counters.  The constant vectors -- all equal, all one, all r - 1: 2^18 pairs, from 2^17 up a
+    lone vector is probed -- are taken by the two-valued form (k_tv_probe / k_tv_sum) and never reach a bucket.  Two values alternating,
+    and a constant vector with a uniform tenth mixed in (giant and ordinary buckets inside one partition), reach the chunked pipeline --
+    over the plain key behind a bucket-per-lane prep that overflows --, where the prep splits their partitions over 64 workgroups
+    (k_prep_heavy_count / k_prep_heavy_place) and the accumulation lists their buckets as heavy (k_accum_l2a / k_accum_l2b:
+    Context.heavy_buckets()); the grouped form as well.  All six curves, with the two-valued form off too: tests/test_skew_gpu.py."""
     from accumulation_amd import CommitterKey, VariableBaseMSM
     c = o.PALLAS
     ctx = ctxs[c.name]
@@ -571,12 +574,19 @@ def test_skewed_scalars_heavy_partitions_vs_c_oracle(ctxs, cref, mode):
     cases["mostly_equal"] = mixed
     for name, sc in cases.items():
         sc = np.ascontiguousarray(sc)
+        heavy, tv = ctx.heavy_buckets(), ctx.two_valued_msms()
         out, oinf = VariableBaseMSM.multi_scalar_mul(ck, sc)
         ref, rinf = cref.msm(c.curve_id, xy, sc, threads=8)
         assert oinf == rinf and np.array_equal(out, ref), (mode, name)
+        if name in ("two_values", "mostly_equal"):
+            assert ctx.heavy_buckets() > heavy and ctx.two_valued_msms() == tv, (mode, name)
+        else:
+            assert ctx.two_valued_msms() == tv + 1 and ctx.heavy_buckets() == heavy, (mode, name)
     # grouped: two sums over the index classes of bit 17 (= halves), constant scalars
     sc = np.ascontiguousarray(cases["mostly_equal"])
+    heavy = ctx.heavy_buckets()
     out, inf = VariableBaseMSM.multi_scalar_mul_grouped(ck, ctx.upload(sc), 17, mont=False)
+    assert ctx.heavy_buckets() > heavy
     for g in (0, 1):
         masked = sc.copy()
         masked[(np.arange(n) >> 17) & 1 != g] = 0
