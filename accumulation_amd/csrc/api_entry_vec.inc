@@ -290,7 +290,9 @@ int amsm_points_fold(amsm_ctx* c, const void* d_l, const void* d_r, size_t n, co
   u32 canon[8];
   canonical_scalar(c->curve, x_mont, canon);
   u32* scratch = fold_scratch(c, n);
-  DISPATCH_DO(c, launch_points_fold<Fq>(c->stream, (const u32*)d_l, (const u32*)d_r, (u32)n, canon, nbits, (u32*)d_out, true, scratch));
+  FoldDigits d;
+  const bool glv = DISPATCH(c, host::fold_digits<Fq>(canon, nbits, &d));
+  DISPATCH_DO(c, launch_points_fold<Fq>(c->stream, (const u32*)d_l, (const u32*)d_r, (u32)n, d, glv, (u32*)d_out, true, scratch));
   HIP_TRY(hipGetLastError());
   return AMSM_OK;
 }
@@ -330,14 +332,20 @@ int amsm_bases_fold(amsm_ctx* c, const amsm_bases* key, size_t n_half, const uin
   const u32* r = (const u32*)((const char*)key->d_table + n_half * pb);
   u32* scratch = fold_scratch(c, n_half);
   // a key with window multiples folds through them (c + 1 doublings instead of nbits; msm_kernels.h k_points_fold_tab) -- the
-  // top level of a bucket-per-lane table sits 2^top_shift short of its place and is left out
+  // top level of a bucket-per-lane table sits 2^top_shift short of its place and is left out.  An x that does not fit the usable
+  // levels (fold_recode.h: fold_tab_ops says) takes the plain ladder
   bool done = false;
   if (key->precomp && key->W > 1 && key->n < (1ull << 31)) {
     const u32 levels = (u32)(key->top_shift ? key->W - 1 : key->W);
-    done = DISPATCH(c, launch_points_fold_tab<Fq>(c->stream, l, (u32)key->n, (u32)key->c, (u32)key->W, (u32)key->n_narrow, levels,
-                                                  (u32)n_half, canon, nbits, b->d_table, scratch));
+    FoldTabOps ops;
+    done = fold_tab_ops((u32)key->c, (u32)key->W, (u32)key->n_narrow, levels, canon, nbits, &ops);
+    if (done) DISPATCH_DO(c, launch_points_fold_tab<Fq>(c->stream, l, (u32)key->n, (u32)n_half, ops, b->d_table, scratch));
   }
-  if (!done) DISPATCH_DO(c, launch_points_fold<Fq>(c->stream, l, r, (u32)n_half, canon, nbits, b->d_table, false, scratch));
+  if (!done) {
+    FoldDigits d;
+    const bool glv = DISPATCH(c, host::fold_digits<Fq>(canon, nbits, &d));
+    DISPATCH_DO(c, launch_points_fold<Fq>(c->stream, l, r, (u32)n_half, d, glv, b->d_table, false, scratch));
+  }
   if (hipGetLastError() != hipSuccess || hipEventCreateWithFlags(&b->ready, hipEventDisableTiming) != hipSuccess ||
       hipEventRecord(b->ready, c->stream) != hipSuccess) {
     (void)hipGetLastError();

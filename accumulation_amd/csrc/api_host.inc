@@ -83,18 +83,11 @@ host::HXYZZ<Fq> host_mul_cached(const uint64_t* xy, const host::HFe<Fr>& k_mont)
   return fb ? fb->mul(k.v) : host::hx_mul<Fq>(p, k.v);
 }
 
-// The curve's GLV set-up on the host (host_glv.h: lambda, beta, the lattice basis, all verified at first use); null if it failed
+// The curve's GLV set-up on the host (host_glv.h: curve_glv -- lambda, beta, the lattice basis, all verified at first use); null if it
+// failed
 template <class Fq, class Fr>
 const host::Glv<Fq, Fr>* host_glv() {
-  static const host::Glv<Fq, Fr> g = [] {
-    host::Glv<Fq, Fr> t;
-    constexpr int N = host::HFe<Fq>::N;
-    std::vector<u32> g32 = generator_mont<Fq>();
-    u64 gen[2 * N];
-    memcpy(gen, g32.data(), sizeof(gen));
-    t.setup(gen);
-    return t;
-  }();
+  const host::Glv<Fq, Fr>& g = host::curve_glv<Fq>();
   return g.ok ? &g : nullptr;
 }
 

@@ -72,7 +72,6 @@ int ensure_red_ticket(amsm_ctx* ctx, Slot* sl, size_t n_sets) {
   return AMSM_OK;
 }
 
-inline u32 cdiv(u32 a, u32 b) { return (a + b - 1) / b; }
 using msel::ilog2_ceil;
 
 template <class Fq>

@@ -12,6 +12,7 @@
 // Product code (the reference reaches the same group elements through ark-ec's plain `mul`; only canonical affine results are
 // compared).
 #pragma once
+#include "fold_recode.h"
 #include "host_field.h"
 
 namespace amsm {
@@ -326,29 +327,12 @@ struct Glv {
   }
 };
 
-// non-adjacent form of |k| into (pos, neg) masks, swapped when k is negative; returns the number of digit positions
+// non-adjacent form of |k| into (pos, neg) masks of 160 digits, swapped when k is negative; returns the number of digit positions, or
+// 0xffffffff (NAF_NO_FIT) when 160 do not hold it
 inline u32 big_naf(const Big& k, u32 pos[5], u32 neg[5]) {
   Big m = k;
-  m.neg = false;
-  u32 nd = 0;
   for (int i = 0; i < 5; i++) pos[i] = neg[i] = 0;
-  u32* plus = k.neg ? neg : pos;
-  u32* minus = k.neg ? pos : neg;
-  const Big one = big_small(1);
-  for (u32 d = 0; d < 160 && !big_is_zero(m); d++) {
-    if (m.w[0] & 1u) {
-      if ((m.w[0] & 3u) == 1u) {
-        plus[d >> 5] |= 1u << (d & 31);
-        m.w[0] &= ~1u;
-      } else {
-        minus[d >> 5] |= 1u << (d & 31);
-        big_add_mag(m, m, one);
-      }
-      nd = d + 1;
-    }
-    m = big_shr(m, 1);
-  }
-  return big_is_zero(m) ? nd : 0xffffffffu;
+  return naf_words(m.w, Big::N, 160, k.neg ? neg : pos, k.neg ? pos : neg);
 }
 
 template <class Fq, class Fr>
@@ -359,6 +343,49 @@ inline bool glv_digits(const Glv<Fq, Fr>& g, const u64 k[4], GlvDigits& out) {
   if (n1 == 0xffffffffu || n2 == 0xffffffffu) return false;
   out.nd = std::max(n1, n2);
   return true;
+}
+
+// The GLV set-up of the curve over Fq (curves.h), built and verified on first use, once per process: the key folds (fold_digits) and
+// the host's linear combinations (api_host.inc) share it.  Not ok: no split, every caller has a plain form to fall back to.
+template <class Fq>
+inline const Glv<Fq, typename CurveOf<Fq>::type::Fr>& curve_glv() {
+  using G = Glv<Fq, typename CurveOf<Fq>::type::Fr>;
+  static const G g = [] {
+    G t;
+    std::vector<u32> g32 = generator_mont<Fq>();
+    u64 gen[2 * HFe<Fq>::N];
+    memcpy(gen, g32.data(), sizeof(gen));
+    t.setup(gen);
+    return t;
+  }();
+  return g;
+}
+
+// What a fold by the low `nbits` bits of x (canonical, below 2^255) launches with: a full-size scalar is split (half the doublings;
+// true: *d holds both halves and beta), a short one gains nothing and takes the plain non-adjacent form, as does any scalar whose split
+// fails its checks (false).
+template <class Fq>
+inline bool fold_digits(const u32 x_canon[8], u32 nbits, FoldDigits* d) {
+  u32 k[9];
+  if (fold_low_bits(x_canon, nbits, k) > 140) {
+    const auto& g = curve_glv<Fq>();
+    u64 k64[4];
+    memcpy(k64, k, 32);
+    GlvDigits gd;
+    if (g.ok && glv_digits(g, k64, gd)) {
+      memset(d, 0, sizeof(*d));
+      memcpy(d->pos1, gd.pos1, sizeof(gd.pos1));
+      memcpy(d->neg1, gd.neg1, sizeof(gd.neg1));
+      memcpy(d->pos2, gd.pos2, sizeof(gd.pos2));
+      memcpy(d->neg2, gd.neg2, sizeof(gd.neg2));
+      d->nd = gd.nd;
+      static_assert(sizeof(g.beta.v) <= sizeof(d->beta), "beta words");
+      memcpy(d->beta, g.beta.v, sizeof(g.beta.v));  // Montgomery form in the C ABI's radix
+      return true;
+    }
+  }
+  fold_digits_plain(k, d);
+  return false;
 }
 
 

@@ -13,14 +13,13 @@
 
 namespace amsm {
 
-static inline u32 cdiv_(u32 a, u32 b) { return (a + b - 1) / b; }
 void launch_bounds(hipStream_t st, const void* keys_sorted, bool keys16, u32* vals_sorted, MsmGeom g, u32* start,
                    u32* items) {
   if (keys16)
-    hipLaunchKernelGGL((k_bounds<uint16_t>), dim3(cdiv_(g.B, 256)), dim3(256), 0, st, (const uint16_t*)keys_sorted,
+    hipLaunchKernelGGL((k_bounds<uint16_t>), dim3(cdiv(g.B, 256)), dim3(256), 0, st, (const uint16_t*)keys_sorted,
                        vals_sorted, g, start, items);
   else
-    hipLaunchKernelGGL((k_bounds<u32>), dim3(cdiv_(g.B, 256)), dim3(256), 0, st, (const u32*)keys_sorted, vals_sorted,
+    hipLaunchKernelGGL((k_bounds<u32>), dim3(cdiv(g.B, 256)), dim3(256), 0, st, (const u32*)keys_sorted, vals_sorted,
                        g, start, items);
 }
 
@@ -31,7 +30,7 @@ void launch_mirror_flags(hipStream_t st, const u32* flags, u32* host_mirror) {
   hipLaunchKernelGGL(k_mirror_flags, dim3(1), dim3(64), 0, st, flags, host_mirror);
 }
 void launch_vec_fill(hipStream_t st, u32* out, const u32 v[8], u32 n) {
-  hipLaunchKernelGGL(k_vec_fill, dim3(cdiv_(n, 256)), dim3(256), 0, st, out, make_uint4(v[0], v[1], v[2], v[3]),
+  hipLaunchKernelGGL(k_vec_fill, dim3(cdiv(n, 256)), dim3(256), 0, st, out, make_uint4(v[0], v[1], v[2], v[3]),
                      make_uint4(v[4], v[5], v[6], v[7]), n);
 }
 
@@ -74,7 +73,7 @@ static void launch_hist_scan(hipStream_t st, const u32* scalars, int mont, const
                              u32* err) {
   PrepGeom ph = pg;
   ph.SPB = 1024;
-  hipLaunchKernelGGL((k_prep_hist<FR>), dim3(cdiv_(g.n, 1024)), dim3(1024), pg.P * sizeof(u32), st, scalars, mont, g, ph, s.part_total,
+  hipLaunchKernelGGL((k_prep_hist<FR>), dim3(cdiv(g.n, 1024)), dim3(1024), pg.P * sizeof(u32), st, scalars, mont, g, ph, s.part_total,
                      err);
   hipLaunchKernelGGL(k_prep_scan, dim3(1), dim3(1024), 0, st, s.part_total, s.part_start, pg.P, pg.HEAVY, s.hv);
 }
@@ -87,7 +86,7 @@ static void launch_scatter(hipStream_t st, const u32* scalars, int mont, const M
   auto launch = [&](auto kernel, u32 lanes) {
     if (WIDE || lds > 64 * 1024)
       (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PREP_LDS_LIMIT);
-    hipLaunchKernelGGL(kernel, dim3(cdiv_(g.n, pg.SPB)), dim3(lanes), lds, st, scalars, mont, g, pg, s.part_start, s.part_cursor, part,
+    hipLaunchKernelGGL(kernel, dim3(cdiv(g.n, pg.SPB)), dim3(lanes), lds, st, scalars, mont, g, pg, s.part_start, s.part_cursor, part,
                        err);
   };
   if (g.S <= 16u) launch(k_prep_scatter<FR, 16, 1, WIDE>, 512u);
@@ -110,7 +109,7 @@ int launch_prep(hipStream_t st, const u32* scalars, int mont, MsmGeom g, const P
   if (pg.HEAVY != 0xffffffffu)
     hipLaunchKernelGGL(k_prep_heavy_place, dim3(PREP_HEAVY_GRID), dim3(256), lds_heavy, st, s.part_start, b.part, g, pg, s.hv,
                        b.vals_sorted);
-  hipLaunchKernelGGL(k_prep_offsets, dim3(cdiv_(g.B, 256)), dim3(256), (pg.P + 256) * sizeof(u32), st, s.part_start, s.part_items, pg, g,
+  hipLaunchKernelGGL(k_prep_offsets, dim3(cdiv(g.B, 256)), dim3(256), (pg.P + 256) * sizeof(u32), st, s.part_start, s.part_items, pg, g,
                      b.start, b.items, b.item_off, b.vals_sorted);
   return 0;
 }
@@ -148,7 +147,7 @@ int launch_prep_bps_batch(hipStream_t st, const u32* const* scalars, u32 nv, int
   if (lds_scatter > 64 * 1024)
     (void)hipFuncSetAttribute((const void*)k_prep_scatter_batch<FR, 16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)PREP_LDS_LIMIT);
-  hipLaunchKernelGGL((k_prep_scatter_batch<FR, 16, 1>), dim3(cdiv_(g.n, pg.SPB), nv), dim3(512), lds_scatter, st, sc, mont, g, pg,
+  hipLaunchKernelGGL((k_prep_scatter_batch<FR, 16, 1>), dim3(cdiv(g.n, pg.SPB), nv), dim3(512), lds_scatter, st, sc, mont, g, pg,
                      s0.part_start, s0.part_cursor, b.small_stride, b.part, b.part_stride, b.small);
   hipLaunchKernelGGL(k_prep_local_s_batch, dim3(pg.P, nv), dim3(1024), prep_bps_local_lds(pg), st, s0.part_cursor, b.small_stride, b.part,
                      b.part_stride, g, pg, stride, log2_l, b.ents_t, b.ents_stride, (BplGroup*)b.grp, b.grp_stride, b.order, b.order_stride,
@@ -172,9 +171,9 @@ int launch_prep_bpl(hipStream_t st, const u32* scalars, int mont, MsmGeom g, con
 template <class FR>
 void launch_digits(hipStream_t st, const u32* scalars, int mont, MsmGeom g, void* keys, bool keys16, u32* vals, u32* err) {
   if (keys16)
-    hipLaunchKernelGGL((k_digits<FR, uint16_t>), dim3(cdiv_(g.n, 256)), dim3(256), 0, st, scalars, mont, g, (uint16_t*)keys, vals, err);
+    hipLaunchKernelGGL((k_digits<FR, uint16_t>), dim3(cdiv(g.n, 256)), dim3(256), 0, st, scalars, mont, g, (uint16_t*)keys, vals, err);
   else
-    hipLaunchKernelGGL((k_digits<FR, u32>), dim3(cdiv_(g.n, 256)), dim3(256), 0, st, scalars, mont, g, (u32*)keys, vals, err);
+    hipLaunchKernelGGL((k_digits<FR, u32>), dim3(cdiv(g.n, 256)), dim3(256), 0, st, scalars, mont, g, (u32*)keys, vals, err);
 }
 template <class FR>
 void launch_skew_probe(hipStream_t st, const u32* scalars, int mont, u32 n, DigitWalk walk, u32* d_flag, const u32* d_tv_words) {
@@ -182,16 +181,16 @@ void launch_skew_probe(hipStream_t st, const u32* scalars, int mont, u32 n, Digi
 }
 template <class FR>
 void launch_vec_random(hipStream_t st, u32* out, u64 seed, u32 n, int mont) {
-  hipLaunchKernelGGL((k_vec_random<FR>), dim3(cdiv_(n, 256)), dim3(256), 0, st, out, seed, n, mont);
+  hipLaunchKernelGGL((k_vec_random<FR>), dim3(cdiv(n, 256)), dim3(256), 0, st, out, seed, n, mont);
 }
 template <class FR>
 void launch_vec_sample(hipStream_t st, u32* out, const blind::Key& key, u32 curve_id, u32 stream, u64 first, u32 n, int mont, int form) {
   static_assert(VEC_SAMPLE_TILE == 1024u || VEC_SAMPLE_TILE == 4096u, "one of the two instantiated tiles");
   if (form == 0) form = VEC_SAMPLE_TILE == 1024u ? 1 : 2;
   if (form == 1)
-    hipLaunchKernelGGL((k_vec_sample<FR, 1024>), dim3(cdiv_(n, 1024)), dim3(256), 0, st, out, key, curve_id, stream, first, n, mont);
+    hipLaunchKernelGGL((k_vec_sample<FR, 1024>), dim3(cdiv(n, 1024)), dim3(256), 0, st, out, key, curve_id, stream, first, n, mont);
   else
-    hipLaunchKernelGGL((k_vec_sample<FR, 4096>), dim3(cdiv_(n, 4096)), dim3(256), 0, st, out, key, curve_id, stream, first, n, mont);
+    hipLaunchKernelGGL((k_vec_sample<FR, 4096>), dim3(cdiv(n, 4096)), dim3(256), 0, st, out, key, curve_id, stream, first, n, mont);
 }
 template <class FR>
 void launch_vec_hadamard(hipStream_t st, VecGrid vg, const u32* a, const u32* b, u32* out, u32 n) {
@@ -218,7 +217,7 @@ void launch_vec_powers(hipStream_t st, const u32 point[8], u32 n, u32* out) {
   memset(&a, 0, sizeof(a));
   memcpy(a.coeff[0], point, 32);
   a.n = n;
-  hipLaunchKernelGGL((k_vec_powers<FR>), dim3(cdiv_(n, 256)), dim3(256), 0, st, a, out);
+  hipLaunchKernelGGL((k_vec_powers<FR>), dim3(cdiv(n, 256)), dim3(256), 0, st, a, out);
 }
 template <class FR>
 void launch_poly_tile_values(hipStream_t st, const PolyArgs& a, u32 n_polys, u32 max_tiles, bool eval, u32* out) {
@@ -255,7 +254,7 @@ void launch_check_poly_coeffs(hipStream_t st, const u32* xi, u32 k, u32* out) {
   memset(&a, 0, sizeof(a));
   memcpy(a.xi, xi, (size_t)k * 32);
   a.k = k;
-  hipLaunchKernelGGL((k_check_poly_coeffs<FR>), dim3(cdiv_(1u << k, 256)), dim3(256), 0, st, a, out);
+  hipLaunchKernelGGL((k_check_poly_coeffs<FR>), dim3(cdiv(1u << k, 256)), dim3(256), 0, st, a, out);
 }
 template <class FR>
 void launch_ipa_round_scalars(hipStream_t st, const u32* xi, u32 j, u32 log_n, const u32* c, u32* out_l, u32* out_r) {
@@ -263,12 +262,12 @@ void launch_ipa_round_scalars(hipStream_t st, const u32* xi, u32 j, u32 log_n, c
   memset(&a, 0, sizeof(a));
   memcpy(a.xi, xi, (size_t)j * 32);
   a.k = j;
-  hipLaunchKernelGGL((k_ipa_round_scalars<FR>), dim3(cdiv_(1u << log_n, 256)), dim3(256), 0, st, a, j, log_n, c, out_l, out_r);
+  hipLaunchKernelGGL((k_ipa_round_scalars<FR>), dim3(cdiv(1u << log_n, 256)), dim3(256), 0, st, a, j, log_n, c, out_l, out_r);
 }
 template <class FR>
 void launch_spmv(hipStream_t st, const u32* row_ptr, const u32* col, const u32* val, const u32* input, u32 n_input, const u32* witness,
                  u32 n_witness, u32* out, u32 n_rows) {
-  hipLaunchKernelGGL((k_spmv<FR>), dim3(cdiv_(n_rows, 256)), dim3(256), 0, st, row_ptr, col, val, input, n_input, witness, n_witness, out,
+  hipLaunchKernelGGL((k_spmv<FR>), dim3(cdiv(n_rows, 256)), dim3(256), 0, st, row_ptr, col, val, input, n_input, witness, n_witness, out,
                      n_rows);
 }
 template <class FR>

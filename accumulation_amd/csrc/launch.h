@@ -1,6 +1,7 @@
 // Host-callable launchers for the device kernels.  The heavy elliptic-curve kernels are compiled in one
-// translation unit per curve (kern_pallas.hip / kern_bls12_381.hip / kern_vesta.hip / kern_bn254.hip / kern_grumpkin.hip / kern_bls12_377.hip), the scalar-field kernels in
-// kern_fr.hip, so the library builds in parallel; api.hip only sees these declarations.
+// translation unit per curve (kern_pallas.hip / kern_bls12_381.hip / kern_vesta.hip / kern_bn254.hip / kern_grumpkin.hip / kern_bls12_377.hip:
+// each instantiates kern_ec.inc's templates for its base field), the scalar-field kernels in kern_fr.hip, so the library builds in
+// parallel; api.hip only sees these declarations.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,7 @@
 #include <atomic>
 
 #include "blind.h"
+#include "fold_recode.h"
 #include "msm_select.h"
 #include "msm_types.h"
 #include "prep_geom.h"
@@ -29,6 +31,9 @@ struct DeviceOnce {
     done.fetch_or(bit, std::memory_order_release);
   }
 };
+
+// workgroups of b lanes (or lanes of b items) that cover a items
+inline u32 cdiv(u32 a, u32 b) { return (a + b - 1) / b; }
 
 // ---- per-curve (Fq) launchers ------------------------------------------------------------------
 template <class Fq>
@@ -117,16 +122,18 @@ void launch_points_export(hipStream_t st, const u32* src, u32* dst, u32 n);
 // affine in a second kernel with one inversion per few points (batch_affine_pays(n) says when the scratch is used)
 template <class Fq>
 bool batch_affine_pays(u32 n);
+// out[i] = l[i] + x r[i], i < n, with x as the caller recoded it (host_glv.h: fold_digits -- glv is what it returned; the scalar is
+// where the entry point is, api_entry_vec.inc, and so is its recoding: these units only launch).  abi_radix: l, r and out are
+// caller-visible buffers in the C ABI's radix, else key tables in the device's.
 template <class Fq>
-void launch_points_fold(hipStream_t st, const u32* l, const u32* r, u32 n, const u32 x_canon[8], u32 nbits, u32* out,
-                        bool abi_radix, u32* xyzz_scratch);
+void launch_points_fold(hipStream_t st, const u32* l, const u32* r, u32 n, const FoldDigits& d, bool glv, u32* out, bool abi_radix,
+                        u32* xyzz_scratch);
 
 // Fold of a key that carries window multiples (table level w at w * stride points, = 2^(e_w) G with e_w =
-// window_exponent_of(c, W, n_narrow, 0, w); levels 0 .. levels-1 usable): out[i] = table[i] + x * table[n + i], i < n.  False
-// (nothing launched) when x does not fit the usable levels.
+// window_exponent_of(c, W, n_narrow, 0, w)): out[i] = table[i] + x * table[n + i], i < n, by the additions fold_recode.h: fold_tab_ops
+// listed -- which refuses an x that does not fit the usable levels; the caller then takes launch_points_fold.
 template <class Fq>
-bool launch_points_fold_tab(hipStream_t st, const u32* table, u32 stride, u32 c, u32 W, u32 n_narrow, u32 levels, u32 n,
-                            const u32 x_canon[8], u32 nbits, u32* out, u32* xyzz_scratch);
+void launch_points_fold_tab(hipStream_t st, const u32* table, u32 stride, u32 n, const FoldTabOps& ops, u32* out, u32* xyzz_scratch);
 
 // two-valued vectors (vec_kernels.h k_tv_probe, msm_kernels.h k_tv_sum): exact probe into TV_PROBE_WORDS zeroed words, and the
 // sum of the generators with non-zero scalars as `blocks` partial records

@@ -23,6 +23,7 @@
 // and the reduce stage shrinks W-fold.
 #pragma once
 #include "ec.h"
+#include "fold_recode.h"
 #include "msm_select.h"
 #include "msm_types.h"
 #include "rng.h"
@@ -1033,14 +1034,7 @@ __global__ void __launch_bounds__(64) k_precompute_all_levels(const u32* __restr
 // out[i] = l[i] + x * r[i] for affine point vectors (the commitment-key fold `key_l += key_r * xi` of the IPA
 // opening, ark_poly_commit::ipa_pc ext, under src/ipa_pc_as/mod.rs:454): one lane per point, left-to-right
 // double-and-add over the `nbits` low bits of the canonical scalar x, then one inversion back to affine.
-struct FoldDigits {  // the scalar as kernel-argument digit masks (uniform over the grid), recoded once on the host
-  // plain form: x in non-adjacent form (digits +1 / -1 / 0, a third non-zero) in pos1 / neg1, up to 256 digits.
-  // GLV form (host_glv.h): x = k1 + k2 lambda, |k_i| ~ 2^128: NAF(k1) in pos1 / neg1, NAF(k2) in pos2 / neg2 (signs folded
-  // in), and beta (C-ABI Montgomery words) with phi(x, y) = (beta x, y) = [lambda](x, y): half the doublings.
-  u32 pos1[8], neg1[8], pos2[5], neg2[5];
-  u32 nd;         // digit positions to run
-  u32 beta[12];   // W words used
-};
+// The scalar arrives as kernel-argument digit masks, uniform over the grid, recoded once on the host (fold_recode.h: FoldDigits).
 // ABI = true: l, r, out are caller-visible device buffers (C-ABI Montgomery radix in and out); false: key tables
 // (device radix, amsm_bases_fold)
 // XYZZ_OUT: leave the sums unconverted in out (XYZZ records, internal radix) for k_batch_to_affine.
@@ -1098,11 +1092,7 @@ __global__ void __launch_bounds__(256)
 // (one per non-zero NAF digit of every x_w) stay what they were.  A 128-bit challenge over 17-bit windows: 18 doublings + ~45
 // mixed additions instead of 128 + ~43 (the first fold of an IPA opening, which is half of all its fold work, always runs over
 // the original key).  The host flattens the digits into one list of additions, most significant position first; they are
-// uniform over the grid, so the next table row is requested while the current addition runs.
-struct FoldTabOps {
-  uint16_t op[160];  // bits 0..4: digit position, 5..9: level, 15: negate
-  u32 n_ops, nd;
-};
+// uniform over the grid, so the next table row is requested while the current addition runs (fold_recode.h: FoldTabOps).
 template <class Fq, bool XYZZ_OUT>
 __global__ void __launch_bounds__(256)
     k_points_fold_tab(const u32* __restrict__ table, u32 stride, u32 n, FoldTabOps d, u32* __restrict__ out) {

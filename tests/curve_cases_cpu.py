@@ -88,7 +88,11 @@ def test_pack_names_stay_in_the_field_headers(row):
         if f not in ("curves.h", unit_name, "kern_fr.hip", "api_types.h"):  # the table, the two units, the sponge's state tuple
             assert fq[:-1] not in src, f
     unit = open(os.path.join(CSRC, unit_name)).read()
-    assert "AMSM_FQ " + fq in unit and "AMSM_FR " + fr in unit and "AMSM_CURVE_ID %d" % row.curve.curve_id in unit
+    # the unit names the base field; the scalar field and the id it is built for are the curve table's (CurveOf<Fq>)
+    assert "AMSM_EC_LAUNCHERS(" + fq + ")" in unit and fr not in unit
+    table = open(os.path.join(CSRC, "curves.h")).read()
+    assert re.search(r"using Fq = %s;\s+using Fr = %s;\s+static constexpr int id = %s;" % (fq, fr, row.ffi), table)
+    assert re.search(r"struct CurveOf<%s> \{\s+using type = \w+;" % fq, table)
     assert not any(other.packs[0][:-2] in unit for other in cr.ROWS if other is not row) and "Bls12381" not in unit
     assert "AMSM_FR_LAUNCHERS(" + fr + ")" in open(os.path.join(CSRC, "kern_fr.hip")).read()
     from accumulation_amd import build
