@@ -33,6 +33,7 @@
 #include "host_sample.h"
 #include "host_serialize.h"
 #include "launch.h"
+#include "msm_geom.h"
 #include "msm_select.h"
 #include "rng.h"
 

@@ -57,6 +57,10 @@ int amsm_ctx_create(amsm_ctx** out, int curve, int device_id, void* stream) {
   if (!c) return AMSM_E_OOM;
   c->curve = curve;
   c->device = device_id;
+  with_curve(curve, [&](auto cv) {
+    for (int i = 0; i < 8; i++) c->r_mod[i] = decltype(cv)::Fr::mod(i);
+    return AMSM_OK;
+  });
   ctx_bind_bufs(c);
   bool ok = true;
   if (stream) {

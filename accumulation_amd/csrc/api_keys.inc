@@ -133,9 +133,6 @@ int top_window_shift(int c, int W, int n_narrow = 0, unsigned long long* raw_max
   for (int i = 0; i < 8; i++) mod[i] = Fr::mod(i);
   return top_window_shift_of(mod, c, W, n_narrow, raw_max_out);
 }
-inline int top_window_shift_curve(int curve, int c, int W, int n_narrow, unsigned long long* raw_max_out) {
-  return with_curve(curve, [&](auto cv) { return top_window_shift<typename decltype(cv)::Fr>(c, W, n_narrow, raw_max_out); });
-}
 
 template <class Fq, class Fr>
 int bases_finish(amsm_ctx* ctx, amsm_bases* b, unsigned flags) {

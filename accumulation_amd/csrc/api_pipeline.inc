@@ -90,7 +90,6 @@ int reserve_tail(amsm_ctx* ctx, Slot* sl, size_t n_sets, const msel::TailPlan& t
   TRY(ensure_pinned(sl, n_sets * rec + 64));
   return t.ticket ? ensure_red_ticket(ctx, sl, n_sets) : AMSM_OK;
 }
-inline msel::TailPlan tail_plan_of(const MsmGeom& g, Place place) { return msel::tail_plan(g.nb, g.n_sets, g.B, g.E, g.bpl == 1u, place); }
 
 // Every size threshold -- which window a key's table is built for, which pipeline an MSM takes, where a long MSM is cut -- lives in
 // msm_select.h (two tables, plain C++, unit-tested without a GPU: tests/test_pipeline_select_cpu.py).  Here: how the context's
@@ -123,8 +122,25 @@ inline msel::Choice choose_pipeline(const amsm_ctx* ctx, const amsm_bases* bases
 }
 constexpr int BPL_WINDOW = msel::BPL_WINDOW;
 constexpr size_t BPS_MIN_PAIRS = msel::BPS_MIN_PAIRS, BPS_MAX_PAIRS = msel::BPS_MAX_PAIRS;
-inline int windows_for(int c) { return 255 / c + 1; }  // W*c >= 256 (signed digits need one spare bit)
-inline int slots_for(int c) { return windows_for(c); }   // entry slots per scalar
+// ... and to the geometry (msm_geom.h: make_geom, bpl_geom, bps_geom, chunked_geom -- plain C++ too: tests/test_msm_geom_cpu.py)
+inline GeomKey geom_key(const amsm_bases* b) {
+  GeomKey k;
+  k.n = b->n;
+  k.precomp = b->precomp != 0;
+  k.c = b->c;
+  k.W = b->W;
+  k.n_narrow = b->n_narrow;
+  k.top_shift = b->top_shift;
+  return k;
+}
+inline GeomCtx geom_ctx(const amsm_ctx* c) {
+  GeomCtx g;
+  g.window_override = c->window_override;
+  g.wave_slots = c->wave_slots;
+  g.top_sets = c->top_sets;
+  memcpy(g.r_mod, c->r_mod, sizeof(g.r_mod));
+  return g;
+}
 
 template <class Fq>
 constexpr size_t affine_bytes() {
@@ -134,114 +150,8 @@ constexpr size_t affine_bytes() {
 // ---------------------------------------------------------------------------------------------
 // The MSM pipeline.  Leaves n_sets folded XYZZ records in ctx->fold_out.
 // ---------------------------------------------------------------------------------------------
-struct RunInfo {
-  MsmGeom g;
-};
-
-// (api_keys.inc) MsmGeom::top_shift of a walk over the curve's scalar field; *raw_max_out = the largest raw top digit
-inline int top_window_shift_curve(int curve, int c, int W, int n_narrow, unsigned long long* raw_max_out = nullptr);
-// c_plain > 0 (plain keys, the bucket-per-lane pipeline): that window width, its widths adding up to 256 bits (n_narrow), the top
-// window over top_sets = 2, 4 or 8 bucket sets (MsmGeom::top_split)
-int make_geom(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, size_t n, MsmGeom* out, int group_shift = -1,
-              int c_plain = 0, u32 top_sets = 2) {
-  MsmGeom g;
-  memset(&g, 0, sizeof(g));
-  int c, W;
-  if (bases->precomp) {
-    c = bases->c;
-    W = bases->W;
-    g.n_narrow = (u32)bases->n_narrow;
-  } else if (c_plain > 0) {
-    c = c_plain;
-    W = windows_for(c);
-    const u32 nn = narrow_windows_for((u32)c);
-    if (nn == ~0u) return AMSM_E_INVALID_ARG;
-    g.n_narrow = nn;
-    g.top_shift = (u32)top_window_shift_curve(ctx->curve, c, W, (int)nn);  // (precomputed keys: set from the key below)
-    if (top_sets != 2u && top_sets != 4u && top_sets != 8u) return AMSM_E_INVALID_ARG;
-    g.top_split = top_sets - 1u;
-  } else {
-    c = ctx->window_override ? ctx->window_override : msel::key_window(n, false, false);
-    W = windows_for(c);
-  }
-  if (c < 2 || c > 24) return AMSM_E_INVALID_ARG;
-  g.n = (u32)n;
-  g.c = (u32)c;
-  g.W = (u32)W;
-  g.nb = 1u << (c - 1);
-  g.groups = group_shift >= 0 ? 2u : 1u;
-  g.group_shift = group_shift >= 0 ? (u32)group_shift : 0u;
-  g.n_sets = g.groups * (bases->precomp ? 1u : (u32)W + g.top_split);
-  g.B = g.n_sets * g.nb;
-  g.S = (u32)slots_for(c);
-  if ((unsigned long long)n * g.S >= (1ull << 30)) return AMSM_E_UNSUPPORTED;  // entry words carry a 30-bit index
-  g.E = (u32)(n * g.S);
-  g.base_off = (u32)base_off;
-  g.table_stride = (u32)bases->n;
-  g.precomp = (u32)bases->precomp;
-  if (bases->precomp) g.top_shift = (u32)bases->top_shift;
-  if ((unsigned long long)bases->n * (bases->precomp ? W : 1) >= (1ull << 30)) return AMSM_E_UNSUPPORTED;
-  // chunk length of accumulate L0: the grid should be a whole number of rounds of the resident wave
-  // slots (queried from the kernel's occupancy), so that no SIMD idles while a partial last round drains
-  {
-    // <= K0_max entries per lane per round of resident waves (24 measured best on MI355X for batches of MSMs,
-    // tools/ab_pipeline.py: shorter chunks let the other MSMs' prep / tail kernels in sooner, longer ones save partials),
-    // and the grid a WHOLE number of rounds: every resident lane gets `rounds` chunks whose sizes (multiples of 4: the
-    // entries are read 16 bytes at a time) add up to its share of the list -- ra rounds of kb + 4 entries, then
-    // rounds - ra of kb.  One size for all rounds left the last round of a 2^20-pair launch 56 % full.
-    const unsigned long long lanes = (unsigned long long)ctx->wave_slots * 64ull;
-    const unsigned long long kmax = (unsigned long long)tune::K0_MAX;
-    const unsigned long long share = (g.E + lanes - 1) / lanes;  // entries per resident lane
-    const unsigned long long rounds = std::max<unsigned long long>(1, (share + kmax - 1) / kmax);
-    unsigned long long kb = (share / rounds) & ~3ull;
-    if (kb < 12ull) {  // small problems: one size, at least 12 (2^16: 12 -> 0.57 ms per blocking call, 16 -> 0.59)
-      unsigned long long k = (share + rounds - 1) / rounds;
-      g.K0 = ((u32)std::min<unsigned long long>(std::max<unsigned long long>(k, 12ull), kmax) + 3u) & ~3u;
-      g.K0b = g.K0;
-      g.nA = 0xffffff00u;
-    } else {
-      const unsigned long long ra = (share - rounds * kb + 3ull) / 4ull;  // rounds that take 4 more entries (<= rounds)
-      g.K0 = (u32)(kb + 4ull);
-      g.K0b = (u32)kb;
-      g.nA = (u32)(ra * lanes);  // lanes = 64 * wave_slots, wave_slots a multiple of 4: a multiple of 256
-      if (ra >= rounds) {
-        g.K0b = g.K0;
-        g.nA = 0xffffff00u;
-      }
-    }
-  }
-  {
-    unsigned long long t0 = (unsigned long long)g.nA * g.K0;
-    if (t0 >= g.E) {  // phase A covers everything
-      g.nA = (g.E + g.K0 - 1) / g.K0;
-      g.nA = (g.nA + 255u) & ~255u;
-      g.T0 = g.nA * g.K0;  // < E + 256 * K0: fits
-      g.n_chunks = (g.E + g.K0 - 1) / g.K0;
-    } else {
-      g.T0 = (u32)t0;
-      g.n_chunks = g.nA + (g.E - g.T0 + g.K0b - 1) / g.K0b;
-    }
-  }
-  g.K1 = tune::K1;
-  *out = g;  // (red_s / red_threads: the tail's plan, msm_select.h -- launch_tail fills them in)
-  return AMSM_OK;
-}
-
 void stage_mark(amsm_ctx* ctx, Slot* sl, int idx, hipStream_t st) {
   if (ctx->profiling) (void)hipEventRecord(sl->ev[idx], st);
-}
-
-// lanes cooperating on one bucket in accumulate L1 (tree over partials): more lanes = lower latency,
-// but only worth it when buckets have several partials each
-// `hidden`: the tail runs behind the next MSM's accumulation (inside a batch): what counts is its ALU work, not its
-// depth -- one lane per bucket does no butterfly additions at all when there are buckets enough to fill the lanes.
-// Measured (round 2, 2^20 Pallas, stand-alone kernel): 16 lanes per bucket 0.23 ms, 4 lanes 0.107 ms for ~21-26 partials per
-// bucket -- the wide tree only pays when there are too few buckets to occupy the chip with 4 lanes each.
-u32 l1_lanes(const MsmGeom& g, bool hidden) {
-  double avg = (double)g.n_chunks / g.B;
-  if (hidden && g.B >= 16384u) return avg >= 48.0 ? 4u : 1u;
-  if (avg >= 24.0 && g.B * 16ull <= 65536ull) return 16u;
-  return avg >= 3.0 ? 4u : 1u;
 }
 
 // AMSM_DEBUG=1: synchronise after every stage of the pipeline and report it on stderr (finds the faulting kernel)
@@ -272,83 +182,6 @@ int bases_alt(amsm_ctx* ctx, const amsm_bases* b, const amsm_bases** out);
 
 // shortest range of a bucket-per-lane key that takes that pipeline (a quarter of its window: msm_select.h), i.e. that is worth probing
 inline size_t bpl_min_pairs(const amsm_bases*) { return msel::P2(18) + 1; }
-
-// The geometry of an MSM on the bucket-per-lane pipeline (msm_select.h chose it; c_plain = the window of a plain key, 0 for a
-// 20-bit table) -- false when the prep cannot take it (prep_bpl_supported: the caller falls back to the chunked pipeline).
-inline bool bpl_geom_sets(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, size_t n, int group_shift, int c_plain, u32 top_sets,
-                          MsmGeom* out) {
-  MsmGeom g;
-  if (make_geom(ctx, bases, base_off, n, &g, group_shift, c_plain, top_sets) != AMSM_OK) return false;
-  if (g.groups == 1u && g.precomp) {  // window-relative indices (MsmGeom::idx_rel_bits)
-    u32 b = 1;
-    while ((1ull << b) < n) b++;
-    unsigned long long abs_max = (unsigned long long)g.base_off + n - 1ull + (unsigned long long)(g.W - 1u) * g.table_stride;
-    unsigned long long rel_max = ((unsigned long long)(g.W - 1u) << b) | ((1ull << b) - 1ull);
-    if (rel_max < abs_max) g.idx_rel_bits = b;
-  }
-  g.bpl = 1;
-  {
-    // entries the fullest 1024-bucket partition expects: a window's n digits spread over the bucket range -- the top window's
-    // over the part of it its raw values reach (r / 2^256 of the range: no sign to fold, and only as far as top_shift spreads it)
-    unsigned long long raw_max = 0;
-    (void)top_window_shift_curve(ctx->curve, (int)g.c, (int)g.W, (int)g.n_narrow, &raw_max);
-    const unsigned long long top_reach = top_window_reach(g.nb, raw_max, g.top_shift, g.n_narrow);
-    if (g.precomp) {  // W windows share one bucket set
-      const unsigned long long per_win = ((unsigned long long)n * 1024ull + g.nb - 1) / g.nb;  // a regular window's, per partition
-      const unsigned long long per_top = ((unsigned long long)n * 1024ull + top_reach - 1) / top_reach;
-      g.part_max = (u32)std::min<unsigned long long>(0xffffffffull, (g.W - 1ull) * per_win + per_top);
-      if (g.groups > 1u) g.part_max = (g.part_max + 1u) / 2u;  // (a group sees half the scalars)
-    } else {
-      // (a plain key's top window is split over T sets, MsmGeom::top_split; what is sized for is TWICE the uniform load of one:
-      // msm_select.h: plain_part_max)
-      g.part_max = (u32)std::min<unsigned long long>(0xffffffffull, msel::plain_part_max(n, g.nb, top_reach, top_sets, g.groups));
-    }
-  }
-  if (!prep_bpl_supported(g)) return false;
-  *out = g;
-  return true;
-}
-inline bool bpl_geom(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, size_t n, int group_shift, int c_plain, MsmGeom* out) {
-  if (c_plain <= 0 || bases->precomp) return bpl_geom_sets(ctx, bases, base_off, n, group_shift, c_plain, 2, out);
-  // a plain key: the sets of its top window (msm_select.h: plain_top_sets) -- AMSM_TOP_SETS = 4 / 8 where the prep takes that geometry,
-  // else the smallest count that fits its stage (AMSM_TOP_SETS=2: two or none)
-  if (ctx->top_sets > 2 && bpl_geom_sets(ctx, bases, base_off, n, group_shift, c_plain, (u32)ctx->top_sets, out)) return true;
-  const int W = windows_for(c_plain);
-  const u32 nn = narrow_windows_for((u32)c_plain);
-  if (nn == ~0u) return false;
-  unsigned long long raw_max = 0;
-  const int shift = top_window_shift_curve(ctx->curve, c_plain, W, (int)nn, &raw_max);
-  const u32 nb = 1u << (c_plain - 1);
-  const u32 T = msel::plain_top_sets(n, nb, top_window_reach(nb, raw_max, (u32)shift, nn), (u32)W, group_shift >= 0 ? 2u : 1u,
-                                     msel::BPL_STAGE_CAP, msel::plain_top_sets_cap(ctx->top_sets));
-  return T != 0u && bpl_geom_sets(ctx, bases, base_off, n, group_shift, c_plain, T, out);
-}
-
-// The geometry of an MSM on the bucket-split pipeline (precomputed key, one or two bucket sets, 2^16 .. 2^17 pairs: msm_select.h) --
-// false when no lane count fits (prep_bps_choose).  Where it was measured to win (same-process A/B against the chunked pipeline,
-// Pallas, uniform scalars): 2^16 pairs -- a blocking call 0.400 -> 0.354 ms, batches 216 -> 250 M pairs/s -- and 2^17 (357 -> 383);
-// below 2^16 the parts get too short (the padded blocks overflow their stride), from 2^18 up the chunked pipeline's longer runs win.
-inline bool bps_geom(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, size_t n, int group_shift, MsmGeom* out) {
-  MsmGeom g;
-  if (make_geom(ctx, bases, base_off, n, &g, group_shift) != AMSM_OK) return false;
-  if (g.groups == 1u) {  // window-relative indices, as in the chunked plan
-    u32 b = 1;
-    while ((1ull << b) < n) b++;
-    unsigned long long abs_max = (unsigned long long)g.base_off + n - 1ull + (unsigned long long)(g.W - 1u) * g.table_stride;
-    unsigned long long rel_max = ((unsigned long long)(g.W - 1u) << b) | ((1ull << b) - 1ull);
-    if (rel_max < abs_max) g.idx_rel_bits = b;
-  }
-  int l = prep_bps_choose(g);
-  if (l < 0 && g.idx_rel_bits) {
-    g.idx_rel_bits = 0;
-    l = prep_bps_choose(g);
-  }
-  if (l < 0) return false;
-  g.bpl = 2;
-  g.bps_log2_l = (u32)l;
-  *out = g;
-  return true;
-}
 
 // one MSM over generators [off, off + n) of `key` (n already clamped to the key), as the single-MSM entry points describe it
 inline MsmJob single_job(const amsm_bases* key, size_t off, const void* scalars, size_t n, int mont, int group_shift = -1) {
@@ -431,6 +264,7 @@ int msm_plan(amsm_ctx* ctx, Slot* sl, const MsmJob& job, bool* short_prep_out, c
     return direct_plan<Fq>(ctx, sl, &job, 1, &dp);
   }
   const msel::Choice ch = choose_pipeline(ctx, bases, n, group_shift, job.force_chunked);
+  const GeomCtx gc = geom_ctx(ctx);
   auto common = [&]() -> int {  // what every sorted pipeline needs behind its accumulation: the buckets, and the tail wherever the
     TRY(ensure(sl->buckets, (size_t)g.B * rec));  // MSM will stand in its call (msm_enqueue knows, callers that reserve first do not)
     return reserve_tail<Fq>(ctx, sl, g.n_sets, msel::tail_plan_any_place(g.nb, g.n_sets, g.B, g.E, g.bpl == 1u));
@@ -443,7 +277,7 @@ int msm_plan(amsm_ctx* ctx, Slot* sl, const MsmJob& job, bool* short_prep_out, c
     TRY(common());
     return ensure(sl->prep_small, nd.prep_small);
   };
-  if (ch.pipeline == msel::BUCKET_PER_LANE && bpl_geom(ctx, bases, base_off, n, group_shift, ch.plain_window, &g)) {
+  if (ch.pipeline == msel::BUCKET_PER_LANE && bpl_geom(gc, geom_key(bases), base_off, n, group_shift, ch.plain_window, &g)) {
     sl->geom = g;
     if (eff) *eff = bases;
     TRY(prep_reserve(prep_bpl_needs(g)));
@@ -453,14 +287,15 @@ int msm_plan(amsm_ctx* ctx, Slot* sl, const MsmJob& job, bool* short_prep_out, c
   // everything a 20-bit key's table does not take runs over its 17-bit twin (built on first use)
   if (bases->bpl) TRY(bases_alt<Fq>(ctx, bases, &bases));
   if (eff) *eff = bases;
-  if (ch.pipeline == msel::BUCKET_SPLIT && bps_geom(ctx, bases, base_off, n, group_shift, &g)) {
+  if (ch.pipeline == msel::BUCKET_SPLIT && bps_geom(gc, geom_key(bases), base_off, n, group_shift, &g)) {
     sl->geom = g;
     TRY(prep_reserve(prep_bps_needs(g)));
     *short_prep_out = true;
     return AMSM_OK;
   }
-  // chunked pipeline
-  TRY(make_geom(ctx, bases, base_off, n, &g, group_shift));
+  // chunked pipeline: window-relative indices where the short prep chain (prep_kernels.h) takes them, and that chain wherever its word
+  // layout takes the geometry; else (windows below 8 bits: tiny plain keys, window overrides) the rocPRIM sort
+  TRY(chunked_geom(gc, geom_key(bases), base_off, n, group_shift, &g, short_prep_out));
   sl->geom = g;
   const u32 max_items = g.n_chunks + g.B + 1;
   TRY(ensure(sl->vals_a, (size_t)g.E * 4 + 64));
@@ -473,32 +308,14 @@ int msm_plan(amsm_ctx* ctx, Slot* sl, const MsmJob& job, bool* short_prep_out, c
   TRY(ensure(sl->heavy, (size_t)(g.B + 1) * 4));
   // at most max_items / K1 buckets can hold more than K1 partials each
   TRY(ensure(sl->heavy_scratch, ((size_t)max_items / std::max<u32>(g.K1, 1u) + 2) * accum_l2_slices<Fq>() * rec));
-  // An MSM over a window of a longer precomputed key: the interchange word of the partition pass carries the index relative
-  // to the window (MsmGeom::idx_rel_bits), so that its bucket-id bits -- the number of partitions -- follow the MSM's size,
-  // not the key's
-  if (g.precomp && g.groups == 1u) {
-    u32 b = 1;
-    while ((1ull << b) < n) b++;
-    unsigned long long abs_max = (unsigned long long)g.base_off + n - 1ull + (unsigned long long)(g.W - 1u) * g.table_stride;
-    unsigned long long rel_max = ((unsigned long long)(g.W - 1u) << b) | ((1ull << b) - 1ull);
-    if (rel_max < abs_max) {
-      MsmGeom g2 = g;
-      g2.idx_rel_bits = b;
-      if (prep_supported(g2)) sl->geom = g = g2;
-    }
-  }
-  // the short prep chain (prep_kernels.h) where its word layout takes the geometry; else (windows below 8 bits: tiny plain keys,
-  // window overrides) the rocPRIM sort.  16 flag words (scalar-range error, heavy-bucket count) lead the chain's block of small
-  // arrays, so that ONE fill clears both
-  const bool short_prep = prep_supported(g);
-  if (short_prep) {
+  // 16 flag words (scalar-range error, heavy-bucket count) lead the short chain's block of small arrays, so that ONE fill clears both
+  if (*short_prep_out) {
     TRY(ensure(sl->prep_small, prep_small_bytes(g)));
   } else {  // only the rocPRIM chain sorts (key, value) pairs
     TRY(ensure(sl->misc, 64));
     TRY(ensure(sl->keys_a, (size_t)g.E * 4));
     TRY(ensure(sl->keys_b, (size_t)g.E * 4));
   }
-  *short_prep_out = short_prep;
   return AMSM_OK;
 }
 
@@ -754,23 +571,6 @@ template <class Fq>
 size_t bps_slot_bytes(const MsmGeom& g) {
   const PrepNeeds nd = prep_bps_needs(g);
   return nd.vals_a + nd.vals_b + nd.bpl_grp + nd.bpl_order + (size_t)g.B * xyzz_bytes<Fq>() + nd.prep_small;
-}
-// The unit as its tail sees it: nv * n_sets bucket sets in one table, one result ("group") per MSM -- what msm_collect's horner hands out
-inline MsmGeom bps_unit_geom(const MsmGeom& g, u32 nv) {
-  MsmGeom u = g;
-  u.n_sets = g.n_sets * nv;
-  u.groups = nv;
-  u.B = g.B * nv;
-  return u;
-}
-inline msel::TailPlan bps_unit_tail(const MsmGeom& g, u32 nv, Place place) {
-  return msel::tail_plan(g.nb, g.n_sets * nv, g.B * nv, g.E * nv, false, place);
-}
-// Does the bucket-split geometry of n pairs at `off` of `bases` (the key the MSMs run over) take the batched kernels?  One bucket set
-// per MSM, and at most 16 entry slots per scalar (windows of 16 bits and more: what every key long enough for 2^16 pairs has --
-// k_prep_scatter_batch is built for that width only)
-inline bool bps_unit_geom_ok(amsm_ctx* ctx, const amsm_bases* bases, size_t off, size_t n, MsmGeom* g) {
-  return bps_geom(ctx, bases, off, n, -1, g) && g->n_sets == 1u && g->S <= 16u;
 }
 // What msm_multi_xyzz found when it formed the unit (bps_unit_geom_ok, once per run of jobs): ONE MSM's geometry, shared by all of the
 // unit's MSMs (skip_ones set), and the key they run over (a 20-bit key's twin)
@@ -1258,7 +1058,7 @@ int msm_multi_xyzz(amsm_ctx* ctx, const std::vector<MsmJob>& jobs, std::vector<h
       // bps_geom must take the run's geometry, over the key the MSMs run over (a 20-bit key's twin; one that cannot be had is the
       // single path's to report)
       ugeom[i].eff = j.key;
-      if ((!j.key->bpl || bases_alt<Fq>(ctx, j.key, &ugeom[i].eff) == AMSM_OK) && bps_unit_geom_ok(ctx, ugeom[i].eff, j.off, j.n, &ugeom[i].g)) {
+      if ((!j.key->bpl || bases_alt<Fq>(ctx, j.key, &ugeom[i].eff) == AMSM_OK) && bps_unit_geom_ok(geom_ctx(ctx), geom_key(ugeom[i].eff), j.off, j.n, &ugeom[i].g)) {
         ugeom[i].g.skip_ones = j.skip_ones ? 1u : 0u;
         b.geom_ok = true;
         b.slot_bytes = bps_slot_bytes<Fq>(ugeom[i].g);
@@ -1609,7 +1409,7 @@ int msm_multi_split_impl(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, std::ve
       MsmGeom g;
       while (first_job + n_sh < jobs.size() &&
              choose_pipeline(ctx, key, jobs[first_job + n_sh].n, -1, false).pipeline == msel::BUCKET_PER_LANE &&
-             bpl_geom(ctx, key, jobs[first_job + n_sh].off, jobs[first_job + n_sh].n, -1, 0, &g) && g.n_sets == 1u)
+             bpl_geom(geom_ctx(ctx), geom_key(key), jobs[first_job + n_sh].off, jobs[first_job + n_sh].n, -1, 0, &g) && g.n_sets == 1u)
         n_sh++;
       if (n_sh >= 2) TRY(arm_shared_set<Fq>(ctx, jobs, first_job, n_sh, g.B));
     }
@@ -1793,7 +1593,7 @@ int msm_multi_host_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const 
     const bool halve = !no_halves && !os && k == 1 && key == bases && !split && !force_chunked && host_halves_apply(ctx, key, len) &&
                        choose_pipeline(ctx, key, h1, -1, false).pipeline == msel::BUCKET_PER_LANE &&
                        choose_pipeline(ctx, key, len - h1, -1, false).pipeline == msel::BUCKET_PER_LANE &&
-                       bpl_geom(ctx, key, vecs[v].off, h1, -1, 0, &hg) && hg.n_sets == 1u;
+                       bpl_geom(geom_ctx(ctx), geom_key(key), vecs[v].off, h1, -1, 0, &hg) && hg.n_sets == 1u;
     if (halve) step = h1;
     if (len) {  // (an empty slice is no job here)
       MsmJob vec = vecs[v];

@@ -29,10 +29,9 @@ struct MemGate {
 
 }  // namespace
 
-// Measured constants of the launcher (environment knobs until round 5: each was A/B'd, the numbers are in DESIGN.md / profiles/)
+// Measured constants of the launcher (environment knobs until round 5: each was A/B'd, the numbers are in DESIGN.md / profiles/;
+// K0_MAX and K1 stand with the geometry they size, msm_geom.h)
 namespace tune {
-constexpr int K0_MAX = 32;                 // largest chunk of accumulate L0 (24 -> 805, 32 -> 811-816 M pairs/s in 2^20 batches)
-constexpr amsm::u32 K1 = 1024;             // buckets with more partials than this go to the workgroup-per-bucket path (extreme skew)
 constexpr size_t ONESHOT_RANGE = (size_t)1 << 19;  // amsm_msm_oneshot: pairs per range (upload of range j + 1 beside the MSM of range j)
 }  // namespace tune
 
@@ -214,6 +213,7 @@ struct amsm_ctx {
   int cu_count = 256;
   unsigned vec_grid_max = 0;  // amsm_ctx_set_vec_grid_max: upper bound on the workgroups of every grid-stride Fr kernel (0: none; tests)
   int wave_slots = 4096;  // resident accumulate-L0 waves: CUs x resident 256-lane blocks per CU x 4
+  amsm::u32 r_mod[8] = {};  // the modulus of the curve's scalar field, set at creation (msm_geom.h: GeomCtx)
   // ---- the documented switches (include/amsm.h "Environment"; msm_select.h: Switches) -- everything else that used to be an
   // environment knob is a measured constant now (namespace tune below; the A/Bs are in profiles/ and DESIGN.md) ----
   bool bpl = true;        // AMSM_BPL=0: no 20-bit tables, no bucket-per-lane pipeline (17-bit windows + the chunked pipeline)

@@ -42,8 +42,8 @@ constexpr int HP_MAX_INPUTS = 8;  // max inputs+accumulators of one hp_as t-vect
 struct MsmGeom {
   u32 n;             // pairs in this call
   u32 c;             // window bits (2..24)
-  u32 W;             // windows = floor(255 / c) + 1
-  u32 S;             // entry slots per scalar (= W)
+  u32 W;             // windows (windows_for below)
+  u32 S;             // entry slots per scalar (slots_for below)
   u32 nb;            // buckets per set = 2^(c-1)
   u32 n_sets;        // bucket sets = groups * (1 when precomputed, else W)
   u32 groups;        // 1, or 2: scalar i adds into the sum of group (i >> group_shift) & 1 (two MSMs in one pass)
@@ -126,9 +126,12 @@ AMSM_GEOM_FN DigitWalk digit_walk_of(const MsmGeom& g) {
   d.skip_ones = g.skip_ones;
   return d;
 }
+// windows of a width-c walk: W c >= 256 (signed digits need one spare bit); entry slots per scalar
+AMSM_GEOM_FN int windows_for(int c) { return 255 / c + 1; }
+AMSM_GEOM_FN int slots_for(int c) { return windows_for(c); }
 // narrow windows a width-c walk over 256 bits needs (0 when the widths divide evenly; ~0u when c - 1 is not narrow enough)
 AMSM_GEOM_FN u32 narrow_windows_for(u32 c) {
-  const u32 W = 255u / c + 1u, nn = W * c - 256u;
+  const u32 W = (u32)windows_for((int)c), nn = W * c - 256u;
   return nn < W ? nn : ~0u;
 }
 // MsmGeom::top_shift for window width c over the scalar field of modulus `mod` (8 little-endian words, odd): the largest s for which
