@@ -34,6 +34,7 @@
 #include "host_serialize.h"
 #include "launch.h"
 #include "msm_geom.h"
+#include "msm_jobs.h"
 #include "msm_select.h"
 #include "rng.h"
 

@@ -142,6 +142,29 @@ inline GeomCtx geom_ctx(const amsm_ctx* c) {
   return g;
 }
 
+// ... and to the job list (msm_jobs.h: plan_ranges, plan_units, the probes' rules -- plain C++ as well: tests/test_msm_jobs_cpu.py)
+inline mjobs::PlanCtx plan_ctx(const amsm_ctx* c) {
+  mjobs::PlanCtx p;
+  p.sw = switches_of(c);
+  p.geom = geom_ctx(c);
+  p.share_buckets = c->share_buckets;
+  p.host_halves = c->host_halves;
+  p.bpl_probe = c->bpl_probe;
+  return p;
+}
+inline mjobs::JobKey job_key(const amsm_bases* b, const amsm_bases* twin = nullptr) {  // twin: the 17-bit twin of a 20-bit key, once built
+  mjobs::JobKey k;
+  k.id = b;
+  k.desc = key_desc(b);
+  k.geom = geom_key(b);
+  k.has_twin = twin != nullptr;
+  if (twin) {
+    k.twin_desc = key_desc(twin);
+    k.twin_geom = geom_key(twin);
+  }
+  return k;
+}
+
 template <class Fq>
 constexpr size_t affine_bytes() {
   return 2 * Fq::L * 4;
@@ -179,9 +202,6 @@ int prep_fork(amsm_ctx* ctx) {
 
 template <class Fq>
 int bases_alt(amsm_ctx* ctx, const amsm_bases* b, const amsm_bases** out);
-
-// shortest range of a bucket-per-lane key that takes that pipeline (a quarter of its window: msm_select.h), i.e. that is worth probing
-inline size_t bpl_min_pairs(const amsm_bases*) { return msel::P2(18) + 1; }
 
 // one MSM over generators [off, off + n) of `key` (n already clamped to the key), as the single-MSM entry points describe it
 inline MsmJob single_job(const amsm_bases* key, size_t off, const void* scalars, size_t n, int mont, int group_shift = -1) {
@@ -565,14 +585,7 @@ int msm_enqueue(amsm_ctx* ctx, Slot* sl, const MsmJob& job, Place place) {
 }
 
 // ---- a unit of bucket-split MSMs: one launch per pipeline stage (msm_select.h: batch_units; DESIGN.md 4.2h) ----
-// What ONE bucket-split MSM of geometry g takes of a slot: what msm_plan reserves for its prep (prep_geom.h: prep_bps_needs) and its
-// buckets.  batch_units keeps a unit's V of them below msel::BPS_BATCH_MAX_BYTES.
-template <class Fq>
-size_t bps_slot_bytes(const MsmGeom& g) {
-  const PrepNeeds nd = prep_bps_needs(g);
-  return nd.vals_a + nd.vals_b + nd.bpl_grp + nd.bpl_order + (size_t)g.B * xyzz_bytes<Fq>() + nd.prep_small;
-}
-// What msm_multi_xyzz found when it formed the unit (bps_unit_geom_ok, once per run of jobs): ONE MSM's geometry, shared by all of the
+// What msm_multi_xyzz found when it formed the unit (msm_jobs.h: plan_units, once per run of jobs): ONE MSM's geometry, shared by all of the
 // unit's MSMs (skip_ones set), and the key they run over (a 20-bit key's twin)
 struct BpsUnitGeom {
   MsmGeom g = {};
@@ -839,14 +852,8 @@ int arm_shared_set(amsm_ctx* ctx, std::vector<MsmJob>& jobs, size_t first, size_
 
 template <class Fq, class Fr>
 int msm_multi_split_xyzz(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, std::vector<host::HXYZZ<Fq>>* out);
-// Large MSMs run as ranges of the key (msm_select.h: range_of)
-inline size_t split_chunk(const amsm_ctx* ctx, const amsm_bases* bases) {
-  const size_t r = msel::range_of(key_desc(bases), ~(size_t)0 >> 1, switches_of(ctx));
-  return r ? r : ((size_t)1 << 20);
-}
-inline bool split_needed(const amsm_ctx* ctx, const amsm_bases* bases, size_t n) {
-  return msel::range_of(key_desc(bases), n, switches_of(ctx)) != 0;
-}
+// Large MSMs run as ranges of the key (msm_jobs.h)
+inline bool split_needed(const amsm_ctx* ctx, const amsm_bases* bases, size_t n) { return mjobs::split_needed(switches_of(ctx), key_desc(bases), n); }
 
 // Which of the k device vectors would overflow the bucket-per-lane prep (vec_kernels.h: k_skew_probe)?  One tiny launch per
 // candidate on the caller's stream (behind the kernels that produce the vectors), one copy, one synchronisation per CALL.
@@ -854,31 +861,10 @@ struct SkewProbe {  // launched, not yet read back
   std::vector<size_t> cand, first;
   size_t k = 0;
 };
-// the walk a key's MSMs use (launch.h: DigitWalk), as the skew probes need it
-inline DigitWalk key_walk(const amsm_bases* b) {
-  DigitWalk d;
-  memset(&d, 0, sizeof(d));
-  d.c = (u32)b->c;
-  d.W = d.c ? (u32)windows_for((int)d.c) : 0u;  // (a plain key has no window of its own: c = 0, never walked)
-  if (b->precomp) {
-    d.W = (u32)b->W;
-    d.n_narrow = (u32)b->n_narrow;
-  }
-  return d;
-}
-// Identical vectors (a prover commits to the same accumulator vector more than once; bench.py cycles four) are probed once:
-// first[j] = the first i <= j with the scalars and the length of vecs[cand[j]] (an index into cand).  The offset into the key is
-// deliberately not compared: what the probes say depends on the scalars, their number and the key alone.
+// Identical vectors are probed once (msm_jobs.h: first_identical): first[j] is an index into cand
 inline std::vector<size_t> first_identical(const std::vector<MsmJob>& vecs, const std::vector<size_t>& cand) {
   std::vector<size_t> first(cand.size());
-  for (size_t j = 0; j < cand.size(); j++) {
-    first[j] = j;
-    for (size_t i = 0; i < j; i++)
-      if (vecs[cand[i]].scalars == vecs[cand[j]].scalars && vecs[cand[i]].n == vecs[cand[j]].n) {
-        first[j] = first[i];
-        break;
-      }
-  }
+  mjobs::first_identical(cand.size(), [&](size_t j) { return mjobs::VecRef{vecs[cand[j]].scalars, vecs[cand[j]].n}; }, first.data());
   return first;
 }
 template <class Fr>
@@ -922,49 +908,24 @@ int bpl_probe_device(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, std::vector
 // Which skew probe (if any) the pipelines behind msm_multi_split_impl want for these vectors over `bases`: 0 none, else the window
 // width / the shortest vector probed.  (msm_multi_split_xyzz launches it together with the two-valued probe: one synchronisation for both.)
 inline int skew_probe_params(const amsm_ctx* ctx, const amsm_bases* bases, const std::vector<MsmJob>& vecs, size_t* min_len, DigitWalk* walk) {
-  if (!ctx->bpl_probe || !bases->precomp) return 0;
-  *walk = key_walk(bases);
+  const mjobs::PlanCtx pc = plan_ctx(ctx);
+  const msel::KeyDesc kd = key_desc(bases);
   bool want = false;
-  for (const MsmJob& v : vecs) want = want || (v.n && msel::wants_skew_probe(key_desc(bases), v.n, switches_of(ctx)));
+  for (const MsmJob& v : vecs) want = want || mjobs::probe_wanted(pc, kd, v.n);
   if (!want) return 0;
-  *min_len = bases->bpl ? bpl_min_pairs(bases) : BPS_MIN_PAIRS;
+  *walk = mjobs::key_walk(geom_key(bases));
+  *min_len = mjobs::probe_min_len(kd);
   return bases->c;
 }
-// the same test on a host slice (the digit walk of vec_kernels.h: digit_step, on the host)
+// the same test on a host slice (msm_jobs.h: skew_probe_host, over the samples in canonical form)
 template <class Fr>
 bool bpl_probe_host(const uint64_t* scalars, size_t n, int mont, DigitWalk dw, size_t min_len) {
-  constexpr u32 SAMPLES = 1024, BINS = 2048, LIMIT = 24;
-  if (n < min_len) return false;
-  std::vector<std::array<u32, 8>> smp(SAMPLES);
-  for (u32 t = 0; t < SAMPLES; t++) {
+  return mjobs::skew_probe_host(n, min_len, dw, [&](size_t i, u32* out) {
     host::HFe<Fr> s;
-    memcpy(s.v, scalars + 4 * (size_t)(((unsigned long long)t * n) / SAMPLES), 32);
+    memcpy(s.v, scalars + 4 * i, 32);
     if (mont) s = host::h_from_mont<Fr>(s);
-    memcpy(smp[t].data(), s.v, 32);
-  }
-  std::vector<u32> carry(SAMPLES, 0), bins(BINS);
-  for (u32 w = 0; w < dw.W; w++) {
-    std::fill(bins.begin(), bins.end(), 0u);
-    for (u32 t = 0; t < SAMPLES; t++) {
-      u32* v = smp[t].data();
-      u32 d;
-      {
-        const u32 cw = window_bits_of(dw.c, dw.W, dw.n_narrow, w);
-        const u32 mask = (1u << cw) - 1u, half = 1u << (cw - 1);
-        u32 raw = (v[0] & mask) + carry[t];
-        for (int k = 0; k < 7; k++) v[k] = (v[k] >> cw) | (v[k + 1] << (32 - cw));
-        v[7] >>= cw;
-        carry[t] = 0;
-        d = raw;
-        if (raw > half && w + 1 < dw.W) {
-          d = (1u << cw) - raw;
-          carry[t] = 1;
-        }
-      }
-      if (d != 0 && ++bins[(d * 2654435761u) >> 21] >= LIMIT) return true;
-    }
-  }
-  return false;
+    memcpy(out, s.v, 32);
+  });
 }
 
 // The callers' k vectors over windows of one key -- vector v: generators [offs[v], offs[v] + ns[v]) and the scalars at scalars[v] -- as
@@ -989,17 +950,34 @@ template <class Fq>
 void add_by_owner(const std::vector<MsmJob>& jobs, const std::vector<host::HXYZZ<Fq>>& part, std::vector<host::HXYZZ<Fq>>* out) {
   for (size_t j = 0; j < jobs.size(); j++) (*out)[jobs[j].owner] = host::hx_add<Fq>((*out)[jobs[j].owner], part[j]);
 }
-// Vector `vec` in ranges of `step` pairs, appended to *jobs (an empty vector: one empty job); every range inherits the vector's fields
-inline void cut_into_ranges(const MsmJob& vec, size_t step, std::vector<MsmJob>* jobs) {
-  size_t lo = 0;
-  do {
-    jobs->push_back(vec);
-    MsmJob& r = jobs->back();
-    r.off = vec.off + lo;
-    r.n = std::min(step, vec.n - lo);
-    r.scalars = (const char*)vec.scalars + lo * 32;
-    lo += step;
-  } while (lo < vec.n);
+// The job list of a call (msm_jobs.h: plan_ranges says how its vectors are cut, which ranges share a bucket set, which run over the
+// twin) as MsmJobs: the twin is built first where a skewed vector needs it, every range inherits its vector's fields, every shared
+// set gets its buffers (arm_shared_set).  skew: the probes' verdict per vector (null: none skewed)
+template <class Fq>
+int plan_jobs(amsm_ctx* ctx, const amsm_bases* bases, const std::vector<MsmJob>& vecs, const uint8_t* skew, const mjobs::Form& form,
+              std::vector<MsmJob>* jobs) {
+  std::vector<mjobs::PlanVec> pv(vecs.size());
+  for (size_t v = 0; v < vecs.size(); v++) pv[v] = mjobs::PlanVec{vecs[v].off, vecs[v].n, skew && skew[v]};
+  const amsm_bases* alt = nullptr;
+  if (mjobs::needs_twin(job_key(bases), pv.data(), pv.size())) TRY(bases_alt<Fq>(ctx, bases, &alt));
+  std::vector<mjobs::Range> plan;
+  mjobs::plan_ranges(plan_ctx(ctx), job_key(bases, alt), pv.data(), pv.size(), form, &plan);
+  jobs->clear();
+  jobs->reserve(plan.size());
+  size_t set_first = 0;
+  for (const mjobs::Range& r : plan) {
+    jobs->push_back(vecs[r.vec]);
+    MsmJob& j = jobs->back();
+    j.owner = r.vec;  // the vector's place in `vecs`
+    j.key = r.over_twin ? alt : bases;
+    j.force_chunked = r.force_chunked;
+    j.off += r.lo;
+    j.n = r.n;
+    j.scalars = (const char*)j.scalars + r.lo * 32;
+    if (r.first) set_first = jobs->size() - 1;
+    if (r.last) TRY(arm_shared_set<Fq>(ctx, *jobs, set_first, jobs->size() - set_first, r.set_buckets));
+  }
+  return AMSM_OK;
 }
 
 // The jobs' MSMs through the slot ring; (*part)[j] = job j's result (the identity for an empty job, and for every range of a shared
@@ -1033,38 +1011,30 @@ int msm_multi_xyzz(amsm_ctx* ctx, const std::vector<MsmJob>& jobs, std::vector<h
   std::vector<msel::Unit> units(live.size());
   size_t n_units = live.size();
   std::vector<MsmJob> ujobs;  // the live jobs in order (a unit's are adjacent in memory)
-  std::vector<BpsUnitGeom> ugeom;  // per live job: the geometry its unit would run with (found once per run, handed to the plan)
+  std::vector<mjobs::UnitGeom> ugeom;  // per live job: the geometry its unit would run with (msm_jobs.h: plan_units)
+  std::vector<mjobs::UnitJob> uj;
+  std::vector<mjobs::JobKey> keys;          // the keys the live jobs name (one; or a 20-bit key and, for its skewed vectors, the twin)
+  std::vector<const amsm_bases*> twin;      // ... and their twins, where plan_units will look at a job over a 20-bit key
   if (live.size() >= 2 && ctx->bps_batch >= 2) {
-    std::vector<msel::BatchJob> bj(live.size());
+    const mjobs::PlanCtx pc = plan_ctx(ctx);
     ugeom.resize(live.size());
-    const msel::Switches sw = switches_of(ctx);
-    size_t last_eval = live.size();  // the last job whose geometry was looked at (none yet)
+    uj.resize(live.size());
     for (size_t i = 0; i < live.size(); i++) {
       const MsmJob& j = jobs[live[i]];
-      msel::BatchJob& b = bj[i];
-      b = msel::BatchJob{j.key, key_desc(j.key), j.off, j.n, j.mont, j.group_shift, j.share.buf >= 0, j.force_chunked, j.skip_ones, false, 0};
-      if (j.group_shift >= 0 || j.share.buf >= 0 || j.force_chunked || choose_pipeline(ctx, j.key, j.n, -1, false).pipeline != msel::BUCKET_SPLIT)
-        continue;
-      // one geometry per run -- taken from a neighbour only if that neighbour's geometry was itself looked at (a job skipped above,
-      // a skewed vector for instance, says nothing about the jobs behind it)
-      if (last_eval + 1 == i && msel::batch_same_run(bj[last_eval], b)) {
-        b.geom_ok = bj[last_eval].geom_ok;
-        b.slot_bytes = bj[last_eval].slot_bytes;
-        ugeom[i] = ugeom[last_eval];
-        last_eval = i;
-        continue;
+      size_t ki = 0;
+      while (ki < keys.size() && keys[ki].id != j.key) ki++;
+      if (ki == keys.size()) {
+        keys.push_back(job_key(j.key));
+        twin.push_back(nullptr);
       }
-      last_eval = i;
-      // bps_geom must take the run's geometry, over the key the MSMs run over (a 20-bit key's twin; one that cannot be had is the
-      // single path's to report)
-      ugeom[i].eff = j.key;
-      if ((!j.key->bpl || bases_alt<Fq>(ctx, j.key, &ugeom[i].eff) == AMSM_OK) && bps_unit_geom_ok(geom_ctx(ctx), geom_key(ugeom[i].eff), j.off, j.n, &ugeom[i].g)) {
-        ugeom[i].g.skip_ones = j.skip_ones ? 1u : 0u;
-        b.geom_ok = true;
-        b.slot_bytes = bps_slot_bytes<Fq>(ugeom[i].g);
-      }
+      uj[i] = mjobs::UnitJob{ki, j.off, j.n, j.mont, j.group_shift, j.share.buf >= 0, j.force_chunked, j.skip_ones};
     }
-    n_units = msel::batch_units(bj.data(), bj.size(), sw, units.data());
+    // the key a unit's MSMs would run over: a 20-bit key's twin, built on first use -- asked for once per key (one that cannot be
+    // had is the single path's to report: the jobs then stay singles)
+    for (size_t ki = 0; ki < keys.size(); ki++)
+      if (mjobs::units_need_twin(pc, keys[ki], ki, uj.data(), uj.size()) && bases_alt<Fq>(ctx, (const amsm_bases*)keys[ki].id, &twin[ki]) == AMSM_OK)
+        keys[ki] = job_key((const amsm_bases*)keys[ki].id, twin[ki]);
+    n_units = mjobs::plan_units(pc, keys.data(), uj.data(), uj.size(), xyzz_bytes<Fq>(), units.data(), ugeom.data());
     ujobs.reserve(live.size());
     for (size_t i : live) ujobs.push_back(jobs[i]);
   } else {
@@ -1076,7 +1046,8 @@ int msm_multi_xyzz(amsm_ctx* ctx, const std::vector<MsmJob>& jobs, std::vector<h
       [&](size_t u, Slot* sl) -> int {
         const msel::Unit un = units[u];
         if (un.count == 1) return msm_enqueue<Fq, Fr>(ctx, sl, jobs[live[un.first]], place_of(u, n_units));
-        int r = msm_enqueue_bps_batch<Fq, Fr>(ctx, sl, &ujobs[un.first], un.count, ugeom[un.first], place_of(u, n_units));
+        const BpsUnitGeom found{ugeom[un.first].g, ugeom[un.first].over_twin ? twin[uj[un.first].key] : ujobs[un.first].key};
+        int r = msm_enqueue_bps_batch<Fq, Fr>(ctx, sl, &ujobs[un.first], un.count, found, place_of(u, n_units));
         if (r != AMSM_E_OOM) return r;
         // the unit's buffers could not be had (nothing was launched): its MSMs singly on this slot, the last one left to the ring
         (void)hipGetLastError();
@@ -1112,7 +1083,7 @@ int msm_device_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t base_off, con
     *out = host::hx_inf<Fq>();
     return AMSM_OK;
   }
-  const bool probe_wanted = ctx->bpl_probe && msel::wants_skew_probe(key_desc(bases), n, switches_of(ctx));
+  const bool probe_wanted = mjobs::probe_wanted(plan_ctx(ctx), key_desc(bases), n);
   // (long single vectors are worth the two-valued probe's synchronisation: ~20 us against 0.45 ms and up)
   const bool split = split_needed(ctx, bases, n) || probe_wanted || (ctx->two_valued && n >= ((size_t)1 << 17));  // windows of the key / the probes
   std::vector<host::HXYZZ<Fq>> r;
@@ -1140,7 +1111,6 @@ int msm_multi_split_impl(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, std::ve
 // Four steps, plain data between them: tv_probe (launch the probes, one synchronisation), msel::classify (msm_select.h),
 // tv_launch_sums (the sums on their own stream), then msm_multi_split_xyzz runs the rest and finishes on the host.
 constexpr size_t TV_MIN_PAIRS = (size_t)1 << 14;
-constexpr u32 TV_ONES_MIN_SAMPLES = msel::TV_ONES_MIN_SAMPLES;
 constexpr size_t TV_PW = TV_PROBE_WORDS, TV_PB = TV_PROBE_WORDS * 4;  // probe block per vector: words, bytes
 template <class Fq>
 constexpr size_t tv_exc_rec() { return (8 + 2 * Fq::W) * 4; }  // one exception record: the scalar, its generator
@@ -1372,48 +1342,16 @@ int msm_multi_split_impl(amsm_ctx* ctx, const std::vector<MsmJob>& vecs, std::ve
   out->assign(k, host::hx_inf<Fq>());
   if (k == 0) return AMSM_OK;
   const amsm_bases* bases = vecs[0].key;
-  // the digit probe's verdicts (msm_select.h: wants_skew_probe): a skewed vector over a 20-bit key runs chunked over the twin, cut by
-  // ITS rule; over any other precomputed key it runs chunked over the same key (force_chunked)
+  // the digit probe's verdicts (msm_select.h: wants_skew_probe), where the pipelines want them for this key
   std::vector<uint8_t> skew(k, 0);
-  const amsm_bases* alt = nullptr;
   size_t probe_min = 0;
   DigitWalk probe_walk;
-  const bool probed = skew_probe_params(ctx, bases, vecs, &probe_min, &probe_walk) != 0;
-  if (probed) {
+  if (skew_probe_params(ctx, bases, vecs, &probe_min, &probe_walk) != 0) {
     if (pre_skew) skew = *pre_skew;
     else TRY(bpl_probe_device<Fr>(ctx, vecs, &skew, probe_walk, probe_min));
   }
-  if (probed && bases->bpl) {
-    for (size_t v = 0; v < k; v++)
-      if (skew[v] && !alt) TRY(bases_alt<Fq>(ctx, bases, &alt));
-  } else if (probed) {
-    bool any_split = false;
-    for (size_t v = 0; v < k; v++) any_split = any_split || split_needed(ctx, bases, vecs[v].n);
-    if (any_split) std::fill(skew.begin(), skew.end(), 0);  // (longer than 2^21: ranges of the key, chunked anyway)
-  }
-  std::vector<MsmJob> jobs;  // the vectors' ranges; owner: the vector's place in `vecs`
-  for (size_t v = 0; v < k; v++) {
-    MsmJob vec = vecs[v];
-    vec.owner = v;
-    vec.key = skew[v] && bases->bpl ? alt : bases;
-    vec.force_chunked = skew[v] && !bases->bpl;
-    const amsm_bases* key = vec.key;
-    const bool split = split_needed(ctx, key, vec.n);
-    const size_t first_job = jobs.size();
-    // (an empty vector stays one empty job: a batch with one is no batch of direct sums, msm_multi_xyzz)
-    cut_into_ranges(vec, split ? split_chunk(ctx, key) : std::max<size_t>(vec.n, 1), &jobs);
-    // Round 5: the ranges of one vector over a bucket-per-lane key share ONE bucket set (struct Share) -- every leading range
-    // that takes that pipeline; a short last range (below a quarter of the window: the twin's pipelines) stays an MSM of its own
-    if (split && ctx->share_buckets && key->bpl && key->precomp && ctx->bpl && jobs.size() - first_job >= 2) {
-      size_t n_sh = 0;
-      MsmGeom g;
-      while (first_job + n_sh < jobs.size() &&
-             choose_pipeline(ctx, key, jobs[first_job + n_sh].n, -1, false).pipeline == msel::BUCKET_PER_LANE &&
-             bpl_geom(geom_ctx(ctx), geom_key(key), jobs[first_job + n_sh].off, jobs[first_job + n_sh].n, -1, 0, &g) && g.n_sets == 1u)
-        n_sh++;
-      if (n_sh >= 2) TRY(arm_shared_set<Fq>(ctx, jobs, first_job, n_sh, g.B));
-    }
-  }
+  std::vector<MsmJob> jobs;  // the vectors' ranges (msm_jobs.h: plan_ranges, the device form); owner: the vector's place in `vecs`
+  TRY(plan_jobs<Fq>(ctx, bases, vecs, skew.data(), mjobs::device_form(), &jobs));
   std::vector<host::HXYZZ<Fq>> part;
   std::vector<uint8_t> ovf;
   TRY((msm_multi_xyzz<Fq, Fr>(ctx, jobs, &part, &ovf)));
@@ -1458,30 +1396,9 @@ bool host_ptr_pinned(const void* p) {
 // that a buffer is rewritten only after the MSM that read it was collected (a bucket-per-lane MSM may be re-run from it,
 // msm_collect): upload(j + RING) is issued after enqueue(j + RING - 1), which collected MSM j's slot long before.
 // Long vectors over a precomputed key are cut into the same windows as msm_multi_split_xyzz cuts device vectors.
-// Does a host slice LOOK two-valued (every scalar 0 or one value v -- the reference harness's `vec![rand; len]` inputs and the
-// DummyCircuit's constant A z, B z, C z)?  1024 evenly spaced samples with at most one non-zero value among them.  The exact test
-// is the device probe's (k_tv_probe); this only decides whether the slices go there.
-inline bool host_looks_two_valued(const uint64_t* s, size_t n) {
-  constexpr size_t SAMPLES = 1024;
-  const uint64_t* v = nullptr;
-  for (size_t t = 0; t < SAMPLES; t++) {
-    const uint64_t* e = s + 4 * (size_t)(((unsigned long long)t * n) / SAMPLES);
-    if (!(e[0] | e[1] | e[2] | e[3])) continue;
-    if (!v) v = e;
-    else if (memcmp(v, e, 32) != 0) return false;
-  }
-  return true;
-}
-
-// ... or hold a share of UNIT scalars (the boolean wires of a witness: msm_multi_split_xyzz sums their generators apart)?  The same
-// 1024 samples, the same threshold as the device probe's count; `one`: the unit as the slice stores it.
-inline bool host_has_unit_scalars(const uint64_t* s, size_t n, const u32 one[8]) {
-  constexpr size_t SAMPLES = 1024;
-  u32 cnt = 0;
-  for (size_t t = 0; t < SAMPLES; t++)
-    if (memcmp(s + 4 * (size_t)(((unsigned long long)t * n) / SAMPLES), one, 32) == 0) cnt++;
-  return cnt >= TV_ONES_MIN_SAMPLES;
-}
+// What the host learns about a slice before anything is uploaded -- does it LOOK two-valued (the reference harness's `vec![rand; len]`
+// inputs and the DummyCircuit's constant A z, B z, C z), does it hold a share of unit scalars, are its digits skewed -- is sampled by
+// the rules of msm_jobs.h (looks_two_valued, has_unit_scalars, skew_probe_host).
 // amsm_msm_oneshot (round 6): the generators are HOST memory too (`VariableBaseMSM::multi_scalar_mul(&[G], &[BigInt])`, the ark-ec
 // call shape: SURVEY.md section 8(b) attachment 1).  `key` is the call's temporary plain key over the context's one-shot buffer;
 // the job loop of msm_multi_host_xyzz uploads and imports the generators of a range on the copy stream right in front of that
@@ -1505,13 +1422,10 @@ int oneshot_upload_range(amsm_ctx* ctx, const amsm_bases* key, const OneshotBase
   return AMSM_OK;
 }
 // Round 6 -- a LONE host slice of [3 x 2^18, 2^20] pairs over a 20-bit key (the reference's `commit(&ck, &[Fr], ..)`: one blocking call at a
-// time, src/hp_as/mod.rs:372-385,911-918) used to be upload (0.6 ms) + MSM (1.4 ms) in series by construction.  It now runs as TWO
-// ranges over ONE bucket set (struct Share: range 1 writes the set, range 2 adds to it and carries the only tail): the second half
-// crosses the link while the first half is sorted and accumulated.  A range whose digits turn out skewed sends the call back to the
-// one-range form (no_halves).
-inline bool host_halves_apply(const amsm_ctx* ctx, const amsm_bases* key, size_t len) {
-  return ctx->host_halves && ctx->share_buckets && ctx->bpl && key->bpl && key->precomp && len >= ((size_t)3 << 18) && len <= ((size_t)1 << 20);  // (measured at 2^20: 2.03 -> 1.90 ms; thinner halves fill the 2^19 buckets too thinly)
-}
+// time, src/hp_as/mod.rs:372-385,911-918) runs as TWO ranges over ONE bucket set (struct Share: range 1 writes the set, range 2 adds to
+// it and carries the only tail): msm_jobs.h: halves_apply has the rule and its measurements.  A range whose digits turn out skewed sends
+// the call back to the one-range form (no_halves).
+inline bool host_halves_apply(const amsm_ctx* ctx, const amsm_bases* key, size_t len) { return mjobs::halves_apply(plan_ctx(ctx), key_desc(key), len); }
 template <class Fq, class Fr>
 int msm_multi_host_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const size_t* offs, const uint64_t* const* h_scalars,
                         const size_t* ns, int scalars_mont, std::vector<host::HXYZZ<Fq>>* out, const OneshotBases* os = nullptr,
@@ -1523,29 +1437,29 @@ int msm_multi_host_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const 
   // histogram of the skew probe.  Round 5: the samples are 1024 cache and TLB misses per look and the histogram 13 windows of
   // them -- ~0.1 ms per slice, serial in front of the first upload: 1.1-1.3 ms of a 17.5 ms call of twelve 2^20-scalar slices
   // (rocprofv3 timeline against the call's wall clock, profiles/r05_host_slices.md).  Now one task per DISTINCT slice on the host pool.
-  std::vector<uint8_t> looks_tv(k, 0), skew_bps(k, 0), skew_bpl(k, 0);
+  std::vector<uint8_t> looks_tv(k, 0), skew(k, 0);
   {
-    const bool want_probe = ctx->bpl_probe && bases->precomp;
+    const mjobs::PlanCtx pc = plan_ctx(ctx);
+    const msel::KeyDesc kd = key_desc(bases);
     std::vector<size_t> all(k);
     for (size_t v = 0; v < k; v++) all[v] = v;
     const std::vector<size_t> first = first_identical(vecs, all);
     HostPool::get().run(k, [&](size_t v) {
       if (first[v] != v || !h_scalars[v]) return;
       const size_t len = vecs[v].n;
-      if (ctx->two_valued && len >= TV_MIN_PAIRS) looks_tv[v] = host_looks_two_valued(h_scalars[v], len);
+      if (ctx->two_valued && len >= TV_MIN_PAIRS) looks_tv[v] = mjobs::looks_two_valued(h_scalars[v], len);
       if (!looks_tv[v] && ctx->two_valued && len >= TV_MIN_PAIRS && !bases->bpl) {  // (a witness with boolean wires goes there too)
         u32 one_words[8] = {1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
         if (scalars_mont)
           for (int i = 0; i < 8; i++) one_words[i] = Fr::one(i);
-        looks_tv[v] = host_has_unit_scalars(h_scalars[v], len, one_words);
+        looks_tv[v] = mjobs::has_unit_scalars(h_scalars[v], len, one_words);
       }
       if (looks_tv[v]) return;  // (such a call goes to the device path's exact probe: the digit verdicts are not used)
-      if (want_probe && msel::wants_skew_probe(key_desc(bases), len, switches_of(ctx))) {
-        const bool sk = bpl_probe_host<Fr>(h_scalars[v], len, scalars_mont, key_walk(bases), bases->bpl ? bpl_min_pairs(bases) : BPS_MIN_PAIRS);
-        (bases->bpl ? skew_bpl : skew_bps)[v] = sk;
-      }
+      // (a skewed slice -- the constant hiding vectors of the zk provers -- would pay an aborted prep plus a re-run)
+      if (mjobs::probe_wanted(pc, kd, len))
+        skew[v] = bpl_probe_host<Fr>(h_scalars[v], len, scalars_mont, mjobs::key_walk(geom_key(bases)), mjobs::probe_min_len(kd));
     });
-    for (size_t v = 0; v < k; v++) looks_tv[v] = looks_tv[first[v]], skew_bps[v] = skew_bps[first[v]], skew_bpl[v] = skew_bpl[first[v]];
+    for (size_t v = 0; v < k; v++) looks_tv[v] = looks_tv[first[v]], skew[v] = skew[first[v]];
   }
   // Round 4: slices that look two-valued take the device path's exact probe and its n-addition form (4.2d) -- a constant vector of
   // 2^20 scalars is 0.3 ms there against ~3 ms through the skew fallback here.  All slices of the call are copied into one staging
@@ -1570,43 +1484,13 @@ int msm_multi_host_xyzz(amsm_ctx* ctx, const amsm_bases* bases, size_t k, const 
       return msm_multi_split_xyzz<Fq, Fr>(ctx, vecs, out);
     }
   }
-  std::vector<MsmJob> jobs;  // the slices' ranges (scalars: host pointers)
+  // the slices' ranges (msm_jobs.h: plan_ranges, the host form; scalars: host pointers): long slices cut like device vectors, the
+  // lone slice in two halves over one bucket set (host_halves_apply above), a one-shot call by its own step
+  std::vector<MsmJob> jobs;
+  TRY(plan_jobs<Fq>(ctx, bases, vecs, skew.data(), mjobs::host_form(k, os != nullptr, os ? os->step : 0, no_halves), &jobs));
   size_t n_max = 0;
-  const amsm_bases* alt = nullptr;
-  bool halved = false;
-  for (size_t v = 0; v < k; v++) {
-    const size_t len = vecs[v].n;
-    const amsm_bases* key = bases;
-    // bucket-split candidates (2^16 .. 2^17 pairs over a precomputed key): the same 1024-sample look at the digits the device
-    // vectors get -- a skewed slice (the constant hiding vectors of the zk provers) would pay an aborted prep plus a re-run
-    const bool force_chunked = skew_bps[v] != 0;
-    if (skew_bpl[v]) {
-      if (!alt) TRY(bases_alt<Fq>(ctx, bases, &alt));
-      key = alt;
-    }
-    const size_t chunk = split_chunk(ctx, key);
-    const bool split = chunk && split_needed(ctx, key, len);
-    size_t step = (os && os->step) ? os->step : (split ? chunk : std::max<size_t>(len, 1));
-    // the lone slice in two halves over one bucket set (host_halves_apply above)
-    MsmGeom hg;
-    const size_t h1 = ((len + 1) / 2 + 63) & ~(size_t)63;
-    const bool halve = !no_halves && !os && k == 1 && key == bases && !split && !force_chunked && host_halves_apply(ctx, key, len) &&
-                       choose_pipeline(ctx, key, h1, -1, false).pipeline == msel::BUCKET_PER_LANE &&
-                       choose_pipeline(ctx, key, len - h1, -1, false).pipeline == msel::BUCKET_PER_LANE &&
-                       bpl_geom(geom_ctx(ctx), geom_key(key), vecs[v].off, h1, -1, 0, &hg) && hg.n_sets == 1u;
-    if (halve) step = h1;
-    if (len) {  // (an empty slice is no job here)
-      MsmJob vec = vecs[v];
-      vec.key = key;
-      vec.force_chunked = force_chunked;
-      cut_into_ranges(vec, step, &jobs);
-      n_max = std::max(n_max, std::min(step, len));
-    }
-    if (halve && jobs.size() == 2) {
-      TRY(arm_shared_set<Fq>(ctx, jobs, 0, 2, hg.B));
-      halved = true;
-    }
-  }
+  for (const MsmJob& j : jobs) n_max = std::max(n_max, j.n);
+  const bool halved = !jobs.empty() && jobs[0].share.buf >= 0;  // (the only shared set of this form)
   if (jobs.empty()) return AMSM_OK;
   const size_t J = jobs.size();
   std::vector<host::HXYZZ<Fq>> part;

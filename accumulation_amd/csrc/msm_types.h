@@ -126,6 +126,13 @@ AMSM_GEOM_FN DigitWalk digit_walk_of(const MsmGeom& g) {
   d.skip_ones = g.skip_ones;
   return d;
 }
+// The skew probe's sampling (host: msm_jobs.h skew_probe_host, device: vec_kernels.h k_skew_probe -- stated here once, for both):
+// PROBE_SAMPLES evenly spaced samples, per window a histogram of their non-zero digits hashed into PROBE_BINS bins; the vector is
+// skewed when a bin reaches PROBE_LIMIT (uniform digits put at most ~6 samples into a bin)
+constexpr u32 PROBE_SAMPLES = 1024, PROBE_BINS = 2048, PROBE_LIMIT = 24;
+static_assert(PROBE_BINS == 1u << 11, "probe_bin keeps the top 11 bits of the hash");
+AMSM_GEOM_FN u64 probe_sample(u32 t, u64 n) { return ((u64)t * n) / PROBE_SAMPLES; }  // the index of sample t of n scalars
+AMSM_GEOM_FN u32 probe_bin(u32 d) { return (d * 2654435761u) >> 21; }
 // windows of a width-c walk: W c >= 256 (signed digits need one spare bit); entry slots per scalar
 AMSM_GEOM_FN int windows_for(int c) { return 255 / c + 1; }
 AMSM_GEOM_FN int slots_for(int c) { return windows_for(c); }

@@ -663,13 +663,13 @@ __global__ void __launch_bounds__(256) k_vec_sample(u32* __restrict__ out, blind
 
 // ---------------------------------------------------------------------------------------------
 // Skew probe (round 3): would this scalar vector overflow the bucket-per-lane prep?  1024 evenly spaced samples, signed
-// c-bit digits as the prep computes them; per window a 2048-bin histogram of the non-zero digits (hashed) in LDS.  Uniform
+// c-bit digits as the prep computes them; per window a 2048-bin histogram of the non-zero digits (hashed) in LDS (msm_types.h:
+// PROBE_SAMPLES, PROBE_BINS, PROBE_LIMIT, probe_sample, probe_bin -- the host's probe of a slice uses the same).  Uniform
 // digits put at most ~6 samples into a bin; a constant vector (`vec![x; len]`), a vector with a large share of
 // equal or of few distinct values puts hundreds.  *flag = 1 when any bin reaches PROBE_LIMIT.  An optimisation only: the
 // host then sends the vector straight to the chunked pipeline instead of finding out from the prep's overflow flag (which
 // stays the safety net for what 1024 samples miss).  One 1024-lane workgroup.
 // ---------------------------------------------------------------------------------------------
-constexpr u32 PROBE_SAMPLES = 1024, PROBE_BINS = 2048, PROBE_LIMIT = 24;
 template <class Fr>
 // tv (may be null): the vector's k_tv_probe words, written earlier on the same stream -- a two-valued vector never reaches the
 // pipelines this probe protects, so there is nothing to look at
@@ -680,7 +680,7 @@ __global__ void __launch_bounds__(1024) k_skew_probe(const u32* __restrict__ sca
   if (tv && tv[0] == 0u && (tv[1] == 1u || tv[2] == 1u)) return;
   const u32 t = threadIdx.x;
   if (t == 0) worst = 0;
-  const u32 i = (u32)(((u64)t * n) / PROBE_SAMPLES);
+  const u32 i = (u32)probe_sample(t, n);
   Fe<Fr> s = fe_load<Fr>(scalars + (size_t)i * 8);
   if (dw.skip_ones) fe_drop_stored_one<Fr>(s, mont);
   if (mont) s = fe_from_mont<Fr>(s);
@@ -692,7 +692,7 @@ __global__ void __launch_bounds__(1024) k_skew_probe(const u32* __restrict__ sca
     u32 neg;
     const u32 d = digit_step<Fr>(s, dw, w, carry, neg);
     u32 seen = 0;
-    if (d != 0 && t < n) seen = atomicAdd(&bins[(d * 2654435761u) >> 21], 1u) + 1u;
+    if (d != 0 && t < n) seen = atomicAdd(&bins[probe_bin(d)], 1u) + 1u;
     if (seen >= PROBE_LIMIT) atomicMax(&worst, seen);
     __syncthreads();
     if (worst) break;  // (uniform: read behind the barrier) a constant vector's 1024 samples serialise on ONE bin counter --
