@@ -528,7 +528,8 @@ __global__ void __launch_bounds__(256) k_ipa_fold_ip(u32* __restrict__ c, u32* _
 
 // coefficients of the succinct-check polynomial h(X) = prod_{i=1..k} (1 + xi_i X^(2^(k-i)))
 // (`SuccinctCheckPolynomial::compute_coeffs`, ext; called at src/ipa_pc_as/mod.rs:400): coefficient p is the
-// product of the challenges xi_i whose bit (k-i) is set in p.  challenges in a.coeff[0..k) (k <= VEC_MAX*4).
+// product of the challenges xi_i whose bit (k-i) is set in p.  challenges in a.xi[0..k); k <= 30, the bound amsm_ipa_check_poly_coeffs
+// and amsm_ipa_round_scalars enforce (api_entry_vec.inc) -- a.xi has room for 32, the grid's 2^k lanes for k < 32.
 struct CheckPolyArgs {
   u32 xi[32][8];
   u32 k;

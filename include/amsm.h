@@ -674,7 +674,8 @@ int amsm_ipa_round_fused(amsm_ctx* ctx, const amsm_bases* key, const uint64_t* x
                          void* d_coeffs, void* d_z, const uint64_t* fold_x_mont, const uint64_t* h_prime_xy, void* d_u,
                          uint64_t* out_lr_xy, uint8_t* out_lr_inf, uint64_t* out_ip_mont);
 /* d_out[p] (p < 2^k) = coefficients of prod_{i=1..k} (1 + xi_i X^(2^(k-i))):
- * `SuccinctCheckPolynomial::compute_coeffs` (ext), call sites src/ipa_pc_as/mod.rs:400 and under :836. k <= 32. */
+ * `SuccinctCheckPolynomial::compute_coeffs` (ext), call sites src/ipa_pc_as/mod.rs:400 and under :836.  k <= 30 (k = 0: the one
+ * coefficient 1); more challenges: AMSM_E_INVALID_ARG, d_out untouched. */
 int amsm_ipa_check_poly_coeffs(amsm_ctx* ctx, const uint64_t* xi_mont, size_t k, void* d_out);
 /* Round 6 -- the JUMP FOLD of an opening that never folded its key: after j rounds (challenges xi_mont[0 .. j), the first one pairs the
  * two halves of the key) the reference holds the folded key `key_l[i] += key_r[i] * xi` applied j times (ark_poly_commit::ipa_pc ext,
